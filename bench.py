@@ -3,11 +3,18 @@
 
 Workload (BASELINE.json configs[1]): euclidean_encoder_dynamicCenter, synthetic clips
 B=4096 per GPU, T=12, V=17, C=2, channels 2->32->16->32->64, latent 16, fp32.
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the driver's
 form), or, when WORLD_SIZE is unset, this script starts those N ranks itself as a child process BEFORE touching the
 GPU, forwards their output and exits with the child's code.
 Prints ONE JSON line on rank 0.  Inputs are resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the headline (clips/s, ms_per_step, final loss).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step left to its caller as DIR/<name>.npy:
+            the head's stats block (stats.npy, stats[0] = loss) and the model's state_dict (parameters after Adam,
+            BatchNorm running statistics, centre), one file per entry.  Weights and clips are seeded: the same arguments
+            give the same inputs in every run.
+--full adds the secondary measurements below, each outside the timed region except the dominant kernel's probe.
 
 roofline  : the step's dominant kernel -- k_layer_bwd_bpc<2,4,2,1>, layer 4's backward data path + dA / dT -- priced on SURVEY 8d's
             ALGORITHMIC bytes of that layer's backward (read dOut, read the saved input, write dIn: 104 448 B per clip) over its
@@ -131,6 +138,17 @@ def cpu_baseline(full_b: int, sample_b: int, fwd_b: int):
     return out
 
 
+def dump_outputs(d, stats, model):
+    """--dump-outputs: the stats block the last timed step returned and the model state it left, float32 (integer
+    counters as float64), one DIR/<name>.npy each (about 1 MB for the default stack)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"stats": stats, **model.state_dict()}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(d, f"{name}.npy"), a.astype(np.float32 if t.is_floating_point() else np.float64))
+
+
 def run_legs(B, rank, world, sync, steps, warmup, only=None):
     """The other shapes the north_star names, each timed like the main loop (warm-up, sync, `steps` steps, sync)."""
     import torch
@@ -247,6 +265,9 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="clips per GPU (weak scaling)")
     ap.add_argument("--head", default="euclidean", choices=["euclidean", "poincare"])
     ap.add_argument("--graph", type=int, default=int(os.environ.get("COSKAD_GRAPH", "0")))
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements: the dominant kernel's probe (inside the "
+                    "timed region), the per-kernel table, training / eval-mode forward, the legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's stats and model state as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the extra workloads (wide, V=25, VAE, Poincare, mlp)")
     ap.add_argument("--leg-steps", type=int, default=20)
@@ -337,10 +358,11 @@ def main():
     sync()
     # The step's dominant kernel is layer 4's fused backward (k_layer_bwd_bpc<2,4,2,1>: rocprof, profiles/*_kernel_instances.csv).
     # The library brackets every launch of it with HIP events on the launch stream (coskad_probe_*), inside the timed region.
+    # Only --full probes: a plain run times the steps alone.
     import ctypes
     lib = _lib.lib()
     KID_LAYER_APPLY, KID_BWD_DATA, KID_LAYER_BWD, KID_FUSED, KID_BTLNK_BWD = 1, 2, 6, 7, 8
-    probing = not args.graph and not args.profile_only
+    probing = args.full and not args.graph and not args.profile_only
     if probing:
         lib.coskad_probe_stride(8)                   # every 8th step's launch: a probed launch costs ~5 us of stream time
         lib.coskad_probe_begin(KID_BWD_DATA, CHANNELS[-1], HID)
@@ -354,10 +376,44 @@ def main():
         lib.coskad_probe_end(ctypes.byref(dom_ms_c), ctypes.byref(dom_n_c))
         lib.coskad_probe_stride(1)
     dom_ms, dom_n = dom_ms_c.value, dom_n_c.value
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stats, model)
     if args.profile_only:
         if rank == 0:
             print(json.dumps({"metric": "pose_clips_per_sec_fwd_bwd", "value": round(world * B * args.steps / dt, 1), "unit": "clips/s",
                               "ms_per_step": round(dt / args.steps * 1e3, 4), "steps": args.steps, "profile_only": True}), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    if world > 1:
+        tmax = torch.tensor([dt], device="cuda", dtype=torch.float64)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        dt = float(tmax.item())
+    loss = float(stats[0])
+    devices = [f"cuda:{dev} {torch.cuda.get_device_name(dev)}"]
+    if world > 1:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, f"rank {rank} pid {os.getpid()} {devices[0]}")
+        devices = gathered
+    fwd_b, bwd_b = algorithmic_bytes_per_clip()
+    headline = {
+        "metric": "pose_clips_per_sec_fwd_bwd", "value": round(world * B * args.steps / dt, 1), "unit": "clips/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "euclidean_encoder_dynamicCenter train step (fwd+mse-to-centre+L2 reg+bwd+Adam), "
+                               f"synthetic clips B={B}/GPU T={T} V={V} C={C_IN}, channels 2-32-16-32-64, latent 16",
+                   "clips_per_gpu": B, "global_batch": B * world, "head": args.head,
+                   "parallelism": f"dp{world}", "hip_graph": bool(args.graph)},
+        "backend": (args.backend + (" (RCCL)" if args.backend == "nccl" else "")) if world > 1 else None,
+        "world": world, "devices": devices,
+        "algorithmic_bytes_per_clip": {"fwd": fwd_b, "bwd": bwd_b},
+        "step_hbm_frac": round(world * B * args.steps / dt * (fwd_b + bwd_b) / world / (HBM_PEAK_GBS * 1e9), 4),
+        "final_loss": round(loss, 6),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
         if world > 1:
             dist.destroy_process_group()
         return
@@ -418,22 +474,11 @@ def main():
         sync()
         lib.coskad_probe_end(ctypes.byref(fz_ms), ctypes.byref(fz_n))
     model.train()
-    if world > 1:
-        tmax = torch.tensor([dt], device="cuda", dtype=torch.float64)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dt = float(tmax.item())
-    loss = float(stats[0])
-    devices = [f"cuda:{dev} {torch.cuda.get_device_name(dev)}"]
-    if world > 1:
-        gathered = [None] * world
-        dist.all_gather_object(gathered, f"rank {rank} pid {os.getpid()} {devices[0]}")
-        devices = gathered
     del eng
     torch.cuda.empty_cache()
     legs = None if (args.no_legs or args.graph) else run_legs(B, rank, world, sync, args.leg_steps, 5)
 
     if rank == 0:
-        fwd_b, bwd_b = algorithmic_bytes_per_clip()
         tvb = 4 * T * V
         # HBM traffic per launch from the committed PMC passes (rocprofv3 --pmc cannot run inside this script)
         traffic, traffic_src = {}, None
@@ -507,19 +552,7 @@ def main():
         kp_bytes = 13 * 4 * 64 * 4 * 4        # tile-major activation the fused encoder writes and the bottleneck reads back
         fused_actual = 4 * C_IN * T * V + 2 * kp_bytes + 4 * LATENT
         out = {
-            "metric": "pose_clips_per_sec_fwd_bwd", "value": round(world * B * args.steps / dt, 1), "unit": "clips/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "euclidean_encoder_dynamicCenter train step (fwd+mse-to-centre+L2 reg+bwd+Adam), "
-                                   f"synthetic clips B={B}/GPU T={T} V={V} C={C_IN}, channels 2-32-16-32-64, latent 16",
-                       "clips_per_gpu": B, "global_batch": B * world, "head": args.head,
-                       "parallelism": f"dp{world}", "hip_graph": bool(args.graph)},
-            "backend": (args.backend + (" (RCCL)" if args.backend == "nccl" else "")) if world > 1 else None,
-            "world": world, "devices": devices,
-            "algorithmic_bytes_per_clip": {"fwd": fwd_b, "bwd": bwd_b},
-            "step_hbm_frac": round(world * B * args.steps / dt * (fwd_b + bwd_b) / world / (HBM_PEAK_GBS * 1e9), 4),
-            "final_loss": round(loss, 6),
+            **headline,
             "forward_only": {"value": round(B / fwd_dt, 1), "unit": "clips/s per GPU", "ms": round(fwd_dt * 1e3, 4), "ms_blocks": [round(r * 1e3, 4) for r in reps],
                              # SURVEY 8d's target prices a LAYER-MATERIALISED forward (236 704 B/clip); the fused kernel never moves
                              # those bytes, so this is an equivalent-throughput figure, not an HBM utilisation

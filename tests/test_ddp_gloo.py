@@ -67,8 +67,14 @@ def test_two_rank_gradient_and_centre_allreduce():
     st = R.init_stse_state(2, (8, 4, 8), 8, 8, 12, 17, seed=0)
     x = R.synthetic_clips(12, seed=5)
     c = torch.full((8,), 0.05)
-    g0, s0 = _shard_grads(st, x[parallel.shard_indices(12, 0, 2)], c)
-    g1, s1 = _shard_grads(st, x[parallel.shard_indices(12, 1, 2)], c)
+    # the workers' thread count: the CPU kernels (and so their summation order) may depend on it
+    nthr = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        g0, s0 = _shard_grads(st, x[parallel.shard_indices(12, 0, 2)], c)
+        g1, s1 = _shard_grads(st, x[parallel.shard_indices(12, 1, 2)], c)
+    finally:
+        torch.set_num_threads(nthr)
     for r in range(world):
         np.testing.assert_allclose(res[r][1], ((g0 + g1) / 2).numpy(), rtol=1e-5, atol=1e-8)
         np.testing.assert_allclose(res[r][2], (s0 + s1).numpy(), rtol=1e-6)

@@ -135,3 +135,30 @@ def test_bench_dry_collectives_two_ranks_on_one_gpu():
     assert out["dry_collectives"] == "ok" and out["world"] == 2 and len(out["devices"]) == 2
     assert out["bucket_bottleneck_elems"] == 16 * 64 * 12 * 17 + 16 and out["gscale"] == 0.5 and out["steps_checked"] == 4
     assert out["bucket_bottleneck_elems"] + out["bucket_encoder_elems"] >= 239716        # every parameter is in one of the two buckets
+
+
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """A plain bench.py run times exactly --steps steps, prints only the headline and, with --dump-outputs, writes what the
+    last timed step left to its caller: its stats block (stats[0] = the loss it reports) and the model's state_dict."""
+    import json
+    import numpy as np
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "256",
+                        "--dump-outputs", str(d)], cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["metric"] == "pose_clips_per_sec_fwd_bwd" and out["unit"] == "clips/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 256 * 1e3 / out["ms_per_step"]) <= 1e-3 * out["value"]
+    assert not {"roofline", "legs", "cpu_baseline", "forward_only", "train_forward"} & set(out)      # --full only
+    from coskad_amd.models.sts.ae import STSE
+    keys = STSE(2, [32, 16, 32], 64, 16, 12, 17, 'sts_gcn', 'linear', 'euclidean', 0.0).state_dict().keys()
+    files = {p.name for p in d.iterdir()}
+    assert files == {"stats.npy"} | {f"{k}.npy" for k in keys}
+    assert sum(p.stat().st_size for p in d.iterdir()) < 64 << 20
+    stats = np.load(d / "stats.npy")
+    assert stats.dtype == np.float32 and abs(float(stats[0]) - out["final_loss"]) <= 1e-6 + 1e-5 * abs(out["final_loss"])
+    for k in keys:
+        a = np.load(d / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), k
