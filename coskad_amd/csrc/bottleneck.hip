@@ -348,6 +348,15 @@ int launch_btlnk_reduce(const float* partials, int P, size_t E, float* out, cons
   return check_launch("btlnk_bwd_reduce");
 }
 
+// btlnk_wide.hip: 16 < L <= kBtlWideMax
+constexpr int kBtlWideMax = 512;
+size_t wide_btlnk_fwd_ws_bytes(int B, int K, int L);
+size_t wide_btlnk_bwd_ws_bytes(int B, int K, int L);
+int wide_btlnk_fwd(const float* U, const float* W, const float* bias, const float* slope, float* z, void* ws, int B, int K, int L,
+                   hipStream_t stream);
+int wide_btlnk_bwd(const float* U, const float* W, const float* dz, const float* slope, float* dU, float* dW, float* db,
+                   float* dslope, void* ws, int accumulate, int B, int K, int L, hipStream_t stream);
+
 }  // namespace coskad
 
 using namespace coskad;
@@ -358,7 +367,8 @@ int coskad_btlnk_fwd_f32(const float* U, const float* W, const float* bias, cons
                          int B, int K, int L, hipStream_t stream) {
   if (!U || !W || !z) return fail(COSKAD_ERR_ARG, "btlnk_fwd: null pointer");
   if (B <= 0 || K <= 0 || L <= 0) return fail(COSKAD_ERR_ARG, "btlnk_fwd: B=%d K=%d L=%d", B, K, L);
-  if (L > 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd: latent_dim=%d > 16 not supported", L);
+  // wide latents are a split-K GEMM with a workspace: coskad_btlnk_fwd_ws_f32
+  if (L > 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd: latent_dim=%d > 16 needs the workspace entry point coskad_btlnk_fwd_ws_f32", L);
   if (K % 4) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd: K=%d must be a multiple of 4", K);
   hipLaunchKernelGGL(k_btlnk_fwd, dim3(ceil_div(B, 16)), dim3(64 * kBtlFwdWaves), 0, stream, U, W, bias, slope, z, B, K, L);
   return check_launch("btlnk_fwd");
@@ -366,13 +376,22 @@ int coskad_btlnk_fwd_f32(const float* U, const float* W, const float* bias, cons
 
 size_t coskad_btlnk_fwd_ws_bytes(int B) { return (size_t)kBtlKS * (size_t)(B > 0 ? B : 0) * 16 * sizeof(float); }
 
+size_t coskad_btlnk_fwd_ws_bytes_l(int B, int K, int L) {
+  if (L > 16 && L <= kBtlWideMax) return wide_btlnk_fwd_ws_bytes(B, K, L);
+  return coskad_btlnk_fwd_ws_bytes(B);
+}
+
 /* z = W . PReLU(U) + b like coskad_btlnk_fwd_f32, as a split-K GEMM with a caller-provided workspace of
  * coskad_btlnk_fwd_ws_bytes(B) bytes: the fast path for large batches (K must be a multiple of 16). */
 int coskad_btlnk_fwd_ws_f32(const float* U, const float* W, const float* bias, const float* slope, float* z, void* ws,
                             size_t ws_bytes, int B, int K, int L, hipStream_t stream) {
   if (!U || !W || !z || !ws) return fail(COSKAD_ERR_ARG, "btlnk_fwd_ws: null pointer");
   if (B <= 0 || K <= 0 || L <= 0) return fail(COSKAD_ERR_ARG, "btlnk_fwd_ws: B=%d K=%d L=%d", B, K, L);
-  if (L > 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_ws: latent_dim=%d > 16 not supported", L);
+  if (L > kBtlWideMax) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_ws: latent_dim=%d > %d not supported", L, kBtlWideMax);
+  if (L > 16) {
+    if (ws_bytes < wide_btlnk_fwd_ws_bytes(B, K, L)) return fail(COSKAD_ERR_WORKSPACE, "btlnk_fwd_ws: workspace too small");
+    return wide_btlnk_fwd(U, W, bias, slope, z, ws, B, K, L, stream);
+  }
   if (K % 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_ws: K=%d must be a multiple of 16", K);
   if (ws_bytes < coskad_btlnk_fwd_ws_bytes(B)) return fail(COSKAD_ERR_WORKSPACE, "btlnk_fwd_ws: workspace too small");
   float* part = reinterpret_cast<float*>(ws);
@@ -384,6 +403,7 @@ int coskad_btlnk_fwd_ws_f32(const float* U, const float* W, const float* bias, c
 }
 
 size_t coskad_btlnk_bwd_ws_bytes(int B, int K, int L) {
+  if (L > 16 && L <= kBtlWideMax) return wide_btlnk_bwd_ws_bytes(B, K, L);
   const int S = btl_chunks(B, K);
   return ((size_t)S * L * K + (size_t)S * ceil_div(K, 256) + 64) * sizeof(float);
 }
@@ -394,9 +414,10 @@ int coskad_btlnk_bwd_f32(const float* U, const float* W, const float* dz, const 
                          int B, int K, int L, hipStream_t stream) {
   if (!U || !W || !dz || !dU || !dW || !ws) return fail(COSKAD_ERR_ARG, "btlnk_bwd: null pointer");
   if (B <= 0 || K <= 0 || L <= 0) return fail(COSKAD_ERR_ARG, "btlnk_bwd: B=%d K=%d L=%d", B, K, L);
-  if (L > 16) return fail(COSKAD_ERR_SHAPE, "btlnk_bwd: latent_dim=%d > 16 not supported", L);
-  if (K % 4) return fail(COSKAD_ERR_SHAPE, "btlnk_bwd: K=%d must be a multiple of 4", K);
+  if (L > kBtlWideMax) return fail(COSKAD_ERR_SHAPE, "btlnk_bwd: latent_dim=%d > %d not supported", L, kBtlWideMax);
   if (ws_bytes < coskad_btlnk_bwd_ws_bytes(B, K, L)) return fail(COSKAD_ERR_WORKSPACE, "btlnk_bwd: workspace too small");
+  if (L > 16) return wide_btlnk_bwd(U, W, dz, slope, dU, dW, db, dslope, ws, accumulate, B, K, L, stream);
+  if (K % 4) return fail(COSKAD_ERR_SHAPE, "btlnk_bwd: K=%d must be a multiple of 4", K);
   const int S = btl_chunks(B, K);
   const int chunk = round_up(ceil_div(B, S), 16);
   const int gx = ceil_div(K, 256);

@@ -12,16 +12,11 @@
 //
 // One thread per clip: a 16-float latent lives in registers; block partials are summed in a
 // fixed order (deterministic).
+// Latents of 16 < L <= 512 are dispatched to heads_wide.hip by the entry points below.
 #include "tile_ops.h"
+#include "heads_common.h"
 
 namespace coskad {
-
-constexpr int LMAX = 16;
-constexpr float kMinNorm = 1e-5f;      // hyper_math.py:101,303
-constexpr float kBallEps = 1e-3f;      // hyper_math.py:102
-constexpr float kArtanhEps = 1e-5f;    // hyper_math.py:21
-constexpr float kMobiusEps = 1e-5f;    // hyper_math.py:179
-constexpr float kTanhClamp = 15.f;     // hyper_math.py:13
 
 struct Vec {
   float v[LMAX];
@@ -453,6 +448,11 @@ extern "C" {
 
 int coskad_head_slots(void) { return kHeadSlots; }
 size_t coskad_head_ws_floats(int B) { return (size_t)ceil_div(B, kFlatBlock) * kHeadSlots; }
+int coskad_head_slots_l(int L) { return L > 0 && L <= kWideLMax ? head_slots_for(L) : 0; }
+size_t coskad_head_ws_floats_l(int B, int L) {
+  if (L > LMAX && L <= kWideLMax) return wide_head_ws_floats(B, L);
+  return coskad_head_ws_floats(B);
+}
 
 /* Euclidean one-class head on z [B,L] (staticCenter.py:187, dynamicCenter.py:116, eval_utils.py:63-64).
  *   stats[19]: [0] = mean_{n,j} (z-c)^2 (the loss), [1..L] = sum_n z, [17] = B, [18] = sum_n |z_n|
@@ -461,7 +461,8 @@ size_t coskad_head_ws_floats(int B) { return (size_t)ceil_div(B, kFlatBlock) * k
 int coskad_mse_head_f32(const float* z, const float* c, float* dz, float* score, float* stats, float* acc,
                         float upstream, float* ws, int B, int L, hipStream_t stream) {
   if (!z || !c || !ws) return fail(COSKAD_ERR_ARG, "mse_head: null pointer");
-  if (B <= 0 || L <= 0 || L > LMAX) return fail(COSKAD_ERR_SHAPE, "mse_head: B=%d latent=%d (max %d)", B, L, LMAX);
+  if (B <= 0 || L <= 0 || L > kWideLMax) return fail(COSKAD_ERR_SHAPE, "mse_head: B=%d latent=%d (max %d)", B, L, kWideLMax);
+  if (L > LMAX) return wide_mse_head(z, c, dz, score, stats, acc, upstream, ws, B, L, stream);
   const int P = head_blocks(B);
   hipLaunchKernelGGL(k_mse_head, dim3(P), dim3(kFlatBlock), 0, stream, z, c, dz, score, ws, B, L,
                      upstream / ((float)B * (float)L), 1.f / ((float)B * (float)L), stats, acc);
@@ -477,7 +478,8 @@ int coskad_mahalanobis_head_f32(const float* z, const float* c, const float* VI,
                                 float* stats, float* acc, float* gram, int gram_accumulate, float upstream,
                                 float* ws, int B, int L, hipStream_t stream) {
   if (!z || !c || !VI || !ws) return fail(COSKAD_ERR_ARG, "mahalanobis_head: null pointer");
-  if (B <= 0 || L <= 0 || L > LMAX) return fail(COSKAD_ERR_SHAPE, "mahalanobis_head: B=%d latent=%d (max %d)", B, L, LMAX);
+  if (B <= 0 || L <= 0 || L > kWideLMax) return fail(COSKAD_ERR_SHAPE, "mahalanobis_head: B=%d latent=%d (max %d)", B, L, kWideLMax);
+  if (L > LMAX) return wide_mahalanobis_head(z, c, VI, dz, score, stats, acc, gram, gram_accumulate, upstream, ws, B, L, stream);
   const int P = head_blocks(B);
   hipLaunchKernelGGL(k_mahalanobis_head, dim3(P), dim3(kFlatBlock), 0, stream, z, c, VI, dz, score, ws, B, L,
                      upstream / (float)B, 1.f / (float)B, stats, acc);
@@ -496,7 +498,8 @@ int coskad_poincare_head_f32(const float* z, const float* c, float* dz, float* z
                              float* stats, float* acc, float upstream, float* ws, int B, int L,
                              hipStream_t stream) {
   if (!z || !ws) return fail(COSKAD_ERR_ARG, "poincare_head: null pointer");
-  if (B <= 0 || L <= 0 || L > LMAX) return fail(COSKAD_ERR_SHAPE, "poincare_head: B=%d latent=%d (max %d)", B, L, LMAX);
+  if (B <= 0 || L <= 0 || L > kWideLMax) return fail(COSKAD_ERR_SHAPE, "poincare_head: B=%d latent=%d (max %d)", B, L, kWideLMax);
+  if (L > LMAX) return wide_poincare_head(z, c, dz, zh, score, stats, acc, upstream, ws, B, L, stream);
   const int P = head_blocks(B);
   hipLaunchKernelGGL(k_poincare_head, dim3(P), dim3(kFlatBlock), 0, stream, z, c, dz, zh, score, ws, B, L,
                      upstream / (float)B, 1.f / (float)B, stats, acc);
@@ -508,14 +511,16 @@ int coskad_poincare_head_f32(const float* z, const float* c, float* dz, float* z
 /* score[n] = dist(c, zh_n) for points already on the ball (eval_utils.py:66-67). */
 int coskad_poincare_dist_f32(const float* zh, const float* c, float* score, int B, int L, hipStream_t stream) {
   if (!zh || !c || !score) return fail(COSKAD_ERR_ARG, "poincare_dist: null pointer");
-  if (B <= 0 || L <= 0 || L > LMAX) return fail(COSKAD_ERR_SHAPE, "poincare_dist: B=%d latent=%d", B, L);
+  if (B <= 0 || L <= 0 || L > kWideLMax) return fail(COSKAD_ERR_SHAPE, "poincare_dist: B=%d latent=%d (max %d)", B, L, kWideLMax);
+  if (L > LMAX) return wide_poincare_dist(zh, c, score, B, L, stream);
   hipLaunchKernelGGL(k_poincare_dist, dim3(ceil_div(B, kFlatBlock)), dim3(kFlatBlock), 0, stream, zh, c, score, B, L);
   return check_launch("poincare_dist");
 }
 
 int coskad_poincare_logmap0_f32(const float* y, float* out, int B, int L, hipStream_t stream) {
   if (!y || !out) return fail(COSKAD_ERR_ARG, "poincare_logmap0: null pointer");
-  if (B <= 0 || L <= 0 || L > LMAX) return fail(COSKAD_ERR_SHAPE, "poincare_logmap0: B=%d latent=%d", B, L);
+  if (B <= 0 || L <= 0 || L > kWideLMax) return fail(COSKAD_ERR_SHAPE, "poincare_logmap0: B=%d latent=%d (max %d)", B, L, kWideLMax);
+  if (L > LMAX) return wide_poincare_logmap0(y, out, B, L, stream);
   hipLaunchKernelGGL(k_poincare_logmap0, dim3(ceil_div(B, kFlatBlock)), dim3(kFlatBlock), 0, stream, y, out, B, L);
   return check_launch("poincare_logmap0");
 }
@@ -523,7 +528,8 @@ int coskad_poincare_logmap0_f32(const float* y, float* out, int B, int L, hipStr
 /* Euclidean centre from accumulated sums (acc layout of coskad_mse_head_f32): c = S/n with n = acc[17],
  * then |c| < eps -> +-eps (staticCenter.py:118-121). */
 int coskad_center_finalize_f32(const float* acc, float* c, float eps, int L, hipStream_t stream) {
-  if (!acc || !c || L <= 0 || L > LMAX) return fail(COSKAD_ERR_ARG, "center_finalize: bad argument");
+  if (!acc || !c || L <= 0 || L > kWideLMax) return fail(COSKAD_ERR_ARG, "center_finalize: bad argument (latent=%d, max %d)", L, kWideLMax);
+  if (L > LMAX) return wide_center_finalize(acc, c, eps, L, stream);
   hipLaunchKernelGGL(k_center_finalize, dim3(1), dim3(64), 0, stream, acc, eps, c, L);
   return check_launch("center_finalize");
 }
@@ -531,7 +537,8 @@ int coskad_center_finalize_f32(const float* acc, float* c, float eps, int L, hip
 /* Gyromidpoint (geoopt weighted_midpoint with unit weights; hyperbolic_encoder.py:122,179) from the
  * sums accumulated by coskad_poincare_head_f32. */
 int coskad_midpoint_finalize_f32(const float* acc, float* c, int L, hipStream_t stream) {
-  if (!acc || !c || L <= 0 || L > LMAX) return fail(COSKAD_ERR_ARG, "midpoint_finalize: bad argument");
+  if (!acc || !c || L <= 0 || L > kWideLMax) return fail(COSKAD_ERR_ARG, "midpoint_finalize: bad argument (latent=%d, max %d)", L, kWideLMax);
+  if (L > LMAX) return wide_midpoint_finalize(acc, c, L, stream);
   hipLaunchKernelGGL(k_midpoint_finalize, dim3(1), dim3(64), 0, stream, acc, c, L);
   return check_launch("midpoint_finalize");
 }

@@ -76,8 +76,8 @@ class LitEncoder(nn.Module):
         if stage != "fit":
             return
         dev = next(self.model.parameters()).device
-        acc = torch.zeros(ops.HEAD_SLOTS, device=dev)
         L = self.model.latent_dim
+        acc = torch.zeros(ops.head_slots(L), device=dev)
         maha = self.distance == 'mahalanobis' and not self.hyperbolic
         gram = torch.zeros(L, L, device=dev) if maha else None
         eye = torch.eye(L, device=dev) if maha else None
@@ -94,7 +94,7 @@ class LitEncoder(nn.Module):
         parallel.allreduce_sum_(acc)
         if maha:
             parallel.allreduce_sum_(gram)
-        self.n_samples = float(acc[17]) if not self.hyperbolic else None
+        self.n_samples = float(acc[ops.head_count_slot(L)]) if not self.hyperbolic else None
         if self.hyperbolic:
             c = ops.midpoint_finalize(acc, L)
             assert bool((c < 1).all()), f"center is out of the ball\nc = {c}"        # hyperbolic_encoder.py:123
@@ -322,7 +322,7 @@ class LitAutoEncoder(_AutogradLit):
         if stage != "fit":
             return
         dev = self.model.c.device
-        acc = torch.zeros(ops.HEAD_SLOTS, device=dev)
+        acc = torch.zeros(ops.head_slots(self.model.latent_dim), device=dev)
         self.model.eval()
         with torch.no_grad():
             for batch in train_loader():

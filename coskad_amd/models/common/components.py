@@ -99,7 +99,7 @@ class MLP(nn.Module):
 
     HIP path (`forward_preact`, taken by STSE / STSVAE): the first, wide Linear runs on the bottleneck kernels with the
     encoder's PReLU fused into the load, every following [BatchNorm1d, ReLU, Linear] block on csrc/mlp_head.hip.
-    Widths beyond those kernels (first hidden size > 16, later ones > 64) compose torch modules instead."""
+    Widths beyond those kernels (any hidden size or the output > 64) compose torch modules instead."""
 
     def __init__(self, input_size: int, output_size: int, hidden_layers: List[int] = None, bias=True,
                  device: Union[str, torch.device] = 'cpu', *, hidden_size: List[int] = None) -> None:
@@ -120,7 +120,8 @@ class MLP(nn.Module):
     def hip_ok(self) -> bool:
         hs = self.hidden_layers
         # (BatchNorm1d with momentum=None or without running statistics stays on the kernels: ops.bn_momentum / ops.bn_batch_stats)
-        return len(hs) >= 1 and hs[0] <= 16 and all(h <= 64 for h in hs[1:]) and self.output_size <= 64
+        # first hidden width: the bottleneck kernels (csrc/btlnk_wide.hip above 16) and the first block's input on csrc/mlp_head.hip (HMAX 64)
+        return len(hs) >= 1 and hs[0] <= 64 and all(h <= 64 for h in hs[1:]) and self.output_size <= 64
 
     def blocks(self):
         """[(bn, linear), ...]: the [BatchNorm1d, ReLU, Linear] blocks behind the first Linear."""

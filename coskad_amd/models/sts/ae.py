@@ -132,7 +132,7 @@ class STSE(nn.Module):
         else:
             U, slope = self.encoder(X), None            # plain-GCN encoders: already activated (ReLU)
         X_shape = (B, self.hidden_dimension, self.n_frames, self.n_joints, 1)
-        if isinstance(self.btlnk, nn.Linear) and self.latent_dim <= 16:
+        if isinstance(self.btlnk, nn.Linear) and self.latent_dim <= ops.BTLNK_LMAX:   # > 16: csrc/btlnk_wide.hip
             Z = _BottleneckFn.apply(U, slope, self.btlnk.weight, self.btlnk.bias, self._ws)
         elif isinstance(self.btlnk, MLP) and self.btlnk.hip_ok:
             Z = self.btlnk.forward_preact(U, slope, self._ws, _BottleneckFn.apply)

@@ -492,6 +492,15 @@ def btlnk_fwd(U: Tensor, W: Tensor, bias: Optional[Tensor], slope: Optional[Tens
     L = W.shape[0]
     _chk(U, "U"); _chk(W, "W", (L, K)); _chk(bias, "bias", (L,), optional=True); _chk(slope, "slope", (1,), optional=True)
     z = torch.empty(B, L, device=U.device, dtype=torch.float32)
+    if L > 16:
+        # 16 < L <= 512: the LDS-tiled MFMA GEMM of csrc/btlnk_wide.hip, K slices summed in a fixed order (any K)
+        fn = _lib.lib().coskad_btlnk_fwd_ws_bytes_l
+        fn.restype = ctypes.c_size_t
+        nbytes = fn(i32(B), i32(K), i32(L))
+        buf = ws.get(nbytes, U.device) if ws is not None else torch.empty(nbytes, dtype=torch.uint8, device=U.device)
+        call("coskad_btlnk_fwd_ws_f32", ptr(U), ptr(W), ptr(bias), ptr(slope), ptr(z), ptr(buf), ctypes.c_size_t(nbytes),
+             i32(B), i32(K), i32(L), _stream())
+        return z
     if B >= BTLNK_SPLITK_MIN_B and K % 16 == 0:
         # blocks of 64 clips x 4 K slices (W operands shared by four clip tiles), fixed-order partial sums
         fn = _lib.lib().coskad_btlnk_fwd_ws_bytes
@@ -506,6 +515,7 @@ def btlnk_fwd(U: Tensor, W: Tensor, bias: Optional[Tensor], slope: Optional[Tens
 
 
 BTLNK_SPLITK_MIN_B = 1      # always (K % 16 == 0): a clip's latent must not depend on the batch it arrives in (bit-exact chunking)
+BTLNK_LMAX = 512            # widest latent of the bottleneck and head kernels (csrc/btlnk_wide.hip, csrc/heads_wide.hip)
 
 
 def btlnk_bwd_ws_bytes(B, K, L) -> int:
@@ -874,23 +884,37 @@ def mlp_head_bwd(y1, stat, gamma, beta, W2, dz, grads: dict, training: bool, acc
     return dy1
 
 
-HEAD_SLOTS = 19
+HEAD_SLOTS = 19     # floats of a stats / acc block at latent <= 16 (head_slots(L) at any latent)
 
 
-def head_ws(B: int, device) -> Tensor:
-    fn = _lib.lib().coskad_head_ws_floats
+def head_slots(L: int) -> int:
+    """Floats of a head's stats / acc block at latent L (coskad_head_slots_l): with Lp = max(L, 16), [0] loss term, [1..Lp] vector
+    sum, [Lp+1] scalar A (clip count / sum (gamma - 1)), [Lp+2] scalar B.  HEAD_SLOTS at L <= 16."""
+    if not 0 < L <= BTLNK_LMAX:
+        raise ValueError(f"latent_dim={L}: the head kernels take 1 .. {BTLNK_LMAX}")
+    return max(L, 16) + 3
+
+
+def head_count_slot(L: int) -> int:
+    """Slot of scalar A (the clip count of the Euclidean / Mahalanobis sums): Lp + 1."""
+    return max(L, 16) + 1
+
+
+def head_ws(B: int, device, L: int = 16) -> Tensor:
+    fn = _lib.lib().coskad_head_ws_floats_l
     fn.restype = ctypes.c_size_t
-    return torch.empty(fn(i32(B)), device=device, dtype=torch.float32)
+    return torch.empty(fn(i32(B), i32(L)), device=device, dtype=torch.float32)
 
 
 def mse_head(z, c, need_grad=True, need_score=False, acc=None, upstream=1.0, ws=None):
-    """-> (stats[19], dz or None, score or None).  stats[0] = F.mse_loss(z, c)."""
+    """-> (stats[head_slots(L)], dz or None, score or None).  stats[0] = F.mse_loss(z, c)."""
     B, L = z.shape
-    _chk(z, "z"); _chk(c, "c", (L,)); _chk(acc, "acc", (HEAD_SLOTS,), optional=True)
-    ws = head_ws(B, z.device) if ws is None else ws
+    S = head_slots(L)
+    _chk(z, "z"); _chk(c, "c", (L,)); _chk(acc, "acc", (S,), optional=True)
+    ws = head_ws(B, z.device, L) if ws is None else ws
     dz = torch.empty_like(z) if need_grad else None
     score = torch.empty(B, device=z.device, dtype=torch.float32) if need_score else None
-    stats = torch.empty(HEAD_SLOTS, device=z.device, dtype=torch.float32)
+    stats = torch.empty(S, device=z.device, dtype=torch.float32)
     call("coskad_mse_head_f32", ptr(z), ptr(c), ptr(dz), ptr(score), ptr(stats), ptr(acc), ctypes.c_float(upstream),
          ptr(ws), i32(B), i32(L), _stream())
     return stats, dz, score
@@ -898,28 +922,30 @@ def mse_head(z, c, need_grad=True, need_score=False, acc=None, upstream=1.0, ws=
 
 def mahalanobis_head(z, c, VI, need_grad=True, need_score=False, acc=None, gram=None, gram_accumulate=True,
                      upstream=1.0, ws=None):
-    """-> (stats[19], dz or None, score or None).  stats[0] = mahalanobis(z, c, VI) (mean); gram (+)= sum z z^T."""
+    """-> (stats[head_slots(L)], dz or None, score or None).  stats[0] = mahalanobis(z, c, VI) (mean); gram (+)= sum z z^T."""
     B, L = z.shape
-    _chk(z, "z"); _chk(c, "c", (L,)); _chk(VI, "VI", (L, L)); _chk(acc, "acc", (HEAD_SLOTS,), optional=True)
+    S = head_slots(L)
+    _chk(z, "z"); _chk(c, "c", (L,)); _chk(VI, "VI", (L, L)); _chk(acc, "acc", (S,), optional=True)
     _chk(gram, "gram", (L, L), optional=True)
-    ws = head_ws(B, z.device) if ws is None else ws
+    ws = head_ws(B, z.device, L) if ws is None else ws
     dz = torch.empty_like(z) if need_grad else None
     score = torch.empty(B, device=z.device, dtype=torch.float32) if need_score else None
-    stats = torch.empty(HEAD_SLOTS, device=z.device, dtype=torch.float32)
+    stats = torch.empty(S, device=z.device, dtype=torch.float32)
     call("coskad_mahalanobis_head_f32", ptr(z), ptr(c), ptr(VI), ptr(dz), ptr(score), ptr(stats), ptr(acc), ptr(gram),
          i32(int(gram_accumulate)), ctypes.c_float(upstream), ptr(ws), i32(B), i32(L), _stream())
     return stats, dz, score
 
 
 def poincare_head(z, c, need_grad=True, need_zh=False, need_score=False, acc=None, upstream=1.0, ws=None):
-    """-> (stats[19], dz, zh, score).  stats[0] = dist(c, project(expmap0(z))).mean()."""
+    """-> (stats[head_slots(L)], dz, zh, score).  stats[0] = dist(c, project(expmap0(z))).mean()."""
     B, L = z.shape
-    _chk(z, "z"); _chk(c, "c", (L,), optional=True); _chk(acc, "acc", (HEAD_SLOTS,), optional=True)
-    ws = head_ws(B, z.device) if ws is None else ws
+    S = head_slots(L)
+    _chk(z, "z"); _chk(c, "c", (L,), optional=True); _chk(acc, "acc", (S,), optional=True)
+    ws = head_ws(B, z.device, L) if ws is None else ws
     dz = torch.empty_like(z) if (need_grad and c is not None) else None
     zh = torch.empty_like(z) if need_zh else None
     score = torch.empty(B, device=z.device, dtype=torch.float32) if (need_score and c is not None) else None
-    stats = torch.empty(HEAD_SLOTS, device=z.device, dtype=torch.float32)
+    stats = torch.empty(S, device=z.device, dtype=torch.float32)
     call("coskad_poincare_head_f32", ptr(z), ptr(c), ptr(dz), ptr(zh), ptr(score), ptr(stats), ptr(acc),
          ctypes.c_float(upstream), ptr(ws), i32(B), i32(L), _stream())
     return stats, dz, zh, score
@@ -1158,14 +1184,14 @@ def ps_head_backward(saved, dz: Tensor, w_kl: float, w_exp: float, d_mean_raw: O
 
 
 def center_finalize(acc, eps: float, L: int):
-    _chk(acc, "acc", (HEAD_SLOTS,))
+    _chk(acc, "acc", (head_slots(L),))
     c = torch.empty(L, device=acc.device, dtype=torch.float32)
     call("coskad_center_finalize_f32", ptr(acc), ptr(c), ctypes.c_float(eps), i32(L), _stream())
     return c
 
 
 def midpoint_finalize(acc, L: int):
-    _chk(acc, "acc", (HEAD_SLOTS,))
+    _chk(acc, "acc", (head_slots(L),))
     c = torch.empty(L, device=acc.device, dtype=torch.float32)
     call("coskad_midpoint_finalize_f32", ptr(acc), ptr(c), i32(L), _stream())
     return c

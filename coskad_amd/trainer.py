@@ -58,8 +58,9 @@ class FlatParams:
 
 
 def inv_cov_from_moments(gram: Tensor, acc: Tensor, mu: Tensor, L: int) -> Tensor:
-    """inverse of sum (z-mu)(z-mu)^T / (n-1), written with gram = sum z z^T, s = acc[1..L] = sum z, n = acc[17]."""
-    s, n = acc[1:1 + L].double(), acc[17].double()
+    """inverse of sum (z-mu)(z-mu)^T / (n-1), written with gram = sum z z^T, s = acc[1..L] = sum z, n = acc[Lp+1] (Lp = max(L, 16):
+    acc[17] at L <= 16)."""
+    s, n = acc[1:1 + L].double(), acc[ops.head_count_slot(L)].double()
     m = mu.double()
     S = gram.double() - torch.outer(m, s) - torch.outer(s, m) + n * torch.outer(m, m)
     return torch.inverse((S / (n - 1)).float())
@@ -99,8 +100,8 @@ class STSETrainStep:
         self.layers = [] if self.wide else [layer_tensors(l) for l in model.encoder.model]
         self.stack = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.") if self.wide else None
         self.ws = engine.Workspace()
-        self.center_acc = torch.zeros(ops.HEAD_SLOTS, device=dev, dtype=torch.float32)
         L = model.latent_dim
+        self.center_acc = torch.zeros(ops.head_slots(L), device=dev, dtype=torch.float32)
         self.gram_acc = torch.zeros(L, L, device=dev, dtype=torch.float32) if head == 'mahalanobis' else None
         self.reg_scale = 0.5 / self.fp.n_reg_tensors          # calc_reg_loss value = reg_scale * sum p^2
         self.reg_coef = self.alpha * 2.0 * self.reg_scale      # its gradient coefficient, times alpha
@@ -557,7 +558,7 @@ class STSAETrainStep:
             self.dec = _FlatStack(dec_layers[1:], self.fp, "decoder.model.", first=1)
         else:
             self.dec = _FlatStack(dec_layers, self.fp, "decoder.model.")
-        self.center_acc = torch.zeros(ops.HEAD_SLOTS, device=dev, dtype=torch.float32)
+        self.center_acc = torch.zeros(ops.head_slots(model.latent_dim), device=dev, dtype=torch.float32)
         self.reg_scale = 0.5 / self.fp.n_reg_tensors
         self.reg_coef = self.alpha * 2.0 * self.reg_scale
         self.steps = 0
@@ -569,7 +570,7 @@ class STSAETrainStep:
         from .models.common.components import MLP
         if isinstance(model, STSVAE):
             if isinstance(model.btlnk, MLP):              # `projector: 'mlp'` (spherical_vae.yaml:37): MLP, then the heads on its output
-                return model.btlnk.hip_ok and model.latent_dim <= 16
+                return model.btlnk.hip_ok and model.btlnk.hidden_layers[0] <= 16 and model.latent_dim <= 16
             return isinstance(model.btlnk, torch.nn.Identity) and model.latent_dim + model.fc_var.out_features <= 16
         return isinstance(model.btlnk, torch.nn.Linear) and model.latent_dim <= 16
 
@@ -740,8 +741,8 @@ class AutogradTrainStep:
         self.reg_scale = 0.5 / max(1, len(self.reg_params))
         self.opt = torch.optim.Adam([p for _, p in self.params], lr=lr, betas=betas, eps=eps)
         dev = self.params[0][1].device
-        self.center_acc = torch.zeros(ops.HEAD_SLOTS, device=dev, dtype=torch.float32)
         L = model.latent_dim
+        self.center_acc = torch.zeros(ops.head_slots(L), device=dev, dtype=torch.float32)
         self.gram_acc = torch.zeros(L, L, device=dev, dtype=torch.float32) if head == 'mahalanobis' else None
         self.steps = 0
 
@@ -796,7 +797,7 @@ def make_train_step(model, **kw):
     from .models.common.components import MLP
     btl = getattr(model, 'btlnk', None)
     proj_ok = isinstance(btl, torch.nn.Linear) or (isinstance(btl, MLP) and btl.hip_ok)
-    fast = proj_ok and isinstance(getattr(model, 'encoder', None), Encoder) and model.latent_dim <= 16
+    fast = proj_ok and isinstance(getattr(model, 'encoder', None), Encoder) and model.latent_dim <= ops.BTLNK_LMAX
     if fast:
         if any(l.is_wide for l in model.encoder.model):     # wide layers: main stream, eager launches
             kw.pop('use_graph', None); kw.pop('side_stream', None)

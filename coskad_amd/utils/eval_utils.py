@@ -155,8 +155,8 @@ def rec_and_hy_window_scores(x: torch.Tensor, x_rec: torch.Tensor, z: torch.Tens
     rec = ((x_rec - x) ** 2).reshape(B, -1).mean(-1)
     if loss_type == 'rec':
         return rec
-    if z.is_cuda and z.shape[1] <= 16:           # the head kernel keeps a latent in 16 lanes; wider latents: torch expression
-        from .. import ops
+    from .. import ops
+    if z.is_cuda and z.shape[1] <= ops.BTLNK_LMAX:   # the head kernels take latents up to 512; wider ones: torch expression
         _, _, hyp = ops.mse_head(z.contiguous().float(), c.float().contiguous(), need_grad=False, need_score=True)
     else:
         hyp = ((z - c) ** 2).mean(-1)

@@ -336,17 +336,21 @@ int coskad_gcn_bwd_params_dx_f32(const float* x, const float* dZ, const float* A
 
 /* ---- bottleneck Linear (models/sts/ae.py:97-101,157) ---------------------------------- */
 
-/* z[n][j] = bias[j] + sum_k W[j][k] * PReLU_slope(U[n][k]);  slope NULL: no activation. L <= 16. */
+/* z[n][j] = bias[j] + sum_k W[j][k] * PReLU_slope(U[n][k]);  slope NULL: no activation. L <= 16 (wider: the _ws entry point). */
 int coskad_btlnk_fwd_f32(const float* U, const float* W, const float* bias, const float* slope, float* z,
                          int B, int K, int L, hipStream_t stream);
 
 /* The same as a split-K GEMM (blocks of 64 clips x 8 K slices, fixed-order sum of the partials) with a workspace of
  * coskad_btlnk_fwd_ws_bytes(B) bytes: the large-batch path; K must be a multiple of 16. */
 size_t coskad_btlnk_fwd_ws_bytes(int B);
+/* Workspace bytes of coskad_btlnk_fwd_ws_f32 at any latent L <= 512: coskad_btlnk_fwd_ws_bytes(B) at L <= 16; above, the K-slice
+ * partials of the wide GEMM (csrc/btlnk_wide.hip; any K).  coskad_btlnk_fwd_f32 (no workspace) stays at L <= 16. */
+size_t coskad_btlnk_fwd_ws_bytes_l(int B, int K, int L);
 int coskad_btlnk_fwd_ws_f32(const float* U, const float* W, const float* bias, const float* slope, float* z, void* ws,
                             size_t ws_bytes, int B, int K, int L, hipStream_t stream);
 size_t coskad_btlnk_bwd_ws_bytes(int B, int K, int L);
-/* dU = (dz W) * PReLU'(U);  dW (+)= dz^T PReLU(U);  db (+)= sum_n dz;  dslope (+)= sum (dz W) U [U<0] */
+/* dU = (dz W) * PReLU'(U);  dW (+)= dz^T PReLU(U);  db (+)= sum_n dz;  dslope (+)= sum (dz W) U [U<0].
+ * coskad_btlnk_fwd_ws_f32 / coskad_btlnk_bwd_f32 at 16 < L <= 512: fp32 MFMA GEMMs tiled in LDS (csrc/btlnk_wide.hip), any K. */
 int coskad_btlnk_bwd_f32(const float* U, const float* W, const float* dz, const float* slope, float* dU,
                          float* dW, float* db, float* dslope, void* ws, size_t ws_bytes, int accumulate,
                          int B, int K, int L, hipStream_t stream);
@@ -378,10 +382,16 @@ int coskad_gather_transform_f32(const float* xy, const long long* index, const f
 
 /* ---- one-class heads, centre statistics, regulariser, optimiser ------------------------ */
 
-int coskad_head_slots(void);            /* floats in a stats / acc block (19) */
-size_t coskad_head_ws_floats(int B);    /* scratch floats the head kernels need */
+int coskad_head_slots(void);            /* floats in a stats / acc block (19) at latent <= 16 */
+size_t coskad_head_ws_floats(int B);    /* scratch floats the head kernels need at latent <= 16 */
+/* The same at latent L <= 512 (csrc/heads_wide.hip above 16): with Lp = max(L, 16) a stats / acc block holds Lp + 3 floats,
+ * [0] loss term, [1..Lp] vector sum, [Lp+1] scalar A, [Lp+2] scalar B -- the 19-slot layout at L <= 16.  0 beyond 512. */
+int coskad_head_slots_l(int L);
+size_t coskad_head_ws_floats_l(int B, int L);
 
-/* F.mse_loss(z, c) (euclidean_encoder_staticCenter.py:187, _dynamicCenter.py:116), its gradient,
+/* Every head, centre and midpoint entry point takes latents L <= 512; stats / acc then hold coskad_head_slots_l(L) floats
+ * ([17], [18] below read [Lp+1], [Lp+2]) and ws coskad_head_ws_floats_l(B, L) floats.
+ * F.mse_loss(z, c) (euclidean_encoder_staticCenter.py:187, _dynamicCenter.py:116), its gradient,
  * the per-window score of utils/eval_utils.py:63-64, and the running-centre sums (:172-178).
  * stats: [0] loss, [1..L] sum_n z, [17] B, [18] sum_n |z_n|;  acc += raw sums. */
 int coskad_mse_head_f32(const float* z, const float* c, float* dz, float* score, float* stats, float* acc,
