@@ -10,8 +10,6 @@ sync_batchnorm).
 """
 from __future__ import annotations
 
-import os
-
 from typing import Dict, List, Optional
 
 import torch
@@ -66,219 +64,15 @@ def inv_cov_from_moments(gram: Tensor, acc: Tensor, mu: Tensor, L: int) -> Tenso
     return torch.inverse((S / (n - 1)).float())
 
 
-class STSETrainStep:
-    """One-class training of an STSE (`linear` projector, or `mlp` within the HIP kernels' widths) without autograd.
-
-    head: 'euclidean' -> F.mse_loss(z, c);  'poincare' -> dist(c, project(expmap0(z))).mean().
-    """
-
-    def __init__(self, model, lr: float = 1e-4, alpha: float = 1e-6, head: str = 'euclidean',
-                 betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, use_graph: bool = False,
-                 side_stream: bool = False, sync_bn: bool = False) -> None:
-        from .models.sts.ae import STSE
-        from .models.common.components import MLP
-        self.mlp = isinstance(model.btlnk, MLP)
-        if not isinstance(model, STSE) or not (isinstance(model.btlnk, torch.nn.Linear) or (self.mlp and model.btlnk.hip_ok)):
-            raise TypeError("STSETrainStep drives an STSE with projector='linear' or an 'mlp' within the kernels' widths")
-        self.model, self.head, self.alpha = model, head, float(alpha)
-        self.beta1, self.beta2, self.eps = float(betas[0]), float(betas[1]), float(eps)
-        self.pg = process_group
-        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
-        self.fp = FlatParams(model)
-        dev = self.fp.flat.device
-        self.m = torch.zeros_like(self.fp.flat)
-        self.v = torch.zeros_like(self.fp.flat)
-        self.hyper = torch.tensor([lr, 1.0, 1.0, 0.0], device=dev, dtype=torch.float32)
-        self.lr = float(lr)
-        # an encoder with layers beyond the LDS tile kernels (the wide C = 2 -> 256 stack, dropout) runs as a _FlatStack: tile runs
-        # through engine.chain_*, wide layers through their explicit forward / backward -- same flat buffers, same fused Adam
-        # (so does an encoder with a layer the commuted kernels take -- 32 -> 16 on the 25-joint layout -- unless the step is asked for
-        # something only the plain chain does: hipGraph capture, the side stream, SyncBN)
-        self.wide = any(l.is_wide for l in model.encoder.model)
-        if not self.wide and not (use_graph or side_stream or sync_bn):
-            self.wide = any(_is_commute(l) for l in model.encoder.model)
-        self.layers = [] if self.wide else [layer_tensors(l) for l in model.encoder.model]
-        self.stack = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.") if self.wide else None
-        self.ws = engine.Workspace()
-        L = model.latent_dim
-        self.center_acc = torch.zeros(ops.head_slots(L), device=dev, dtype=torch.float32)
-        self.gram_acc = torch.zeros(L, L, device=dev, dtype=torch.float32) if head == 'mahalanobis' else None
-        self.reg_scale = 0.5 / self.fp.n_reg_tensors          # calc_reg_loss value = reg_scale * sum p^2
-        self.reg_coef = self.alpha * 2.0 * self.reg_scale      # its gradient coefficient, times alpha
-        # gradient views per layer, in the kernels' vocabulary
-        self.grads: List[Dict[str, Tensor]] = []
-        for i, L in enumerate(self.layers):
-            pre = f"encoder.model.{i}."
-            g = {"A": pre + "gcn.A", "T": pre + "gcn.T", "Wt": pre + "tcn.0.weight", "bt": pre + "tcn.0.bias",
-                 "gt": pre + "tcn.1.weight", "bet": pre + "tcn.1.bias", "Wr": pre + "residual.0.weight",
-                 "br": pre + "residual.0.bias", "gr": pre + "residual.1.weight", "ber": pre + "residual.1.bias",
-                 "slope": pre + "prelu.weight"}
-            self.grads.append({k: self.fp.gviews[n] for k, n in g.items() if n in self.fp.gviews})
-        # optional: dA / dT on a second stream beside the next layer's reductions.  Measured SLOWER on MI355X (2.43 vs
-        # 2.28 ms/step: the two LDS-heavy persistent kernels halve each other's occupancy), so it is off by default.
-        self.side = engine.SideStream() if side_stream else None
-        # optional SyncBN of the encoder's BatchNorm2d layers (SURVEY C3; the reference's DDP keeps per-rank statistics): every
-        # BatchNorm boundary of the forward and the backward adds the other ranks' fp64 sums (engine.chain_forward / _backward)
-        self.sync_group = None
-        if self.wide and (side_stream or use_graph):
-            raise ValueError("an encoder with wide layers runs on the main stream, outside hipGraph capture")
-        if sync_bn and self.world > 1:
-            if self.mlp or side_stream or use_graph or self.wide:
-                raise ValueError("sync_bn: encoder BatchNorm only (STS-GCN encoder within the tile kernels, linear projector), on the "
-                                 "main stream, outside hipGraph capture")
-            self.sync_group = process_group if process_group is not None else dist.group.WORLD
-        # gradient buckets for the data-parallel all-reduce: [encoder | bottleneck]; the bottleneck parameters are the
-        # tail of the flat buffer (named_parameters order) and their gradients are final before the encoder backward
-        names = self.fp.names
-        first_tail = next((i for i, n in enumerate(names) if n.startswith("btlnk.")), None)
-        self.tail_off = None
-        if first_tail is not None and all(n.startswith("btlnk.") for n in names[first_tail:]):
-            self.tail_off = self.fp.offsets[names[first_tail]]
-        if use_graph and any(isinstance(b, torch.nn.modules.batchnorm._BatchNorm) and b.momentum is None for b in model.modules()):
-            raise ValueError("use_graph: BatchNorm with momentum=None changes its averaging factor every step (a launch argument here); "
-                             "capture needs a fixed momentum")
-        self.use_graph = use_graph
-        self._graph = None
-        self._x_static: Optional[Tensor] = None
-        self._stats_static: Optional[Tensor] = None
-        self.steps = 0
-
-    def set_lr(self, lr: float) -> None:
-        self.hyper[0] = lr
-        self.lr = float(lr)
-
-    def _adam(self) -> None:
-        """torch.optim.Adam step on the flat buffers with alpha * calc_reg_loss' gradient and the 1 / world of the gradient
-        all-reduce folded in.  Outside hipGraph capture lr and the running products beta^t come from the host (one launch);
-        a captured step keeps them in device memory (`hyper`: a one-thread launch advances beta^t in front of the update)."""
-        if self.use_graph:
-            ops.adam_dev(self.fp.flat, self.fp.grad, self.m, self.v, self.fp.reg_mask, self.hyper, self.beta1,
-                         self.beta2, self.eps, gscale=1.0 / self.world, reg_coef=self.reg_coef)
-        else:
-            import numpy as np
-            b1p, b2p = getattr(self, "_bpow", (np.float32(1.0), np.float32(1.0)))
-            self._bpow = (np.float32(b1p * np.float32(self.beta1)), np.float32(b2p * np.float32(self.beta2)))   # fp32, as the device tick
-            ops.adam_pow(self.fp.flat, self.fp.grad, self.m, self.v, self.fp.reg_mask, self.lr, self.beta1, self.beta2, self.eps,
-                         float(self._bpow[0]), float(self._bpow[1]), gscale=1.0 / self.world, reg_coef=self.reg_coef)
-
-    # -- the step ---------------------------------------------------------------------------
-    def _body(self, x: Tensor) -> Tensor:
-        m = self.model
-        B = x.shape[0]
-        if self.stack is None:
-            U, ctx = engine.chain_forward(x, self.layers, True, self.ws, want_ctx=True, sync=self.sync_group)
-            slope, top_layers, last_slope_grad = self.layers[-1].slope, self.layers, self.grads[-1]["slope"]
-        else:
-            U, slope, saved_stack = self.stack.forward(x, self.ws)      # slope None: the stack ended in a wide layer (activated output)
-            ctx, top_layers = self.stack.top(saved_stack)
-            top_layers = top_layers or []
-            last_slope_grad = self.stack.last_slope_grad
-        gv = self.fp.gviews
-        if self.mlp:
-            # mlp projector (components.py:209-226): wide Linear on the bottleneck kernel (PReLU on load), then every
-            # [BatchNorm1d, ReLU, Linear] block on csrc/mlp_head.hip; parameters and gradients stay in the flat buffers
-            first, wname = m.btlnk.net[0], "btlnk.net.0."
-            W, b = first.weight, first.bias
-            y = ops.btlnk_fwd(U, W, b, slope, ws=self.ws)
-            saved = []
-            if B == 1:                     # nn.BatchNorm1d's own check in training mode
-                raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d of the mlp projector)")
-            for i, (bn, lin) in enumerate(m.btlnk.blocks()):
-                z, stat = ops.mlp_head_fwd(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                           lin.weight, lin.bias, True, momentum=ops.bn_momentum(bn), eps=bn.eps)
-                saved.append((y, stat, bn, lin, f"btlnk.net.{3 * i + 1}.", f"btlnk.net.{3 * i + 3}."))
-                y = z
-            z = y
-        else:
-            wname = "btlnk."
-            W, b = m.btlnk.weight, m.btlnk.bias
-            z = ops.btlnk_fwd(U, W, b, slope, ws=self.ws)
-        if self.head == 'euclidean':
-            stats, dz, _ = ops.mse_head(z, m.c, acc=self.center_acc)
-        elif self.head == 'poincare':
-            stats, dz, _, _ = ops.poincare_head(z, m.c, acc=self.center_acc)
-        elif self.head == 'mahalanobis':
-            stats, dz, _ = ops.mahalanobis_head(z, m.c, m.inv_cov_matrix, acc=self.center_acc, gram=self.gram_acc)
-        else:
-            raise ValueError(f"unknown head {self.head}")
-        if self.mlp:
-            for y_in, stat, bn, lin, bname, lname in reversed(saved):
-                g = {"gamma": gv[bname + "weight"], "beta": gv[bname + "bias"], "W2": gv[lname + "weight"], "b2": gv.get(lname + "bias")}
-                dz = ops.mlp_head_bwd(y_in, stat, bn.weight, bn.bias, lin.weight, dz, g, True)
-        dU, top_stats = engine.btlnk_backward(ctx if self.side is None else None, top_layers, U, W, dz, slope, gv[wname + "weight"],
-                                              gv.get(wname + "bias"), last_slope_grad, self.ws)
-        work = None
-        if self.world > 1 and self.tail_off is not None:
-            # bucket 1 (87 % of the bytes: the bottleneck weight) is complete now: its all-reduce runs on the collective
-            # stream while the encoder backward proceeds (SUM; the 1/W is folded into Adam)
-            work = dist.all_reduce(self.fp.grad[self.tail_off:], group=self.pg, async_op=True)
-        if self.stack is None:
-            engine.chain_backward(ctx, self.layers, dU, self.ws, self.grads, need_dx=False, side=self.side, stats_in=top_stats)
-        else:
-            self.stack.backward(saved_stack, dU, self.ws, need_dx=False, top_stats=top_stats)
-        if self.world > 1:
-            head = self.fp.grad if work is None else self.fp.grad[:self.tail_off]
-            dist.all_reduce(head, group=self.pg)           # bucket 2: the encoder's gradients (0.12 MB)
-            if work is not None:
-                work.wait()
-        self._adam()
-        return stats
-
-    def step(self, x: Tensor) -> Tensor:
-        """One optimisation step on clips x [B,C,T,V]; returns the head's stats block (stats[0] = loss)."""
-        self.steps += 1
-        x = x.contiguous()
-        if not self.use_graph:
-            return self._body(x)
-        if self._graph is None or self._x_static.shape != x.shape:
-            self._x_static = x.clone()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):          # warm-up outside capture (allocator, lazy module load)
-                self._body(self._x_static)
-            torch.cuda.current_stream().wait_stream(s)
-            self.steps += 1
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                self._stats_static = self._body(self._x_static)
-        self._x_static.copy_(x)
-        self._graph.replay()
-        return self._stats_static
-
-    def refresh_inv_cov(self, mu: Tensor, reset: bool = True) -> Tensor:
-        """inv_cov_matrix <- inverse(sum_n (z_n - mu)(z_n - mu)^T / (n - 1)) over the latents seen since the last
-        reset (staticCenter.py:40-46,133-142), from the accumulated second moments (all-reduced over ranks)."""
-        parallel.allreduce_sum_(self.gram_acc, self.pg)
-        acc = self.center_acc.clone()
-        parallel.allreduce_sum_(acc, self.pg)
-        self.model.inv_cov_matrix.copy_(inv_cov_from_moments(self.gram_acc, acc, mu, self.model.latent_dim))
-        if reset:
-            self.gram_acc.zero_()
-        return self.model.inv_cov_matrix
-
-    def reg_loss(self) -> Tensor:
-        """utils/model_utils.py::calc_reg_loss value of the current parameters (1-element tensor)."""
-        return ops.sqnorm(self.fp.flat, self.fp.reg_mask, self.reg_scale)
-
-    # -- centre bookkeeping (staticCenter.py:145-155; hyperbolic_encoder.py:175-183) ----------
-    def refresh_center(self, eps: float = 1e-3) -> Tensor:
-        """c <- statistics accumulated since the last refresh (all-reduced over ranks), then reset them."""
-        parallel.allreduce_sum_(self.center_acc, self.pg)
-        L = self.model.latent_dim
-        # Euclidean and Mahalanobis heads accumulate plain sums (mean centre); only the Poincare head's sums are the
-        # gyromidpoint's
-        c = ops.center_finalize(self.center_acc, eps, L) if self.head != 'poincare' else ops.midpoint_finalize(self.center_acc, L)
-        self.model.c.copy_(c)
-        self.center_acc.zero_()
-        return self.model.c
+# the kernels' vocabulary for one ST_GCNN layer's tensors -> the state_dict suffix behind the layer's prefix (`encoder.model.3.`)
+_LAYER_NAMES = {"A": "gcn.A", "T": "gcn.T", "Wt": "tcn.0.weight", "bt": "tcn.0.bias", "gt": "tcn.1.weight", "bet": "tcn.1.bias",
+                "Wr": "residual.0.weight", "br": "residual.0.bias", "gr": "residual.1.weight", "ber": "residual.1.bias",
+                "slope": "prelu.weight"}
 
 
 def _layer_grad_views(fp: "FlatParams", prefix: str) -> Dict[str, Tensor]:
     """gradient views of one ST_GCNN layer (state_dict prefix `encoder.model.3.`) in the kernels' vocabulary"""
-    g = {"A": "gcn.A", "T": "gcn.T", "Wt": "tcn.0.weight", "bt": "tcn.0.bias", "gt": "tcn.1.weight", "bet": "tcn.1.bias",
-         "Wr": "residual.0.weight", "br": "residual.0.bias", "gr": "residual.1.weight", "ber": "residual.1.bias",
-         "slope": "prelu.weight"}
-    return {k: fp.gviews[prefix + n] for k, n in g.items() if prefix + n in fp.gviews}
+    return {k: fp.gviews[prefix + n] for k, n in _LAYER_NAMES.items() if prefix + n in fp.gviews}
 
 
 # layers with <= 4 output channels behind 16 / 32 / 64 input channels (the decoder's last layer) run by commutation: both 1x1
@@ -316,29 +110,145 @@ def _virtual_narrow_layer(mod, fp: "FlatParams", prefix: str):
     selector of the Y channels (+ the real bias), `residual` convolution = selector of the R channels (+ the real bias); mixing
     parameters, BatchNorms and PReLU are the real layer's.  -> (LayerTensors, gradient views: the selectors' go to scratch)."""
     from .models.graph_layers.stsgcn import check_bn
-    Co = mod.out_channels
-    J = 2 * Co
+    Co, J = mod.out_channels, 2 * mod.out_channels
     tc, tb, rc, rb = mod.tcn[0], mod.tcn[1], mod.residual[0], mod.residual[1]
     check_bn(tb, rb)
-    dev = mod.gcn.A.device
-    sel_t = torch.zeros(Co, J, 1, 1, device=dev)
-    sel_r = torch.zeros(Co, J, 1, 1, device=dev)
-    for o in range(Co):
-        sel_t[o, o] = 1.0
-        sel_r[o, Co + o] = 1.0
+    sel = torch.eye(J, device=mod.gcn.A.device).view(J, J, 1, 1)
+    sel_t, sel_r = sel[:Co].contiguous(), sel[Co:].contiguous()
     lt = engine.LayerTensors(A=mod.gcn.A, T=mod.gcn.T, Wt=sel_t, bt=tc.bias, gt=tb.weight, bet=tb.bias, rm_t=tb.running_mean,
                              rv_t=tb.running_var, nbt_t=tb.num_batches_tracked, Wr=sel_r, br=rc.bias, gr=rb.weight, ber=rb.bias,
                              rm_r=rb.running_mean, rv_r=rb.running_var, nbt_r=rb.num_batches_tracked, slope=mod.prelu.weight,
                              momentum=tb.momentum if tb.momentum is not None else 0.1, bn=tb if tb.momentum is None else None, cache={})
-    gv = fp.gviews
-    g = {"A": gv[prefix + "gcn.A"], "T": gv[prefix + "gcn.T"], "Wt": torch.empty_like(sel_t), "gt": gv[prefix + "tcn.1.weight"],
-         "bet": gv[prefix + "tcn.1.bias"], "Wr": torch.empty_like(sel_r), "gr": gv[prefix + "residual.1.weight"],
-         "ber": gv[prefix + "residual.1.bias"], "slope": gv[prefix + "prelu.weight"]}
-    if tc.bias is not None:
-        g["bt"] = gv[prefix + "tcn.0.bias"]
-    if rc.bias is not None:
-        g["br"] = gv[prefix + "residual.0.bias"]
-    return lt, g
+    return lt, dict(_layer_grad_views(fp, prefix), Wt=torch.empty_like(sel_t), Wr=torch.empty_like(sel_r))
+
+
+class _Segment:
+    """What the segments of a _FlatStack share: `kind`; forward(h, slope, ws, ...) -> (h, slope, saved) with h a pre-activation whose
+    PReLU weight is `slope`, or activated (slope None); backward(saved, d, ws, need_dx, in_slope_grad, ...) -> d; `out_slope_grad`, the
+    gradient view of the PReLU weight of the segment's LAST layer (written by whoever back-propagates through that PReLU: the segment
+    behind, or the stack's caller), None where the segment hands over an activated output.  `in_slope_grad` is the `out_slope_grad` of
+    the segment in front (the caller's for the first one); a segment uses it iff its forward consumed a pre-activation."""
+
+    def __getitem__(self, i: int) -> str:
+        return (self.kind,)[i]         # seg[0] reads the kind, as it did while segments were tuples
+
+
+class _TileRun(_Segment):
+    """a run of layers the LDS tile kernels take: engine.chain_forward / chain_backward"""
+    kind = 'tile'
+
+    def __init__(self, modules, fp: "FlatParams", prefixes, side=None, sync=None) -> None:
+        self.layers = [layer_tensors(m) for m in modules]
+        self.grads = [_layer_grad_views(fp, p) for p in prefixes]
+        self.side, self.sync = side, sync             # engine.SideStream for dA / dT; SyncBN process group
+        self.first_layer, self.out_slope_grad = self.layers[0], self.grads[-1]["slope"]
+
+    def forward(self, h, slope, ws, pending0=None):
+        """saved: the run's ChainCtx"""
+        u, ctx = engine.chain_forward(h, self.layers, True, ws, in_slope=slope, want_ctx=True, sync=self.sync, pending0=pending0)
+        return u, self.layers[-1].slope, ctx
+
+    def backward(self, ctx, d, ws, need_dx, in_slope_grad, stats_in=None):
+        return engine.chain_backward(ctx, self.layers, d, ws, self.grads, need_dx=need_dx, side=self.side, stats_in=stats_in,
+                                     in_slope_grad=in_slope_grad)
+
+
+class _WideLayer(_Segment):
+    """a layer beyond the tile kernels on its composed path (stsgcn.wide_forward / wide_backward); hands over an activated output"""
+    kind = 'wide'
+    out_slope_grad = None
+
+    def __init__(self, mod, fp: "FlatParams", prefix: str) -> None:
+        self.mod = mod
+        # wide_backward's destinations, by state_dict suffix: the kernels write straight into the flat gradient buffer's views; conv
+        # biases in front of a train-mode BatchNorm keep the exact 0 the buffer was created with (nothing ever writes them)
+        self.into = {_LAYER_NAMES[k]: g for k, g in _layer_grad_views(fp, prefix).items()}
+
+    def forward(self, h, slope, ws):
+        from .models.graph_layers.stsgcn import wide_forward
+        xin = ops.prelu_fwd(h, slope) if slope is not None else h
+        out, wsaved, wmeta = wide_forward(xin, *self.mod.wide_args())
+        return out, None, (wsaved, wmeta, h if slope is not None else None, slope)
+
+    def backward(self, saved, d, ws, need_dx, in_slope_grad):
+        from .models.graph_layers.stsgcn import wide_backward
+        wsaved, wmeta, pre_u, pre_slope = saved
+        res = wide_backward(wsaved, wmeta, d, need_dx=need_dx, into=self.into)
+        for n, g in zip(_LAYER_NAMES.values(), res[1:]):
+            if g is not None and g.data_ptr() != self.into[n].data_ptr():      # (eval-statistics layers: bias sums)
+                self.into[n].copy_(g.view_as(self.into[n]))
+        d = res[0] if need_dx else None
+        if d is not None and pre_u is not None:       # the layer consumed PReLU(pre_u): back through it, into the producer's slope
+            d = ops.prelu_bwd(pre_u, d.contiguous(), pre_slope, in_slope_grad)
+        return d
+
+
+class _CommuteLayer(_Segment):
+    """a layer with fewer output than input channels on csrc/commute_layer.hip.  Its last forward kernel can form the first-layer
+    statistics of a tile run behind it (`next_layer` -> `pending`, chain_forward's pending0) and its backward kernel the batch
+    reductions of a tile run in front (`below` -> `chained`, chain_backward's stats_in); _FlatStack pairs them up."""
+    kind = 'commute'
+
+    def __init__(self, mod, fp: "FlatParams", prefix: str) -> None:
+        self.mod = mod
+        g = _layer_grad_views(fp, prefix)
+        self.into = {k: g[k] for k in ("A", "T", "Wt", "Wr", "gt", "bet", "gr", "ber")}
+        self.out_slope_grad = g["slope"]
+
+    def forward(self, h, slope, ws, next_layer: Optional[engine.LayerTensors] = None):
+        """-> (h, slope, saved, pending)"""
+        mod = self.mod
+        tc, tb, rc, rb = mod.tcn[0], mod.tcn[1], mod.residual[0], mod.residual[1]
+        mod.__dict__.get("_fold_cache", {}).clear()                    # (the layer's eval-mode fold goes stale with this step)
+        u, sv, pend = ops.commute_fwd(h, slope, tc.weight, rc.weight, mod.gcn.A, mod.gcn.T, tb.weight, tb.bias, rb.weight, rb.bias,
+                                      tc.bias, rc.bias, tb.running_mean, tb.running_var, rb.running_mean, rb.running_var,
+                                      tb.num_batches_tracked, rb.num_batches_tracked, tb.momentum, tb.eps,
+                                      next_layer=(next_layer.A, next_layer.T) if next_layer is not None else None,
+                                      slope_out=mod.prelu.weight)
+        return u, mod.prelu.weight, (sv, slope is not None), pend
+
+    def backward(self, saved, d, ws, need_dx, in_slope_grad, below=None):
+        """-> (d, chained)"""
+        sv, pre_act = saved
+        into = self.into
+        if pre_act:
+            if in_slope_grad is None:
+                raise RuntimeError("commuted layer: nowhere to put the gradient of its input's PReLU weight")
+            into = dict(into, in_slope=in_slope_grad)
+        d, chained = ops.commute_bwd(sv, d.contiguous(), into, below=below)
+        return (d if need_dx else None), chained
+
+
+class _NarrowLayer(_Segment):
+    """a layer with <= 4 output channels: both convolutions first, as one streaming pass over the wide input (csrc/last_layer.hip),
+    then the few-channel tile kernels on the virtual (2 C_out -> C_out) layer behind them"""
+    kind = 'narrow'
+
+    def __init__(self, mod, fp: "FlatParams", prefix: str) -> None:
+        self.mod = mod
+        self.virt, self.vgrads = _virtual_narrow_layer(mod, fp, prefix)
+        g = _layer_grad_views(fp, prefix)
+        self.gWt, self.gWr, self.out_slope_grad = g["Wt"], g["Wr"], g["slope"]
+
+    def forward(self, h, slope, ws):
+        mod = self.mod
+        Co, Ci = mod.out_channels, mod.in_channels
+        W4 = torch.cat([mod.tcn[0].weight.view(Co, Ci), mod.residual[0].weight.view(Co, Ci)], 0)
+        mod.__dict__.get("_fold_cache", {}).clear()                    # (the real layer's eval-mode fold goes stale with this step)
+        YR = ops.narrow_conv_fwd(h, slope, W4)                         # [Wt X; Wr X] with X = PReLU(h)
+        u, ctx = engine.chain_forward(YR, [self.virt], True, ws, want_ctx=True)
+        return u, self.virt.slope, (ctx, h, slope, W4)
+
+    def backward(self, saved, d, ws, need_dx, in_slope_grad):
+        ctx, pre_u, pre_slope, W4 = saved
+        Co, Ci = self.mod.out_channels, self.mod.in_channels
+        dYR = engine.chain_backward(ctx, [self.virt], d, ws, [self.vgrads], need_dx=True)
+        d, sums = ops.narrow_conv_bwd(pre_u, pre_slope, W4, dYR)
+        self.gWt.copy_(sums[:Co * Ci].view(Co, Ci, 1, 1))
+        self.gWr.copy_(sums[Co * Ci:2 * Co * Ci].view(Co, Ci, 1, 1))
+        if pre_slope is not None and in_slope_grad is not None:
+            in_slope_grad.copy_(sums[2 * Co * Ci:])
+        return d if need_dx else None
 
 
 class _FlatStack:
@@ -346,34 +256,50 @@ class _FlatStack:
     buffers: runs of layers the LDS tile kernels take go through engine.chain_forward / chain_backward (no autograd);
     a layer beyond them (`is_wide`: 64 input channels on the 25-joint layout, > 64 channels, dropout) runs its composed
     HIP path (stsgcn.wide_forward / wide_backward: explicit forward and backward, no autograd), gradients written to the flat
-    buffer's views."""
+    buffer's views; layers the commuted / narrow-output kernels take run there."""
 
-    def __init__(self, modules, fp: "FlatParams", prefix: str, first: int = 0) -> None:
-        """modules: the layers first, first + 1, .. of the nn.Sequential whose parameters are named `{prefix}{index}.`"""
-        self.segs = []                 # ('tile', [LayerTensors], [grad dicts]) | ('wide', module, names)
+    def __init__(self, modules, fp: "FlatParams", prefix: str, first: int = 0, plain: bool = False, side=None, sync=None) -> None:
+        """modules: the layers first, first + 1, .. of the nn.Sequential whose parameters are named `{prefix}{index}.`
+        plain: no commuted / narrow-output segments (those layers stay in the tile runs); side, sync: the tile runs' side stream /
+        SyncBN process group"""
         dec = prefix.startswith("decoder")
+        kinds = ['wide' if m.is_wide else 'narrow' if not plain and _is_narrow(m) else
+                 'commute' if not plain and _is_commute(m, dec) else 'tile' for m in modules]
+        single = {'wide': _WideLayer, 'narrow': _NarrowLayer, 'commute': _CommuteLayer}
+        self.segs = []
         i, n = 0, len(modules)
         while i < n:
-            if modules[i].is_wide:
-                self.segs.append(('wide', modules[i], f"{prefix}{first + i}."))
-                i += 1
-            elif _is_narrow(modules[i]):
-                pre = f"{prefix}{first + i}."
-                self.segs.append(('narrow', modules[i], pre) + _virtual_narrow_layer(modules[i], fp, pre))
-                i += 1
-            elif _is_commute(modules[i], dec):
-                self.segs.append(('commute', modules[i], f"{prefix}{first + i}."))
-                i += 1
-            else:
-                j = i
-                while j < n and not modules[j].is_wide and not _is_narrow(modules[j]) and not _is_commute(modules[j], dec):
+            j = i + 1
+            if kinds[i] == 'tile':
+                while j < n and kinds[j] == 'tile':
                     j += 1
-                self.segs.append(('tile', [layer_tensors(m) for m in modules[i:j]],
-                                  [_layer_grad_views(fp, f"{prefix}{first + k}.") for k in range(i, j)]))
-                i = j
-        self.fp = fp
-        self.last_slope_grad = (fp.gviews[f"{prefix}{first + n - 1}.prelu.weight"]
-                                if self.segs[-1][0] in ('tile', 'narrow', 'commute') else None)
+                self.segs.append(_TileRun(modules[i:j], fp, [f"{prefix}{first + k}." for k in range(i, j)], side=side, sync=sync))
+            else:
+                self.segs.append(single[kinds[i]](modules[i], fp, f"{prefix}{first + i}."))
+            i = j
+        self.last_slope_grad = self.segs[-1].out_slope_grad
+
+    def _stats_rider(self, k: int) -> Optional[engine.LayerTensors]:
+        """the first layer of a tile run behind commuted segment k when its statistics pass rides on that segment's last kernel"""
+        if not (COMMUTE_NEXT and k + 1 < len(self.segs) and self.segs[k + 1].kind == 'tile'):
+            return None
+        mod, nxt = self.segs[k].mod, self.segs[k + 1].first_layer
+        # (25 joints: at 17 the tile kernels' own 16-channel statistics pass is the faster one -- 2.746 vs 2.754 ms on the VAE step)
+        if nxt.Ci != mod.out_channels or nxt.rm_t is None or not engine.STORE_Z or mod.joints_dim != 25:
+            return None
+        return nxt
+
+    def _reductions_rider(self, k: int, saved):
+        """(input, Z) of a tile run in front of commuted segment k that is one 2 -> 32 layer fed by the network input: its batch
+        reductions ride on that segment's backward kernel"""
+        if not (COMMUTE_NEXT and k > 0 and self.segs[k - 1].kind == 'tile'):
+            return None
+        layers, bctx = self.segs[k - 1].layers, saved[k - 1]
+        bl = layers[-1]
+        if (bl.Ci == 2 and bl.Co == 32 and bl.Wr is not None and len(layers) == 1 and bctx.in_slope is None
+                and bctx.zs and bctx.zs[-1] is not None and bctx.sync is None):
+            return bctx.inputs[-1], bctx.zs[-1]
+        return None
 
     def forward(self, x: Tensor, ws: engine.Workspace, in_slope: Optional[Tensor] = None):
         """x: the stack's input, activated (in_slope None) or a pre-activation whose PReLU weight is `in_slope`
@@ -381,48 +307,19 @@ class _FlatStack:
         h, slope, saved = x, in_slope, []
         pend = None                    # the next tile run's first-layer statistics, when the commuted layer in front of it formed them
         for k, seg in enumerate(self.segs):
-            if seg[0] == 'tile':
-                u, ctx = engine.chain_forward(h, seg[1], True, ws, in_slope=slope, want_ctx=True, pending0=pend)
+            if seg.kind == 'commute':
+                h, slope, sv, pend = seg.forward(h, slope, ws, next_layer=self._stats_rider(k))
+            elif seg.kind == 'tile':
+                h, slope, sv = seg.forward(h, slope, ws, pending0=pend)
                 pend = None
-                saved.append(ctx)
-                h, slope = u, seg[1][-1].slope
-            elif seg[0] == 'narrow':
-                mod, virt = seg[1], seg[3]
-                Co, Ci = mod.out_channels, mod.in_channels
-                W4 = torch.cat([mod.tcn[0].weight.view(Co, Ci), mod.residual[0].weight.view(Co, Ci)], 0)
-                mod.__dict__.get("_fold_cache", {}).clear()                # (the real layer's eval-mode fold goes stale with this step)
-                YR = ops.narrow_conv_fwd(h, slope, W4)                     # [Wt X; Wr X] with X = PReLU(h)
-                u, ctx = engine.chain_forward(YR, [virt], True, ws, want_ctx=True)
-                saved.append((ctx, h, slope, W4))
-                h, slope = u, virt.slope
-            elif seg[0] == 'commute':
-                mod = seg[1]
-                Co, Ci = mod.out_channels, mod.in_channels
-                tc, tb, rc, rb = mod.tcn[0], mod.tcn[1], mod.residual[0], mod.residual[1]
-                mod.__dict__.get("_fold_cache", {}).clear()
-                # a tile run behind this layer: its first layer's statistics pass rides on this layer's last kernel
-                nxt = self.segs[k + 1][1][0] if (COMMUTE_NEXT and k + 1 < len(self.segs) and self.segs[k + 1][0] == 'tile') else None
-                # (25 joints: at 17 the tile kernels' own 16-channel statistics pass is the faster one -- 2.746 vs 2.754 ms on the VAE step)
-                if nxt is not None and (nxt.Ci != Co or nxt.rm_t is None or not engine.STORE_Z or mod.joints_dim != 25):
-                    nxt = None
-                u, sv, pend = ops.commute_fwd(h, slope, tc.weight, rc.weight, mod.gcn.A, mod.gcn.T, tb.weight, tb.bias, rb.weight, rb.bias,
-                                              tc.bias, rc.bias, tb.running_mean, tb.running_var, rb.running_mean, rb.running_var,
-                                              tb.num_batches_tracked, rb.num_batches_tracked, tb.momentum, tb.eps,
-                                              next_layer=(nxt.A, nxt.T) if nxt is not None else None, slope_out=mod.prelu.weight)
-                saved.append(sv)
-                h, slope = u, mod.prelu.weight
             else:
-                from .models.graph_layers.stsgcn import wide_forward
-                pre_u, pre_slope = (h, slope) if slope is not None else (None, None)
-                xin = ops.prelu_fwd(h, slope) if slope is not None else h
-                out, wsaved, wmeta = wide_forward(xin, *seg[1].wide_args())
-                saved.append((wsaved, wmeta, pre_u, pre_slope))
-                h, slope = out, None
+                h, slope, sv = seg.forward(h, slope, ws)
+            saved.append(sv)
         return h, slope, saved
 
     def top(self, saved):
         """(ChainCtx, layers) of the last segment when it is a tile run (engine.btlnk_backward), else (None, None)"""
-        return (saved[-1], self.segs[-1][1]) if self.segs[-1][0] == 'tile' else (None, None)
+        return (saved[-1], self.segs[-1].layers) if self.segs[-1].kind == 'tile' else (None, None)
 
     def backward(self, saved, d_last: Tensor, ws: engine.Workspace, need_dx: bool, top_stats=None,
                  in_slope_grad: Optional[Tensor] = None) -> Optional[Tensor]:
@@ -430,87 +327,239 @@ class _FlatStack:
         gradient -- or the activated output of a wide layer); top_stats: the last tile run's top-layer batch reductions when
         the producer of d_last formed them (engine.btlnk_backward); in_slope_grad: where the gradient of forward's `in_slope`
         goes (the returned gradient is then w.r.t. the PRE-activation input)."""
-        d = d_last
-
-        def below_slope_grad(k):
-            """where the PReLU-weight gradient of segment k's INPUT goes: the segment below's last slope, or the caller's"""
-            if k == 0:
-                return in_slope_grad
-            below = self.segs[k - 1]
-            if below[0] == 'tile':
-                return below[2][-1]["slope"]
-            if below[0] == 'narrow':
-                return below[4]["slope"]
-            if below[0] == 'commute':
-                return self.fp.gviews[below[2] + "prelu.weight"]
-            return None
-
-        chained = None                 # batch reductions of the tile run below, formed by the commuted layer's backward kernel
-        for k in range(len(self.segs) - 1, -1, -1):
-            seg, sv = self.segs[k], saved[k]
-            first = k == 0
-            if seg[0] == 'tile':
-                d = engine.chain_backward(sv, seg[1], d, ws, seg[2], need_dx=need_dx or not first,
-                                          stats_in=top_stats if k == len(self.segs) - 1 else chained,
-                                          in_slope_grad=below_slope_grad(k) if (first or self.segs[k - 1][0] == 'commute') else None)
-            elif seg[0] == 'commute':
-                prefix, gv = seg[2], self.fp.gviews
-                into = {"A": gv[prefix + "gcn.A"], "T": gv[prefix + "gcn.T"], "Wt": gv[prefix + "tcn.0.weight"],
-                        "Wr": gv[prefix + "residual.0.weight"], "gt": gv[prefix + "tcn.1.weight"], "bet": gv[prefix + "tcn.1.bias"],
-                        "gr": gv[prefix + "residual.1.weight"], "ber": gv[prefix + "residual.1.bias"]}
-                if sv[1] is not None:
-                    into["in_slope"] = below_slope_grad(k)
-                    if into["in_slope"] is None:
-                        raise RuntimeError("commuted layer: nowhere to put the gradient of its input's PReLU weight")
-                # a tile run in front that ends in a 2-channel layer fed by the network input: its batch reductions ride on this kernel
-                below = None
-                if COMMUTE_NEXT and k > 0 and self.segs[k - 1][0] == 'tile':
-                    bl, bctx = self.segs[k - 1][1][-1], saved[k - 1]
-                    if (bl.Ci == 2 and bl.Co == 32 and bl.Wr is not None and len(self.segs[k - 1][1]) == 1 and bctx.in_slope is None
-                            and bctx.zs and bctx.zs[-1] is not None and bctx.sync is None):
-                        below = (bctx.inputs[-1], bctx.zs[-1])
-                d, chained = ops.commute_bwd(sv, d.contiguous(), into, below=below)
-                if not (need_dx or not first):
-                    d = None
-            elif seg[0] == 'narrow':
-                mod, prefix, virt, vg = seg[1], seg[2], seg[3], seg[4]
-                ctx, pre_u, pre_slope, W4 = sv
-                Co, Ci = mod.out_channels, mod.in_channels
-                dYR = engine.chain_backward(ctx, [virt], d, ws, [vg], need_dx=True)
-                d, sums = ops.narrow_conv_bwd(pre_u, pre_slope, W4, dYR)
-                gv = self.fp.gviews
-                gv[prefix + "tcn.0.weight"].copy_(sums[:Co * Ci].view(Co, Ci, 1, 1))
-                gv[prefix + "residual.0.weight"].copy_(sums[Co * Ci:2 * Co * Ci].view(Co, Ci, 1, 1))
-                if pre_slope is not None:
-                    dslope = (self.segs[k - 1][2][-1]["slope"] if self.segs[k - 1][0] == 'tile' else self.segs[k - 1][4]["slope"]) \
-                        if k > 0 else in_slope_grad
-                    if dslope is not None:
-                        dslope.copy_(sums[2 * Co * Ci:])
-                if not (need_dx or not first):
-                    d = None
+        d, chained = d_last, None                # batch reductions of the tile run below, formed by the commuted layer's backward kernel
+        last = len(self.segs) - 1
+        for k in range(last, -1, -1):
+            seg = self.segs[k]
+            args = (saved[k], d, ws, need_dx or k > 0, self.segs[k - 1].out_slope_grad if k > 0 else in_slope_grad)
+            if seg.kind == 'commute':
+                d, chained = seg.backward(*args, below=self._reductions_rider(k, saved))
+            elif seg.kind == 'tile':
+                d = seg.backward(*args, stats_in=top_stats if k == last else chained)
             else:
-                from .models.graph_layers.stsgcn import wide_backward
-                wsaved, wmeta, pre_u, pre_slope = sv
-                prefix = seg[2]
-                want_x = need_dx or not first
-                names = ("gcn.A", "gcn.T", "tcn.0.weight", "tcn.0.bias", "tcn.1.weight", "tcn.1.bias", "residual.0.weight",
-                         "residual.0.bias", "residual.1.weight", "residual.1.bias", "prelu.weight")
-                # the kernels write straight into the flat gradient buffer's views; conv biases in front of a train-mode BatchNorm keep
-                # the exact 0 the buffer was created with (nothing ever writes them)
-                into = {n: self.fp.gviews[prefix + n] for n in names if prefix + n in self.fp.gviews}
-                res = wide_backward(wsaved, wmeta, d, need_dx=want_x, into=into)
-                for n, g in zip(names, res[1:]):
-                    if g is not None and g.data_ptr() != into[n].data_ptr():      # (eval-statistics layers: bias sums)
-                        into[n].copy_(g.view_as(into[n]))
-                d = res[0] if want_x else None
-                if d is not None and pre_u is not None:
-                    # the wide layer consumed PReLU(pre_u): back through it, into the producing tile run's last slope
-                    dslope = self.segs[k - 1][2][-1]["slope"] if k > 0 else in_slope_grad
-                    d = ops.prelu_bwd(pre_u, d.contiguous(), pre_slope, dslope)
+                d = seg.backward(*args)
         return d
 
 
-class STSAETrainStep:
+class _OneClassHead:
+    """The one-class heads and their centre / covariance bookkeeping (staticCenter.py:40-46,133-155; hyperbolic_encoder.py:175-183)
+    for a step object with `model`, `head`, `pg`, `center_acc`, `gram_acc`."""
+
+    def _head(self, z: Tensor):
+        """-> (stats block, d loss / d z) of latents z against the centre; accumulates the centre (and covariance) statistics"""
+        m = self.model
+        if self.head == 'euclidean':
+            return ops.mse_head(z, m.c, acc=self.center_acc)[:2]
+        if self.head == 'poincare':
+            return ops.poincare_head(z, m.c, acc=self.center_acc)[:2]
+        if self.head == 'mahalanobis':
+            return ops.mahalanobis_head(z, m.c, m.inv_cov_matrix, acc=self.center_acc, gram=self.gram_acc)[:2]
+        raise ValueError(f"unknown head {self.head}")
+
+    def refresh_center(self, eps: float = 1e-3) -> Tensor:
+        """c <- statistics accumulated since the last refresh (all-reduced over ranks), then reset them."""
+        parallel.allreduce_sum_(self.center_acc, self.pg)
+        L = self.model.latent_dim
+        # Euclidean and Mahalanobis heads accumulate plain sums (mean centre); only the Poincare head's sums are the gyromidpoint's
+        c = ops.center_finalize(self.center_acc, eps, L) if self.head != 'poincare' else ops.midpoint_finalize(self.center_acc, L)
+        self.model.c.copy_(c)
+        self.center_acc.zero_()
+        return self.model.c
+
+    def refresh_inv_cov(self, mu: Tensor, reset: bool = True) -> Tensor:
+        """inv_cov_matrix <- inverse(sum_n (z_n - mu)(z_n - mu)^T / (n - 1)) over the latents seen since the last
+        reset (staticCenter.py:40-46,133-142), from the accumulated second moments (all-reduced over ranks)."""
+        parallel.allreduce_sum_(self.gram_acc, self.pg)
+        acc = self.center_acc.clone()
+        parallel.allreduce_sum_(acc, self.pg)
+        self.model.inv_cov_matrix.copy_(inv_cov_from_moments(self.gram_acc, acc, mu, self.model.latent_dim))
+        if reset:
+            self.gram_acc.zero_()
+        return self.model.inv_cov_matrix
+
+
+class _FlatStep:
+    """What the autograd-free steps share: the model's parameters re-homed in flat buffers, Adam's moments and the fused update, the
+    regulariser, the data-parallel world, the `mlp` projector's blocks."""
+
+    use_graph = False
+
+    def __init__(self, model, lr: float, alpha: float, betas, eps: float, process_group) -> None:
+        self.model, self.alpha, self.lr = model, float(alpha), float(lr)
+        self.beta1, self.beta2, self.eps = float(betas[0]), float(betas[1]), float(eps)
+        self.pg = process_group
+        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        self.fp = FlatParams(model)
+        self.m, self.v = torch.zeros_like(self.fp.flat), torch.zeros_like(self.fp.flat)
+        self.ws = engine.Workspace()
+        self.reg_scale = 0.5 / self.fp.n_reg_tensors          # calc_reg_loss value = reg_scale * sum p^2
+        self.reg_coef = self.alpha * 2.0 * self.reg_scale      # its gradient coefficient, times alpha
+        self.steps = 0
+
+    def set_lr(self, lr: float) -> None:
+        self.lr = float(lr)
+
+    def reg_loss(self) -> Tensor:
+        """utils/model_utils.py::calc_reg_loss value of the current parameters (1-element tensor)."""
+        return ops.sqnorm(self.fp.flat, self.fp.reg_mask, self.reg_scale)
+
+    def _adam(self) -> None:
+        """torch.optim.Adam step on the flat buffers with alpha * calc_reg_loss' gradient and the 1 / world of the gradient
+        all-reduce folded in.  Outside hipGraph capture lr and the running products beta^t come from the host (one launch);
+        a captured step keeps them in device memory (`hyper`: a one-thread launch advances beta^t in front of the update)."""
+        if self.use_graph:
+            ops.adam_dev(self.fp.flat, self.fp.grad, self.m, self.v, self.fp.reg_mask, self.hyper, self.beta1,
+                         self.beta2, self.eps, gscale=1.0 / self.world, reg_coef=self.reg_coef)
+        else:
+            import numpy as np
+            b1p, b2p = getattr(self, "_bpow", (np.float32(1.0), np.float32(1.0)))
+            self._bpow = (np.float32(b1p * np.float32(self.beta1)), np.float32(b2p * np.float32(self.beta2)))   # fp32, as the device tick
+            ops.adam_pow(self.fp.flat, self.fp.grad, self.m, self.v, self.fp.reg_mask, self.lr, self.beta1, self.beta2, self.eps,
+                         float(self._bpow[0]), float(self._bpow[1]), gscale=1.0 / self.world, reg_coef=self.reg_coef)
+
+    def _mlp_forward(self, U: Tensor, slope: Tensor):
+        """`mlp` projector (components.py:209-226) on the chain's pre-activation output: the wide first Linear on the bottleneck kernel
+        (PReLU on load), then every [BatchNorm1d, ReLU, Linear] block on csrc/mlp_head.hip; parameters and gradients stay in the flat
+        buffers -> (y, saved)"""
+        if U.shape[0] == 1:                # nn.BatchNorm1d's own check in training mode
+            raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d of the mlp projector)")
+        btl = self.model.btlnk
+        y = ops.btlnk_fwd(U, btl.net[0].weight, btl.net[0].bias, slope, ws=self.ws)
+        saved = []
+        for i, (bn, lin) in enumerate(btl.blocks()):
+            z, stat = ops.mlp_head_fwd(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                       lin.weight, lin.bias, True, momentum=ops.bn_momentum(bn), eps=bn.eps)
+            saved.append((y, stat, bn, lin, f"btlnk.net.{3 * i + 1}.", f"btlnk.net.{3 * i + 3}."))
+            y = z
+        return y, saved
+
+    def _mlp_backward(self, saved, d: Tensor) -> Tensor:
+        """back through the blocks of _mlp_forward -> the gradient of the first Linear's output"""
+        gv = self.fp.gviews
+        for y_in, stat, bn, lin, bname, lname in reversed(saved):
+            g = {"gamma": gv[bname + "weight"], "beta": gv[bname + "bias"], "W2": gv[lname + "weight"], "b2": gv.get(lname + "bias")}
+            d = ops.mlp_head_bwd(y_in, stat, bn.weight, bn.bias, lin.weight, d, g, True)
+        return d
+
+
+class STSETrainStep(_FlatStep, _OneClassHead):
+    """One-class training of an STSE (`linear` projector, or `mlp` within the HIP kernels' widths) without autograd.
+
+    head: 'euclidean' -> F.mse_loss(z, c);  'poincare' -> dist(c, project(expmap0(z))).mean().
+    """
+
+    def __init__(self, model, lr: float = 1e-4, alpha: float = 1e-6, head: str = 'euclidean',
+                 betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, use_graph: bool = False,
+                 side_stream: bool = False, sync_bn: bool = False) -> None:
+        from .models.sts.ae import STSE
+        from .models.common.components import MLP
+        self.mlp = isinstance(model.btlnk, MLP)
+        if not isinstance(model, STSE) or not (isinstance(model.btlnk, torch.nn.Linear) or (self.mlp and model.btlnk.hip_ok)):
+            raise TypeError("STSETrainStep drives an STSE with projector='linear' or an 'mlp' within the kernels' widths")
+        super().__init__(model, lr, alpha, betas, eps, process_group)
+        self.head = head
+        dev = self.fp.flat.device
+        self.hyper = torch.tensor([lr, 1.0, 1.0, 0.0], device=dev, dtype=torch.float32)
+        L = model.latent_dim
+        self.center_acc = torch.zeros(ops.head_slots(L), device=dev, dtype=torch.float32)
+        self.gram_acc = torch.zeros(L, L, device=dev, dtype=torch.float32) if head == 'mahalanobis' else None
+        # an encoder with layers beyond the LDS tile kernels (the wide C = 2 -> 256 stack, dropout) runs them on their explicit forward /
+        # backward between the tile runs: main stream, eager launches
+        wide = any(l.is_wide for l in model.encoder.model)
+        if wide and (side_stream or use_graph):
+            raise ValueError("an encoder with wide layers runs on the main stream, outside hipGraph capture")
+        # optional: dA / dT on a second stream beside the next layer's reductions.  Measured SLOWER on MI355X (2.43 vs
+        # 2.28 ms/step: the two LDS-heavy persistent kernels halve each other's occupancy), so it is off by default.
+        self.side = engine.SideStream() if side_stream else None
+        # optional SyncBN of the encoder's BatchNorm2d layers (SURVEY C3; the reference's DDP keeps per-rank statistics): every
+        # BatchNorm boundary of the forward and the backward adds the other ranks' fp64 sums (engine.chain_forward / _backward)
+        self.sync_group = None
+        if sync_bn and self.world > 1:
+            if self.mlp or side_stream or use_graph or wide:
+                raise ValueError("sync_bn: encoder BatchNorm only (STS-GCN encoder within the tile kernels, linear projector), on the "
+                                 "main stream, outside hipGraph capture")
+            self.sync_group = process_group if process_group is not None else dist.group.WORLD
+        # the commuted kernels take a layer (32 -> 16 on the 25-joint layout) unless the step is asked for something only the plain
+        # chain does: hipGraph capture, the side stream, SyncBN; an encoder without wide or commuted layers is one tile run (a
+        # narrow-output layer alone does not split it)
+        plain = not wide and (use_graph or side_stream or sync_bn or not any(_is_commute(l) for l in model.encoder.model))
+        self.stack = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.", plain=plain, side=self.side, sync=self.sync_group)
+        # gradient buckets for the data-parallel all-reduce: [encoder | bottleneck]; the bottleneck parameters are the
+        # tail of the flat buffer (named_parameters order) and their gradients are final before the encoder backward
+        names = self.fp.names
+        first_tail = next((i for i, n in enumerate(names) if n.startswith("btlnk.")), None)
+        tail = first_tail is not None and all(n.startswith("btlnk.") for n in names[first_tail:])
+        self.tail_off = self.fp.offsets[names[first_tail]] if tail else None
+        if use_graph and any(isinstance(b, torch.nn.modules.batchnorm._BatchNorm) and b.momentum is None for b in model.modules()):
+            raise ValueError("use_graph: BatchNorm with momentum=None changes its averaging factor every step (a launch argument here); "
+                             "capture needs a fixed momentum")
+        self.use_graph = use_graph
+        self._graph = self._x_static = self._stats_static = None
+
+    @property
+    def layers(self) -> List[engine.LayerTensors]:
+        """the encoder's LayerTensors when it is one tile run, else []"""
+        segs = self.stack.segs
+        return segs[0].layers if len(segs) == 1 and segs[0].kind == 'tile' else []
+
+    def set_lr(self, lr: float) -> None:
+        self.hyper[0] = lr                 # the captured step reads it
+        self.lr = float(lr)
+
+    # -- the step ---------------------------------------------------------------------------
+    def _body(self, x: Tensor) -> Tensor:
+        m, gv = self.model, self.fp.gviews
+        U, slope, saved_stack = self.stack.forward(x, self.ws)          # slope None: the stack ended in a wide layer (activated output)
+        ctx, top_layers = self.stack.top(saved_stack)
+        if self.mlp:
+            wname, W = "btlnk.net.0.", m.btlnk.net[0].weight
+            z, saved = self._mlp_forward(U, slope)
+        else:
+            wname, W = "btlnk.", m.btlnk.weight
+            z = ops.btlnk_fwd(U, W, m.btlnk.bias, slope, ws=self.ws)
+        stats, dz = self._head(z)
+        if self.mlp:
+            dz = self._mlp_backward(saved, dz)
+        # (the side-stream backward runs its own batch reductions: no ChainCtx, so the bottleneck's backward forms none)
+        dU, top_stats = engine.btlnk_backward(ctx if self.side is None else None, top_layers or [], U, W, dz, slope, gv[wname + "weight"],
+                                              gv.get(wname + "bias"), self.stack.last_slope_grad, self.ws)
+        work = None
+        if self.world > 1 and self.tail_off is not None:
+            # bucket 1 (87 % of the bytes: the bottleneck weight) is complete now: its all-reduce runs on the collective
+            # stream while the encoder backward proceeds (SUM; the 1/W is folded into Adam)
+            work = dist.all_reduce(self.fp.grad[self.tail_off:], group=self.pg, async_op=True)
+        self.stack.backward(saved_stack, dU, self.ws, need_dx=False, top_stats=top_stats)
+        if self.world > 1:
+            head = self.fp.grad if work is None else self.fp.grad[:self.tail_off]
+            dist.all_reduce(head, group=self.pg)           # bucket 2: the encoder's gradients (0.12 MB)
+            if work is not None:
+                work.wait()
+        self._adam()
+        return stats
+
+    def step(self, x: Tensor) -> Tensor:
+        """One optimisation step on clips x [B,C,T,V]; returns the head's stats block (stats[0] = loss)."""
+        self.steps += 1
+        x = x.contiguous()
+        if not self.use_graph:
+            return self._body(x)
+        if self._graph is None or self._x_static.shape != x.shape:
+            self._x_static = x.clone()
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):          # warm-up outside capture (allocator, lazy module load)
+                self._body(self._x_static)
+            torch.cuda.current_stream().wait_stream(s)
+            self.steps += 1
+            self._graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph):
+                self._stats_static = self._body(self._x_static)
+        self._x_static.copy_(x)
+        self._graph.replay()
+        return self._stats_static
+
+
+class STSAETrainStep(_FlatStep):
     """One optimisation step of the decoder models on flat parameter / gradient buffers with the fused Adam -- the
     reference's training_step + optimizer step of
 
@@ -531,21 +580,12 @@ class STSAETrainStep:
             raise TypeError("STSAETrainStep drives an STSAE / STSVAE with the STS-GCN encoder")
         if mode not in ('ae', 'vae') or (mode == 'vae') != isinstance(model, STSVAE):
             raise ValueError(f"mode {mode!r} does not fit {type(model).__name__}")
-        self.model, self.mode = model, mode
-        self.alpha, self.lambda_, self.phi, self.beta, self.gamma = float(alpha), float(lambda_), float(phi), float(beta), float(gamma)
-        self.beta1, self.beta2, self.eps = float(betas[0]), float(betas[1]), float(eps)
-        self.pg = process_group
-        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         if not self.supports(model):
             raise TypeError("STSAETrainStep: projector / latent size outside the bottleneck kernels (latent rows <= 16, "
                             "'linear' projector)")
-        self.fp = FlatParams(model)
-        dev = self.fp.flat.device
-        self.m = torch.zeros_like(self.fp.flat)
-        self.v = torch.zeros_like(self.fp.flat)
-        self.lr = float(lr)
-        self.use_graph = False
-        self.ws = engine.Workspace()
+        super().__init__(model, lr, alpha, betas, eps, process_group)
+        self.mode = mode
+        self.lambda_, self.phi, self.beta, self.gamma = float(lambda_), float(phi), float(beta), float(gamma)
         self.enc = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.")
         # the decoder's first layer sees a rank-(latent + 1) input (rev_btlnk of the latent): folded into one streaming pass where that
         # layer would otherwise take the composed wide path (coskad_amd/lowrank.py)
@@ -558,10 +598,7 @@ class STSAETrainStep:
             self.dec = _FlatStack(dec_layers[1:], self.fp, "decoder.model.", first=1)
         else:
             self.dec = _FlatStack(dec_layers, self.fp, "decoder.model.")
-        self.center_acc = torch.zeros(ops.head_slots(model.latent_dim), device=dev, dtype=torch.float32)
-        self.reg_scale = 0.5 / self.fp.n_reg_tensors
-        self.reg_coef = self.alpha * 2.0 * self.reg_scale
-        self.steps = 0
+        self.center_acc = torch.zeros(ops.head_slots(model.latent_dim), device=self.fp.flat.device, dtype=torch.float32)
         self.last = {}
 
     @staticmethod
@@ -573,14 +610,6 @@ class STSAETrainStep:
                 return model.btlnk.hip_ok and model.btlnk.hidden_layers[0] <= 16 and model.latent_dim <= 16
             return isinstance(model.btlnk, torch.nn.Identity) and model.latent_dim + model.fc_var.out_features <= 16
         return isinstance(model.btlnk, torch.nn.Linear) and model.latent_dim <= 16
-
-    def set_lr(self, lr: float) -> None:
-        self.lr = float(lr)
-
-    _adam = STSETrainStep._adam
-
-    def reg_loss(self) -> Tensor:
-        return ops.sqnorm(self.fp.flat, self.fp.reg_mask, self.reg_scale)
 
     def step(self, x: Tensor) -> Dict[str, Tensor]:
         """-> {'rec': F.mse_loss(x_rec, x), 'head': MSE(z, c) | KL, ('exp': mean(1 / kappa)), 'z': the latents}"""
@@ -608,18 +637,8 @@ class STSAETrainStep:
             if mlp:
                 # `mlp` projector (vae.py:141-146): wide Linear on the bottleneck kernel, [BatchNorm1d, ReLU, Linear] blocks on
                 # csrc/mlp_head.hip; the two small heads act on its [B, latent] output inside the local autograd graph
-                if B == 1:
-                    raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d of the mlp projector)")
-                first = m.btlnk.net[0]
-                W, b = first.weight, first.bias
-                y = ops.btlnk_fwd(U, W, b, slope, ws=self.ws)
-                mlp_saved = []
-                for i, (bn, lin) in enumerate(m.btlnk.blocks()):
-                    zz, stat = ops.mlp_head_fwd(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                                lin.weight, lin.bias, True, momentum=ops.bn_momentum(bn), eps=bn.eps)
-                    mlp_saved.append((y, stat, bn, lin, f"btlnk.net.{3 * i + 1}.", f"btlnk.net.{3 * i + 3}."))
-                    y = zz
-                Hd = y
+                W = m.btlnk.net[0].weight
+                Hd, mlp_saved = self._mlp_forward(U, slope)
                 head_params = [m.fc_mean.weight, m.fc_mean.bias, m.fc_var.weight, m.fc_var.bias]
             else:
                 W = torch.cat([m.fc_mean.weight, m.fc_var.weight], 0)             # heads stacked: one pass over U
@@ -701,9 +720,7 @@ class STSAETrainStep:
                     for n, g_ in zip(("fc_mean.weight", "fc_mean.bias", "fc_var.weight", "fc_var.bias"), res[1:]):
                         gv[n].copy_(g_)
             if mlp_saved is not None:
-                for y_in, stat, bn, lin, bname, lname in reversed(mlp_saved):
-                    g = {"gamma": gv[bname + "weight"], "beta": gv[bname + "bias"], "W2": gv[lname + "weight"], "b2": gv.get(lname + "bias")}
-                    dHd = ops.mlp_head_bwd(y_in, stat, bn.weight, bn.bias, lin.weight, dHd, g, True)
+                dHd = self._mlp_backward(mlp_saved, dHd)
         tctx, tlayers = self.enc.top(enc_saved)
         bb = lambda gW_, gb_: engine.btlnk_backward(tctx, tlayers, U, W, dHd, slope, gW_, gb_, self.enc.last_slope_grad, self.ws)
         if self.mode == 'ae':
@@ -725,7 +742,7 @@ class STSAETrainStep:
         return out
 
 
-class AutogradTrainStep:
+class AutogradTrainStep(_OneClassHead):
     """Same interface as STSETrainStep for models the flat-buffer path does not take: the plain-GCN encoders, `mlp` projectors and
     latents beyond the bottleneck kernels' widths.  Forward / backward go through the module
     surface (autograd nodes around the HIP kernels, library GEMMs where the module uses them); the one-class head and
@@ -756,14 +773,7 @@ class AutogradTrainStep:
         self.opt.zero_grad(set_to_none=True)
         z = m(x)
         zd = z.detach().contiguous()
-        if self.head == 'euclidean':
-            stats, dz, _ = ops.mse_head(zd, m.c, acc=self.center_acc)
-        elif self.head == 'poincare':
-            stats, dz, _, _ = ops.poincare_head(zd, m.c, acc=self.center_acc)
-        elif self.head == 'mahalanobis':
-            stats, dz, _ = ops.mahalanobis_head(zd, m.c, m.inv_cov_matrix, acc=self.center_acc, gram=self.gram_acc)
-        else:
-            raise ValueError(f"unknown head {self.head}")
+        stats, dz = self._head(zd)
         z.backward(dz)
         with torch.no_grad():
             coef = self.alpha * 2.0 * self.reg_scale          # d/dp of alpha * reg_scale * sum p^2
@@ -778,23 +788,12 @@ class AutogradTrainStep:
         with torch.no_grad():
             return self.reg_scale * sum((p.float() ** 2).sum() for p in self.reg_params).reshape(1)
 
-    def refresh_center(self, eps: float = 1e-3) -> Tensor:
-        parallel.allreduce_sum_(self.center_acc, self.pg)
-        L = self.model.latent_dim
-        c = ops.center_finalize(self.center_acc, eps, L) if self.head != 'poincare' else ops.midpoint_finalize(self.center_acc, L)
-        self.model.c.copy_(c)
-        self.center_acc.zero_()
-        return self.model.c
-
-    refresh_inv_cov = STSETrainStep.refresh_inv_cov
-
 
 def make_train_step(model, **kw):
     """STSETrainStep (flat buffers, fused Adam, no autograd) for every STS-GCN encoder -- tile kernels and wide layers alike -- with a
     linear or in-width mlp projector; AutogradTrainStep for what is left: the plain-GCN encoders, projectors / latents beyond the
     bottleneck kernels."""
-    from .models.common.components import Encoder
-    from .models.common.components import MLP
+    from .models.common.components import MLP, Encoder
     btl = getattr(model, 'btlnk', None)
     proj_ok = isinstance(btl, torch.nn.Linear) or (isinstance(btl, MLP) and btl.hip_ok)
     fast = proj_ok and isinstance(getattr(model, 'encoder', None), Encoder) and model.latent_dim <= ops.BTLNK_LMAX

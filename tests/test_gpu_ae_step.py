@@ -385,7 +385,7 @@ def test_narrow_output_layer_by_commutation_equals_the_layer_kernels(V, monkeypa
         m.load_state_dict(st)
         m.cuda().train()
         eng = trainer.STSAETrainStep(m, mode='ae', lr=0.0, alpha=0.0, lambda_=0.8)
-        assert any(s[0] == 'narrow' for s in eng.dec.segs) == on
+        assert any(s.kind == 'narrow' for s in eng.dec.segs) == on
         out = eng.step(x)
         torch.cuda.synchronize()
         res[on] = (float(out['rec']), float(out['head']), {n: v.cpu().numpy().copy() for n, v in eng.fp.gviews.items()},
@@ -414,7 +414,7 @@ def test_eval_after_training_through_the_narrow_and_folded_paths_sees_the_new_we
     try:
         m = STSAE(2, [16, 8, 16], 16, 8, 12, 17, 'sts_gcn', 'linear', 'euclidean', 0.0).cuda()
         eng = STSAETrainStep(m.train(), mode='ae', lr=5e-3, alpha=0.0, lambda_=1.0)
-        assert eng.lowrank is not None and any(s[0] == 'narrow' for s in eng.dec.segs)
+        assert eng.lowrank is not None and any(s.kind == 'narrow' for s in eng.dec.segs)
         x = R.synthetic_clips(64, 2, 12, 17, seed=3).cuda()
 
         def recon():
@@ -433,3 +433,61 @@ def test_eval_after_training_through_the_narrow_and_folded_paths_sees_the_new_we
         np.testing.assert_allclose(r1.numpy(), ref.numpy(), rtol=2e-4, atol=2e-5)
     finally:
         lowrank.MODE = keep
+
+
+def _ae_step_on_two_paths(monkeypatch, channels, hidden, V, switches, expect):
+    """One STSAETrainStep step (lr = 0, ragged batch of 37 clips) of the same model with the trainer's `switches` off and on ->
+    {on: (rec, head, gradient views, running statistics)}; asserts the two losses, every gradient view and the running statistics
+    equal within the tolerances of test_narrow_output_layer_by_commutation_equals_the_layer_kernels.  expect: (enc kinds, dec kinds)
+    of the run with the switches on; off, every layer sits in a tile run."""
+    from coskad_amd import trainer
+    from coskad_amd.models.sts.ae import STSAE
+    from oracle import ref_cpu as R
+    torch.manual_seed(5)
+    make = lambda: STSAE(2, list(channels), hidden, 8, 12, V, 'sts_gcn', 'linear', 'euclidean', 0.0)
+    st = {k: v.detach().clone() for k, v in make().state_dict().items()}
+    x = R.synthetic_clips(37, 2, 12, V, seed=6).cuda()
+    res = {}
+    for on in (False, True):
+        for name in switches:
+            monkeypatch.setattr(trainer, name, on)
+        m = make()
+        m.load_state_dict(st)
+        m.cuda().train()
+        eng = trainer.STSAETrainStep(m, mode='ae', lr=0.0, alpha=0.0, lambda_=0.8)
+        assert eng.lowrank is not None
+        kinds = ([s.kind for s in eng.enc.segs], [s.kind for s in eng.dec.segs])
+        assert kinds == (expect if on else (['tile'], ['tile'])), kinds
+        out = eng.step(x)
+        torch.cuda.synchronize()
+        res[on] = (float(out['rec']), float(out['head']), {n: v.cpu().numpy().copy() for n, v in eng.fp.gviews.items()},
+                   {k: v.cpu().numpy().copy() for k, v in m.state_dict().items() if "running" in k or "num_batches" in k})
+    a, b = res[False], res[True]
+    print("rec", a[0], b[0], "head", a[1], b[1])
+    np.testing.assert_allclose(b[0], a[0], rtol=1e-5)
+    np.testing.assert_allclose(b[1], a[1], rtol=1e-5)
+    gmax = max(np.abs(v).max() for v in a[2].values())
+    for n, ref in a[2].items():
+        print(n, "max|ref|", float(np.abs(ref).max()), "max|diff|", float(np.abs(b[2][n] - ref).max()))
+        np.testing.assert_allclose(b[2][n], ref, rtol=2e-3, atol=2e-4 * np.abs(ref).max() + 2e-5 * gmax, err_msg=n)
+    for k, ref in a[3].items():
+        np.testing.assert_allclose(b[3][k], ref, rtol=1e-4, atol=1e-6, err_msg=k)
+    return res
+
+
+@pytest.mark.parametrize("V", [17, 25])
+def test_narrow_layer_above_a_commuted_layer_equals_the_layer_kernels(V, monkeypatch):
+    """Decoder 32 -> 32 (folded), 32 -> 16 (commuted), 16 -> 2 (narrow): the narrow layer's backward writes the commuted layer's
+    PReLU-weight gradient.  Against the same model with every layer on the tile kernels."""
+    _ae_step_on_two_paths(monkeypatch, [16, 32], 32, V, ("COMMUTE", "NARROW_OUT"), (['tile'], ['commute', 'narrow']))
+
+
+@pytest.mark.parametrize("V", [17, 25])
+def test_narrow_layer_in_mid_stack_equals_the_layer_kernels(V, monkeypatch):
+    """Encoder 2 -> 32, 32 -> 2 (narrow), 2 -> 32, 32 -> 64 and its mirror: a tile run above a narrow layer writes that layer's
+    PReLU-weight gradient (non-zero on both paths)."""
+    res = _ae_step_on_two_paths(monkeypatch, [32, 2, 32], 64, V, ("NARROW_OUT",),
+                                (['tile', 'narrow', 'tile'], ['narrow', 'tile', 'narrow']))
+    for on in (False, True):
+        for n in ("encoder.model.1.prelu.weight", "decoder.model.1.prelu.weight"):
+            assert np.abs(res[on][2][n]).max() > 0, (on, n)

@@ -734,7 +734,7 @@ def test_flat_train_step_on_wide_stacks(chans, hid):
     m = build()
     assert any(l.is_wide for l in m.encoder.model)
     eng = make_train_step(m, lr=0.0, alpha=0.0, head='euclidean')           # lr 0: the step leaves the gradients, not an update
-    assert isinstance(eng, STSETrainStep) and eng.stack is not None
+    assert isinstance(eng, STSETrainStep) and any(s.kind == 'wide' for s in eng.stack.segs)
     stats = eng.step(x.cuda())
     params = {k: v.clone().requires_grad_(True) for k, v in st.items() if R.is_param_key(k) and v.is_floating_point()}
     sto = dict(st)
