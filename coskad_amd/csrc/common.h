@@ -57,6 +57,14 @@ struct ProbeScope {   // brackets ONE kernel launch with events when the probe i
   bool armed_ = false;
 };
 
+// gcn_window.hip: the mixing kernels of the window lengths 8, 16 and 24 (coskad_window_ok), behind the entry points of
+// stsgcn_fwd.hip / stsgcn_bwd.hip.  dX NULL: parameter gradients only.
+int launch_window_gcn(const float* in, float* out, const float* Aw, const float* Tw, int rows, int T, int V, int adjoint,
+                      hipStream_t st);
+int launch_window_params(const float* x, const float* dZ, const float* Aw, const float* Tw, float* dA, float* dT, void* ws,
+                         int accumulate, int rows, int T, int V, hipStream_t st, float* dX, const float* add);
+size_t window_params_ws_bytes(int T, int V);
+
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 
@@ -120,8 +128,10 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// (T,V) geometries the kernels are instantiated for.  17 = COCO joints (default),
+// (T,V) geometries the tile kernels are instantiated for.  17 = COCO joints (default),
 // 25 = NTU layout (BASELINE config 4), 14 = headless, 18 = kp18 (wrappers, staticCenter.py:70-75).
+// Window lengths 8, 16 and 24 have mixing kernels only (gcn_window.hip, coskad_window_ok): the entry points that
+// serve them branch there BEFORE this dispatch, which stays at T = 12.
 #define COSKAD_DISPATCH_TV(T_, V_, CALL)                                   \
   do {                                                                      \
     if ((T_) == 12 && (V_) == 17) { CALL(12, 17); }                         \
@@ -129,7 +139,8 @@ __device__ __forceinline__ float wave_sum(float v) {
     else if ((T_) == 12 && (V_) == 14) { CALL(12, 14); }                    \
     else if ((T_) == 12 && (V_) == 18) { CALL(12, 18); }                    \
     else return coskad::fail(COSKAD_ERR_SHAPE,                              \
-        "unsupported (n_frames=%d, n_joints=%d): built for T=12, V in {14,17,18,25}", (T_), (V_)); \
+        "unsupported (n_frames=%d, n_joints=%d): tile kernels are built for T=12, mixing kernels for T in {8,12,16,24}, " \
+        "V in {14,17,18,25}", (T_), (V_)); \
   } while (0)
 
 }  // namespace coskad

@@ -1693,7 +1693,10 @@ int coskad_layer_fits(int Ci, int Co, int T, int V) {
   return data <= cap && red <= cap && fwd <= cap;
 }
 
+int coskad_window_ok(int T, int V);   // gcn_window.hip
+
 size_t coskad_gcn_bwd_params_ws_bytes(int T, int V) {
+  if (coskad_window_ok(T, V)) return window_params_ws_bytes(T, V);   // one partial row per workgroup of its persistent grid
   return (size_t)kMaxGridBwd * ((size_t)T * V * V + (size_t)V * T * T) * sizeof(float);
 }
 
@@ -1706,6 +1709,7 @@ int coskad_gcn_bwd_params_f32(const float* x, const float* dZ, const float* A, c
   if (!x || !dZ || !A || !Tm || !dA || !dT || !ws) return fail(COSKAD_ERR_ARG, "gcn_bwd_params: null pointer");
   if (rows <= 0) return fail(COSKAD_ERR_ARG, "gcn_bwd_params: rows=%d", rows);
   if (ws_bytes < coskad_gcn_bwd_params_ws_bytes(T, V)) return fail(COSKAD_ERR_WORKSPACE, "gcn_bwd_params: workspace too small");
+  if (coskad_window_ok(T, V)) return launch_window_params(x, dZ, A, Tm, dA, dT, ws, accumulate, rows, T, V, stream, nullptr, nullptr);
 #define CALL(T_, V_) return launch_gcn_bwd_params<T_, V_>(x, dZ, A, Tm, dA, dT, ws, accumulate, rows, stream)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL
@@ -1720,6 +1724,7 @@ int coskad_gcn_bwd_params_dx_f32(const float* x, const float* dZ, const float* A
   if (!x || !dZ || !A || !Tm || !dA || !dT || !dX || !ws) return fail(COSKAD_ERR_ARG, "gcn_bwd_params_dx: null pointer");
   if (rows <= 0) return fail(COSKAD_ERR_ARG, "gcn_bwd_params_dx: rows=%d", rows);
   if (ws_bytes < coskad_gcn_bwd_params_ws_bytes(T, V)) return fail(COSKAD_ERR_WORKSPACE, "gcn_bwd_params_dx: workspace too small");
+  if (coskad_window_ok(T, V)) return launch_window_params(x, dZ, A, Tm, dA, dT, ws, accumulate, rows, T, V, stream, dX, dX_add);
 #define CALL(T_, V_) return launch_gcn_bwd_params<T_, V_>(x, dZ, A, Tm, dA, dT, ws, accumulate, rows, stream, dX, dX_add)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL

@@ -332,6 +332,8 @@ using namespace coskad;
 
 extern "C" {
 
+int coskad_window_ok(int T, int V);   // gcn_window.hip
+
 int coskad_layer_apply_f32(const float* in, float* out, const float* A, const float* Tm,
                            const float* wfold, const float* bias, const float* in_slope,
                            const float* out_slope, int B, int Ci, int Co, int T, int V,
@@ -347,6 +349,7 @@ int coskad_gcn_f32(const float* in, float* out, const float* A, const float* Tm,
                    int adjoint, hipStream_t stream) {
   if (!in || !out || !A || !Tm) return fail(COSKAD_ERR_ARG, "gcn: null pointer");
   if (rows <= 0) return fail(COSKAD_ERR_ARG, "gcn: rows=%d", rows);
+  if (coskad_window_ok(T, V)) return launch_window_gcn(in, out, A, Tm, rows, T, V, adjoint, stream);
 #define CALL(T_, V_) return launch_gcn<T_, V_>(in, out, A, Tm, rows, adjoint, stream)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL

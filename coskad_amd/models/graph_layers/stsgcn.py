@@ -18,6 +18,7 @@ from ... import engine, ops
 
 Tensor = torch.Tensor
 _FITS: dict = {}      # (Ci, Co, T, V) -> the tile kernels take the layer (coskad_layer_fits)
+TILE_WINDOW = 12     # window length (dataset_seg_len) the tile kernels are built for (csrc/common.h: COSKAD_DISPATCH_TV)
 WIDE_CHANNELS = 64   # widest layer the fused tile kernels take (csrc: `channels > 64 not supported`)
 
 
@@ -286,6 +287,10 @@ class ST_GCNN_layer(nn.Module):
             raise ValueError(f"dropout probability has to be in [0, 1), but got {dropout}")
         if emb_dim is not None:
             raise NotImplementedError("coskad_amd ST_GCNN_layer: emb_dim is unused by the reference's models")
+        if not ((time_dim == TILE_WINDOW and joints_dim in ops.JOINT_LAYOUTS) or ops.window_ok(time_dim, joints_dim)):
+            raise ValueError(f"coskad_amd ST_GCNN_layer: unsupported (time_dim={time_dim}, joints_dim={joints_dim}): the kernels are "
+                             f"built for time_dim in {sorted((TILE_WINDOW,) + ops.WINDOW_LENGTHS)} x joints_dim in "
+                             f"{list(ops.JOINT_LAYOUTS)}")
         self.build_model()
         self._ws = engine.Workspace()
 
@@ -314,9 +319,13 @@ class ST_GCNN_layer(nn.Module):
 
     @property
     def is_wide(self) -> bool:
-        """Beyond the LDS-resident tile kernels: more than 64 channels on either side, or a clip whose images do not fit
-        the 160 KB of LDS (64 input channels on the 25-joint layout: the default-width decoder of BASELINE config 4)."""
+        """Beyond the LDS-resident tile kernels: more than 64 channels on either side, a window length other than 12, or a clip whose
+        images do not fit the 160 KB of LDS (64 input channels on the 25-joint layout: the default-width decoder of BASELINE config 4)."""
         if max(self.in_channels, self.out_channels) > WIDE_CHANNELS:
+            return True
+        if self.time_dim != TILE_WINDOW:
+            # the tile kernels are built for 12-frame windows; other window lengths (ops.window_ok) have mixing kernels only
+            # (csrc/gcn_window.hip), which is all the composed path needs of the geometry
             return True
         if self.dropout > 0:
             # train-mode Dropout (stsgcn.py:66) sits between the tcn BatchNorm and the residual add, so the two branches cannot be

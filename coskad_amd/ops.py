@@ -44,6 +44,17 @@ def cop(co: int) -> int:
     return (co + 15) // 16 * 16
 
 
+WINDOW_LENGTHS = (8, 16, 24)        # window lengths beside 12 that have mixing kernels (csrc/gcn_window.hip)
+JOINT_LAYOUTS = (14, 17, 18, 25)    # joint counts every (T, V) kernel is instantiated for
+
+
+def window_ok(T: int, V: int) -> bool:
+    """Host arithmetic of `coskad_window_ok`: (T, V) has mixing kernels only, so a layer of that window length takes the composed
+    path.  False at T = 12, the tile kernels' geometry.  Restated here so that building a model needs no native library;
+    tests/test_window_host.py holds the two in agreement."""
+    return T in WINDOW_LENGTHS and V in JOINT_LAYOUTS
+
+
 def gcn(x: Tensor, A: Tensor, Tm: Tensor, adjoint: bool = False) -> Tensor:
     """ConvTemporalGraphical.forward (reference stsgcn.py:143-156) or its adjoint."""
     N, C, T, V = x.shape
@@ -1317,21 +1328,23 @@ def gcn_bwd_params(x: Tensor, dZ: Tensor, A: Tensor, Tm: Tensor):
 
 
 def gcn_bwd_params_dx(x: Tensor, dZ: Tensor, A: Tensor, Tm: Tensor, add: Optional[Tensor] = None, dA: Optional[Tensor] = None,
-                      dT: Optional[Tensor] = None):
+                      dT: Optional[Tensor] = None, accumulate: bool = False):
     """(dA, dT, dX) of ConvTemporalGraphical in one pass over dZ: dX = gcn^T(dZ) (+ add, e.g. an identity residual's gradient);
-    dA / dT: destinations (e.g. views of a flat gradient buffer) instead of fresh tensors."""
+    dA / dT: destinations (e.g. views of a flat gradient buffer) instead of fresh tensors; accumulate: add to them."""
     N, C, T, V = x.shape
     _chk(x, "x"); _chk(dZ, "dZ", x.shape); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T)); _chk(add, "add", x.shape, optional=True)
     fn = _lib.lib().coskad_gcn_bwd_params_ws_bytes
     fn.restype = ctypes.c_size_t
     nbytes = fn(i32(T), i32(V))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    if accumulate and (dA is None or dT is None):
+        raise ValueError("gcn_bwd_params_dx: accumulate needs the dA and dT to add to")
     dA = torch.empty_like(A) if dA is None else dA
     dT = torch.empty_like(Tm) if dT is None else dT
     _chk(dA, "dA", (T, V, V)); _chk(dT, "dT", (V, T, T))
     dX = torch.empty_like(x)
     call("coskad_gcn_bwd_params_dx_f32", ptr(x), ptr(dZ), ptr(A), ptr(Tm), ptr(dA), ptr(dT), ptr(dX), ptr(add), ptr(ws),
-         ctypes.c_size_t(nbytes), i32(0), i32(N * C), i32(T), i32(V), _stream())
+         ctypes.c_size_t(nbytes), i32(1 if accumulate else 0), i32(N * C), i32(T), i32(V), _stream())
     return dA, dT, dX
 
 

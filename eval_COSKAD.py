@@ -34,7 +34,7 @@ def main():
     trainer = Trainer()
     if args.data_dir == 'synthetic':
         test, gts = make_dataset(n_scenes=2, n_clips=3, n_persons=3, clip_len=200, num_transform=args.dataset_num_transform,
-                                 anomaly=True, seed=args.seed + 1)
+                                 anomaly=True, seed=args.seed + 1, T=args.dataset_seg_len)
         model.gts = gts
         out = trainer.predict(model, lambda: batches(test, args.dataset_batch_size), ckpt_path=path)
     else:

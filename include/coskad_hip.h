@@ -32,8 +32,15 @@ int coskad_probe_end(float* avg_ms, int* launches);
 
 /* ---- forward ------------------------------------------------------------------------ */
 
+/* 1 for the (T, V) that have MIXING kernels only (csrc/gcn_window.hip): T in {8, 16, 24} x V in {14, 17, 18, 25}.  0 otherwise,
+ * T = 12 -- the geometry of the tile kernels -- included.  coskad_gcn_f32, coskad_gcn_bwd_params_f32, coskad_gcn_bwd_params_dx_f32
+ * and coskad_gcn_bwd_params_ws_bytes take these geometries; every other entry point with a (T, V) stays at T = 12, so a layer of
+ * such a window length is composed from the mixing, coskad_gemm_f32 and the coskad_bn2_* kernels.  Host arithmetic. */
+int coskad_window_ok(int T, int V);
+
 /* ConvTemporalGraphical.forward (models/graph_layers/stsgcn.py:143-156) on rows = N*C rows
- * of T*V floats; adjoint != 0 applies the transposed operator (its backward w.r.t. X). */
+ * of T*V floats; adjoint != 0 applies the transposed operator (its backward w.r.t. X).
+ * (T, V): T = 12 or coskad_window_ok; others fail with COSKAD_ERR_SHAPE ("unsupported ...") before the device is touched. */
 int coskad_gcn_f32(const float* in, float* out, const float* A, const float* Tm, int rows, int T, int V,
                    int adjoint, hipStream_t stream);
 
@@ -321,7 +328,8 @@ int coskad_layer_gcn_params_f32(const float* in, const float* in_slope, const fl
                                 int B, int Ci, int T, int V, hipStream_t stream);
 
 /* Parameter gradients of ConvTemporalGraphical alone (stsgcn.py:154-155), given its input x and
- * the gradient dZ of its output; rows = N*C. */
+ * the gradient dZ of its output; rows = N*C.  The workspace holds one partial row of T*V*V + V*T*T floats per workgroup:
+ * 1024 rows at T = 12, 256 or 512 at the coskad_window_ok geometries. */
 size_t coskad_gcn_bwd_params_ws_bytes(int T, int V);
 int coskad_gcn_bwd_params_f32(const float* x, const float* dZ, const float* A, const float* Tm, float* dA,
                               float* dT, void* ws, size_t ws_bytes, int accumulate, int rows, int T, int V,

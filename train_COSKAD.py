@@ -49,9 +49,9 @@ def main():
     trainer = Trainer(max_epochs=args.ae_epochs, ckpt_dir=args.ckpt_dir, save_top_k=2)
     if args.data_dir == 'synthetic':
         train, _ = make_dataset(n_scenes=4, n_clips=4, n_persons=3, clip_len=200, num_transform=args.dataset_num_transform,
-                                anomaly=False, seed=args.seed)
+                                anomaly=False, seed=args.seed, T=args.dataset_seg_len)
         val, gts = make_dataset(n_scenes=2, n_clips=3, n_persons=3, clip_len=200, num_transform=args.dataset_num_transform,
-                                anomaly=True, seed=args.seed + 1)
+                                anomaly=True, seed=args.seed + 1, T=args.dataset_seg_len)
         model.gts = gts
         epoch = [0]
 
