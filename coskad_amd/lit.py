@@ -111,6 +111,9 @@ class LitEncoder(nn.Module):
         self.model.train()
         # `sync_batchnorm` (not a key of the reference's yamls, whose DDP keeps per-rank BatchNorm statistics): optional SyncBN
         extra = {"sync_bn": True} if bool(getattr(self.args, "sync_batchnorm", False)) else {}
+        # `flat_plain_gcn` (not a key of the reference's yamls either): the Learnable_GCN / Static_GCN encoders train on the flat step
+        # with the fused layer kernels unless the yaml says `flat_plain_gcn: false` (then: the autograd step)
+        extra["flat_plain_gcn"] = bool(getattr(self.args, "flat_plain_gcn", True))
         self._engine = make_train_step(self.model, lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)),
                                      head="poincare" if self.hyperbolic else ("mahalanobis" if maha else "euclidean"), **extra)
         self._epoch = 0

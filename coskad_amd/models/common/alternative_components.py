@@ -5,7 +5,8 @@ A layer is `ReLU(A' . (X W) + b)` on X [B, T*V, C] with one dense (T*V x T*V) ad
 fixed row-normalised skeleton-in-time graph.  Here the activations stay in the [B, C, T*V] layout of the rest of the
 library (the reference's permutes at alternative_components.py:173-175 become strides), and both products, their
 gradients, the bias + ReLU epilogue and the adjacency softmax run on this repo's fp32 MFMA GEMM / elementwise kernels
-(csrc/gemm.hip) -- `_PlainGCNLayerFn` below.  The (T V x T V) mixing is applied on the narrower side of the layer
+(csrc/gemm.hip) -- `_PlainGCNLayerFn` below; without gradients a layer is one launch of csrc/plain_gcn.hip (`_plain_layer`), and
+the flat train step (trainer.py, `_PlainLayer`) drives that file's forward and backward kernels directly.  The (T V x T V) mixing is applied on the narrower side of the layer
 (A'.(X W) = (A'.X) W).  state_dict keys equal the reference's (`gcns.{i}.gcn.{weight,bias,Adj}`, buffer `Adj`)."""
 from __future__ import annotations
 
@@ -94,6 +95,14 @@ class _PlainGCNLayerFn(torch.autograd.Function):
         return dX, dW, dA, db
 
 
+def _plain_layer(X: Tensor, W: Tensor, Ap: Tensor, bias) -> Tensor:
+    """One layer on X [B, Ci, P].  Without gradients (scoring, validation, the centre initialisation) the fused forward kernel
+    of csrc/plain_gcn.hip where it takes the shape; with gradients enabled the autograd composition above."""
+    if not torch.is_grad_enabled() and X.is_cuda and ops.plain_gcn_ok(W.shape[0], W.shape[1], X.shape[2]):
+        return ops.plain_gcn_fwd(X.contiguous(), W, Ap.contiguous(), bias)[0]
+    return _PlainGCNLayerFn.apply(X, W, Ap, bias)
+
+
 class LearnableGraphConvBlock(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, n_frames: int, n_joints: int, bias: bool = True) -> None:
         super().__init__()
@@ -126,7 +135,7 @@ class LearnablePlain_GCNN_Layer(nn.Module):
 
     def forward(self, X: Tensor) -> Tensor:
         """X [B, Ci, T*V] -> [B, Co, T*V] (bias + ReLU fused into the second GEMM's epilogue)."""
-        return _PlainGCNLayerFn.apply(X, self.gcn.weight, self.gcn.adjacency(), self.gcn.bias)
+        return _plain_layer(X, self.gcn.weight, self.gcn.adjacency(), self.gcn.bias)
 
 
 class GraphConvBlock(nn.Module):
@@ -152,7 +161,7 @@ class StaticPlain_GCNN_Layer(nn.Module):
         self.act = nn.ReLU()
 
     def forward(self, X: Tensor, Adj: Tensor) -> Tensor:
-        return _PlainGCNLayerFn.apply(X, self.gcn.weight, Adj, self.gcn.bias)
+        return _plain_layer(X, self.gcn.weight, Adj, self.gcn.bias)
 
 
 class _PlainGCNEncoder(nn.Module):

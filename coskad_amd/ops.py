@@ -788,12 +788,61 @@ def softmax_rows(x: Tensor) -> Tensor:
     return y
 
 
-def softmax_rows_bwd(y: Tensor, dy: Tensor) -> Tensor:
+def softmax_rows_bwd(y: Tensor, dy: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """out: where dx goes (a flat gradient view), a fresh tensor otherwise"""
     n = y.shape[0]
-    _chk(y, "y", (n, n)); _chk(dy, "dy", (n, n))
-    dx = torch.empty_like(y)
+    _chk(y, "y", (n, n)); _chk(dy, "dy", (n, n)); _chk(out, "out", (n, n), optional=True)
+    dx = torch.empty_like(y) if out is None else out
     call("coskad_softmax_rows_bwd_f32", ptr(y), ptr(dy), ptr(dx), i32(n), _stream())
     return dx
+
+
+PLAIN_GCN_CMAX = 64                               # widest channel count of the fused plain-GCN kernels (csrc/plain_gcn.hip)
+PLAIN_GCN_POSITIONS = (168, 204, 216, 300)        # 12 frames x JOINT_LAYOUTS
+
+
+def plain_gcn_ok(Ci: int, Co: int, P: int) -> bool:
+    """Host arithmetic of `coskad_plain_gcn_ok`: the fused plain-GCN kernels take a (Ci -> Co) layer on P = T * V positions; other
+    shapes are composed from the strided GEMM.  Restated here so that building a model needs no native library;
+    tests/test_plain_gcn_host.py holds the two in agreement."""
+    return 1 <= Ci <= PLAIN_GCN_CMAX and 1 <= Co <= PLAIN_GCN_CMAX and P in PLAIN_GCN_POSITIONS
+
+
+def plain_gcn_fwd(X: Tensor, W: Tensor, Ap: Tensor, bias: Optional[Tensor] = None, save: bool = False, grid_cap: int = 0):
+    """O[b] = relu(W^T . X[b] . A'^T + bias) in one launch (csrc/plain_gcn.hip): X [B, Ci, P], W [Ci, Co], A' [P, P] -> (O [B, Co, P],
+    S).  save: S is the narrow-side intermediate (Y = X . A'^T [B, Ci, P] when Ci <= Co, H = W^T . X [B, Co, P] otherwise) for the
+    backward; None otherwise -- it then never leaves the chip."""
+    B, Ci, P = X.shape
+    Co = W.shape[1]
+    _chk(X, "X"); _chk(W, "W", (Ci, Co)); _chk(Ap, "Ap", (P, P)); _chk(bias, "bias", (Co,), optional=True)
+    O = torch.empty(B, Co, P, device=X.device, dtype=torch.float32)
+    S = torch.empty(B, min(Ci, Co), P, device=X.device, dtype=torch.float32) if save else None
+    call("coskad_plain_gcn_fwd_f32", ptr(X), ptr(W), ptr(Ap), ptr(bias), ptr(O), ptr(S), i32(B), i32(Ci), i32(Co), i32(P),
+         i32(grid_cap), _stream(), tag=(Ci, Co))
+    return O, S
+
+
+def plain_gcn_bwd(X: Tensor, S: Optional[Tensor], O: Tensor, dO: Tensor, W: Tensor, Ap: Tensor, dW: Tensor, db: Optional[Tensor],
+                  need_dx: bool = True, need_da: bool = False, accumulate: bool = False, grid_cap: int = 0):
+    """Backward of plain_gcn_fwd in one launch + the fixed-order reduction of its partial rows: dW [Ci, Co] and db [Co] (None: no
+    bias) are written (accumulate: added to) in place -> (dX [B, Ci, P] or None, D or None).  S: plain_gcn_fwd's saved intermediate
+    (needed when Ci <= Co).  need_da: D is the narrow-side gradient for the adjacency gradient
+    dA'[q, p] = sum_rows D[r, q] Src[r, p], Src = X (Ci <= Co) or the saved H (Ci > Co) -- ops.gemm_rows_outer."""
+    B, Ci, P = X.shape
+    Co = W.shape[1]
+    Cn = min(Ci, Co)
+    _chk(X, "X"); _chk(W, "W", (Ci, Co)); _chk(Ap, "Ap", (P, P)); _chk(O, "O", (B, Co, P)); _chk(dO, "dO", (B, Co, P))
+    _chk(S, "S", (B, Cn, P), optional=Ci > Co); _chk(dW, "dW", (Ci, Co)); _chk(db, "db", (Co,), optional=True)
+    fn = _lib.lib().coskad_plain_gcn_ws_bytes
+    fn.restype = ctypes.c_size_t
+    nws = fn(i32(B), i32(Ci), i32(Co), i32(P), i32(grid_cap))
+    ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=X.device)
+    dX = torch.empty_like(X) if need_dx else None
+    D = torch.empty(B, Cn, P, device=X.device, dtype=torch.float32) if need_da else None
+    call("coskad_plain_gcn_bwd_f32", ptr(X), ptr(S), ptr(O), ptr(dO), ptr(W), ptr(Ap), ptr(dX), ptr(dW), ptr(db), ptr(D), ptr(ws),
+         ctypes.c_size_t(nws), i32(B), i32(Ci), i32(Co), i32(P), i32(1 if need_dx else 0), i32(1 if need_da else 0),
+         i32(1 if accumulate else 0), i32(grid_cap), _stream(), tag=(Ci, Co))
+    return dX, D
 
 
 def _bn2_ws(Nb: int, C: int, device, bwd: bool = False) -> Tensor:

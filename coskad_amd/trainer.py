@@ -341,6 +341,95 @@ class _FlatStack:
         return d
 
 
+class _FnCtx:
+    """what _PlainGCNLayerFn's forward / backward ask of their autograd context, for calling them without autograd"""
+
+    def save_for_backward(self, *tensors) -> None:
+        self.saved_tensors = tensors
+
+
+class _PlainLayer(_Segment):
+    """a plain-GCN layer O = relu(W^T X A'^T + bias) on [B, C, P] (alternative_components.py): one fused forward and one fused
+    backward kernel (csrc/plain_gcn.hip) where ops.plain_gcn_ok, the strided-GEMM composition of _PlainGCNLayerFn otherwise; hands
+    over an activated output.  `adj`: the static encoder's fixed graph (a buffer: no gradient), None for the learnable adjacency."""
+    kind = 'plain'
+    out_slope_grad = None
+
+    def __init__(self, mod, fp: "FlatParams", prefix: str, adj: Optional[Tensor] = None) -> None:
+        self.mod, self.adj = mod, adj
+        gv = fp.gviews
+        self.gW, self.gb, self.gAdj = gv[prefix + "gcn.weight"], gv.get(prefix + "gcn.bias"), gv.get(prefix + "gcn.Adj")
+        self.fused = ops.plain_gcn_ok(mod.in_channels, mod.out_channels, mod.time_dim * mod.joints_dim)
+
+    def forward(self, h, slope, ws):
+        gcn = self.mod.gcn
+        learn = self.adj is None
+        Ap = ops.softmax_rows(gcn.Adj) if learn else self.adj          # formed once: forward and backward share it
+        if self.fused:
+            # the narrow-side intermediate: Y (mix first) feeds dW; H (channel product first) feeds only the adjacency gradient
+            O, S = ops.plain_gcn_fwd(h, gcn.weight, Ap, gcn.bias, save=learn or self.mod.in_channels <= self.mod.out_channels)
+            return O, None, (h, Ap, S, O)
+        from .models.common.alternative_components import _PlainGCNLayerFn
+        ctx = _FnCtx()
+        O = _PlainGCNLayerFn.forward(ctx, h, gcn.weight, Ap, gcn.bias)
+        return O, None, (h, Ap, ctx, O)
+
+    def backward(self, saved, d, ws, need_dx, in_slope_grad):
+        X, Ap, S, O = saved
+        gcn = self.mod.gcn
+        learn = self.adj is None
+        B, Ci, P = X.shape
+        if self.fused:
+            dX, D = ops.plain_gcn_bwd(X, S, O, d.contiguous().view_as(O), gcn.weight, Ap, self.gW, self.gb, need_dx=need_dx,
+                                      need_da=learn)
+            if learn:      # dA'[q, p] = sum over (clip, channel) rows of D[r, q] Src[r, p]
+                src = X if Ci <= self.mod.out_channels else S
+                dA = ops.gemm_rows_outer(D.view(-1, P), src.view(-1, P), torch.empty(P, P, device=X.device, dtype=torch.float32))
+        else:
+            from .models.common.alternative_components import _PlainGCNLayerFn
+            S.needs_input_grad = (need_dx, True, learn, gcn.bias is not None)
+            dX, dW, dA, db = _PlainGCNLayerFn.backward(S, d.contiguous().view_as(O))
+            self.gW.copy_(dW)
+            if db is not None:
+                self.gb.copy_(db)
+        if learn:
+            ops.softmax_rows_bwd(Ap, dA, out=self.gAdj)
+        return dX if need_dx else None
+
+
+class _PlainGCNStack:
+    """EncoderLearnablePlainGCN / EncoderStaticPlainGCN behind _FlatStack's interface: one 'plain' segment per layer, on the
+    [B, C, T * V] view of the clips."""
+    last_slope_grad = None
+
+    def __init__(self, enc, fp: "FlatParams", prefix: str = "encoder.gcns.") -> None:
+        adj = getattr(enc, "Adj", None)              # the static encoder's buffer
+        self.segs = [_PlainLayer(l, fp, f"{prefix}{i}.", adj) for i, l in enumerate(enc.gcns)]
+
+    def forward(self, x: Tensor, ws: engine.Workspace, in_slope: Optional[Tensor] = None):
+        B, C, T, V = x.shape
+        h, saved = x.view(B, C, T * V), []
+        for seg in self.segs:
+            h, _, sv = seg.forward(h, None, ws)
+            saved.append(sv)
+        return h.view(B, h.shape[1], T, V), None, saved
+
+    def top(self, saved):
+        return None, None
+
+    def backward(self, saved, d_last: Tensor, ws: engine.Workspace, need_dx: bool, top_stats=None,
+                 in_slope_grad: Optional[Tensor] = None) -> Optional[Tensor]:
+        d = d_last
+        for k in range(len(self.segs) - 1, -1, -1):
+            d = self.segs[k].backward(saved[k], d, ws, need_dx or k > 0, None)
+        return d
+
+
+def _is_plain_gcn(enc) -> bool:
+    from .models.common.alternative_components import _PlainGCNEncoder
+    return isinstance(enc, _PlainGCNEncoder)
+
+
 class _OneClassHead:
     """The one-class heads and their centre / covariance bookkeeping (staticCenter.py:40-46,133-155; hyperbolic_encoder.py:175-183)
     for a step object with `model`, `head`, `pg`, `center_acc`, `gram_acc`."""
@@ -443,7 +532,8 @@ class _FlatStep:
 
 
 class STSETrainStep(_FlatStep, _OneClassHead):
-    """One-class training of an STSE (`linear` projector, or `mlp` within the HIP kernels' widths) without autograd.
+    """One-class training of an STSE (`linear` projector, or `mlp` within the HIP kernels' widths) without autograd: the STS-GCN
+    encoder, or a plain-GCN encoder (EncoderLearnablePlainGCN / EncoderStaticPlainGCN) on csrc/plain_gcn.hip.
 
     head: 'euclidean' -> F.mse_loss(z, c);  'poincare' -> dist(c, project(expmap0(z))).mean().
     """
@@ -465,7 +555,10 @@ class STSETrainStep(_FlatStep, _OneClassHead):
         self.gram_acc = torch.zeros(L, L, device=dev, dtype=torch.float32) if head == 'mahalanobis' else None
         # an encoder with layers beyond the LDS tile kernels (the wide C = 2 -> 256 stack, dropout) runs them on their explicit forward /
         # backward between the tile runs: main stream, eager launches
-        wide = any(l.is_wide for l in model.encoder.model)
+        plain_gcn = _is_plain_gcn(model.encoder)
+        wide = plain_gcn or any(l.is_wide for l in model.encoder.model)
+        if plain_gcn and (side_stream or use_graph):
+            raise ValueError("a plain-GCN encoder runs on the main stream, outside hipGraph capture")
         if wide and (side_stream or use_graph):
             raise ValueError("an encoder with wide layers runs on the main stream, outside hipGraph capture")
         # optional: dA / dT on a second stream beside the next layer's reductions.  Measured SLOWER on MI355X (2.43 vs
@@ -482,8 +575,12 @@ class STSETrainStep(_FlatStep, _OneClassHead):
         # the commuted kernels take a layer (32 -> 16 on the 25-joint layout) unless the step is asked for something only the plain
         # chain does: hipGraph capture, the side stream, SyncBN; an encoder without wide or commuted layers is one tile run (a
         # narrow-output layer alone does not split it)
-        plain = not wide and (use_graph or side_stream or sync_bn or not any(_is_commute(l) for l in model.encoder.model))
-        self.stack = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.", plain=plain, side=self.side, sync=self.sync_group)
+        if plain_gcn:
+            self.stack = _PlainGCNStack(model.encoder, self.fp)
+        else:
+            plain = not wide and (use_graph or side_stream or sync_bn or not any(_is_commute(l) for l in model.encoder.model))
+            self.stack = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.", plain=plain, side=self.side,
+                                    sync=self.sync_group)
         # gradient buckets for the data-parallel all-reduce: [encoder | bottleneck]; the bottleneck parameters are the
         # tail of the flat buffer (named_parameters order) and their gradients are final before the encoder backward
         names = self.fp.names
@@ -743,8 +840,9 @@ class STSAETrainStep(_FlatStep):
 
 
 class AutogradTrainStep(_OneClassHead):
-    """Same interface as STSETrainStep for models the flat-buffer path does not take: the plain-GCN encoders, `mlp` projectors and
-    latents beyond the bottleneck kernels' widths.  Forward / backward go through the module
+    """Same interface as STSETrainStep for models the flat-buffer path does not take: `mlp` projectors and latents beyond the
+    bottleneck kernels' widths; and the plain-GCN encoders when make_train_step is not asked for `flat_plain_gcn` (its default:
+    this step is the yardstick the flat plain-GCN step is held against).  Forward / backward go through the module
     surface (autograd nodes around the HIP kernels, library GEMMs where the module uses them); the one-class head and
     its gradient are the HIP head kernels (`z.backward(dz)`), the regulariser gradient is added to `.grad`, the
     optimiser is torch's Adam (calc_reg_loss / configure_optimizers of the reference wrappers)."""
@@ -789,14 +887,21 @@ class AutogradTrainStep(_OneClassHead):
             return self.reg_scale * sum((p.float() ** 2).sum() for p in self.reg_params).reshape(1)
 
 
-def make_train_step(model, **kw):
+def make_train_step(model, flat_plain_gcn: bool = False, **kw):
     """STSETrainStep (flat buffers, fused Adam, no autograd) for every STS-GCN encoder -- tile kernels and wide layers alike -- with a
-    linear or in-width mlp projector; AutogradTrainStep for what is left: the plain-GCN encoders, projectors / latents beyond the
-    bottleneck kernels."""
+    linear or in-width mlp projector, and with `flat_plain_gcn` for the plain-GCN encoders (Learnable_GCN / Static_GCN) behind such
+    a projector too (fused layer kernels, csrc/plain_gcn.hip; the wrappers ask for it).  AutogradTrainStep for what is left:
+    projectors / latents beyond the bottleneck kernels, and the plain-GCN encoders without `flat_plain_gcn`."""
     from .models.common.components import MLP, Encoder
     btl = getattr(model, 'btlnk', None)
+    enc = getattr(model, 'encoder', None)
     proj_ok = isinstance(btl, torch.nn.Linear) or (isinstance(btl, MLP) and btl.hip_ok)
-    fast = proj_ok and isinstance(getattr(model, 'encoder', None), Encoder) and model.latent_dim <= ops.BTLNK_LMAX
+    if flat_plain_gcn and proj_ok and _is_plain_gcn(enc) and model.latent_dim <= ops.BTLNK_LMAX:
+        kw.pop('use_graph', None); kw.pop('side_stream', None)      # main stream, eager launches, as for wide layers
+        if kw.get('sync_bn') and not (dist.is_available() and dist.is_initialized() and dist.get_world_size(kw.get('process_group')) > 1):
+            kw.pop('sync_bn')
+        return STSETrainStep(model, **kw)
+    fast = proj_ok and isinstance(enc, Encoder) and model.latent_dim <= ops.BTLNK_LMAX
     if fast:
         if any(l.is_wide for l in model.encoder.model):     # wide layers: main stream, eager launches
             kw.pop('use_graph', None); kw.pop('side_stream', None)

@@ -175,6 +175,28 @@ int coskad_relu_bwd_f32(const float* out, const float* dout, float* g, float* pa
 int coskad_softmax_rows_f32(const float* x, float* y, int n, hipStream_t stream);
 int coskad_softmax_rows_bwd_f32(const float* y, const float* dy, float* dx, int n, hipStream_t stream);
 
+/* ---- fused plain-GCN layer (learnable_gcn.py:54-72, gcn.py:48-54 + ReLU; csrc/plain_gcn.hip) ------------------------------------
+ * O[b] = relu(W^T . X[b] . A'^T + bias): X [B][Ci][P], W [Ci][Co], A' [P][P] (softmax of the learnable adjacency, or the fixed
+ * graph), bias [Co] or NULL, O [B][Co][P]; one launch, the narrow-side intermediate stays on chip.  The mixing runs on
+ * min(Ci, Co) channels: Y = X . A'^T first when Ci <= Co, H = W^T . X first otherwise.
+ * coskad_plain_gcn_ok: 1 <= Ci, Co <= 64 and P in {168, 204, 216, 300} (12 frames x 14 / 17 / 18 / 25 joints); other shapes fail
+ *   with COSKAD_ERR_SHAPE ("unsupported ...") before the device is touched -- compose them from coskad_gemm_f32.  Host arithmetic.
+ * save (optional): receives that intermediate, Y [B][Ci][P] or H [B][Co][P].  The backward needs Y (Ci <= Co) always and H
+ *   (Ci > Co) only for the adjacency gradient.
+ * grid_cap: upper bound of the persistent grid, 0 = the kernels' default.
+ * Backward: G = dO * (O > 0) formed on load; dW [Ci][Co] and db [Co] (NULL: no bias) (+)= (accumulate) fixed-order fp64 sums of one
+ *   partial row per workgroup in ws (coskad_plain_gcn_ws_bytes) -- bitwise reproducible; dX [B][Ci][P] iff need_dx; need_da: D
+ *   receives the narrow-side gradient, dY [B][Ci][P] (Ci <= Co; then dA'[q][p] = sum_rows D[r][q] X[r][p]) or G [B][Co][P]
+ *   (Ci > Co; dA'[q][p] = sum_rows G[r][q] H[r][p]) for a coskad_gemm_f32 reduction.  S: the saved Y (Ci <= Co; otherwise unused,
+ *   may be NULL); X is read only when Ci > Co.  X, S, O, dO, D, A' 16-byte aligned. */
+int coskad_plain_gcn_ok(int Ci, int Co, int P);
+size_t coskad_plain_gcn_ws_bytes(int B, int Ci, int Co, int P, int grid_cap);
+int coskad_plain_gcn_fwd_f32(const float* X, const float* W, const float* Ap, const float* bias, float* O, float* save, int B,
+                             int Ci, int Co, int P, int grid_cap, hipStream_t stream);
+int coskad_plain_gcn_bwd_f32(const float* X, const float* S, const float* O, const float* dO, const float* W, const float* Ap,
+                             float* dX, float* dW, float* db, float* D, void* ws, size_t ws_bytes, int B, int Ci, int Co, int P,
+                             int need_dx, int need_da, int accumulate, int grid_cap, hipStream_t stream);
+
 /* ---- 1x1 convolution in NCHW for wide layers (nn.Conv2d(C_in, C_out, 1) of stsgcn.py:57-63,71-75; csrc/conv1x1.hip) -----------
  * Out[b][m][p] (+)= sum_k A(m,k) In[b][k][p] (+ bias[m]) with In [batch][K][P], Out [batch][M][P] contiguous; A(m,k) = A[m sa_m + k sa_k],
  * sa_k == 1 (forward: W [M][K]) or sa_m == 1 (data gradient: W^T of W [K][M]).  Layout-specialised MFMA kernel (float4 loads, K tiles
