@@ -1,7 +1,9 @@
 """Thin, checked wrappers: torch CUDA tensors -> C-ABI calls (include/coskad_hip.h).
 
 Every wrapper validates device / dtype / contiguity / shape on the host before a kernel
-sees a pointer, enqueues on torch's current stream and never synchronises.
+sees a pointer, enqueues on torch's current stream and never synchronises.  Arguments go to
+the library as plain values (tensors, None, Python numbers): _lib binds every entry point to
+its prototype in the header, which converts them and rejects a wrong count or type.
 """
 from __future__ import annotations
 
@@ -11,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import call, i32, ptr
+from ._lib import call
 
 Tensor = torch.Tensor
 
@@ -60,8 +62,7 @@ def gcn(x: Tensor, A: Tensor, Tm: Tensor, adjoint: bool = False) -> Tensor:
     N, C, T, V = x.shape
     _chk(x, "x"); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T))
     out = torch.empty_like(x)
-    call("coskad_gcn_f32", ptr(x), ptr(out), ptr(A), ptr(Tm), i32(N * C), i32(T), i32(V),
-         i32(1 if adjoint else 0), _stream())
+    call("coskad_gcn_f32", x, out, A, Tm, N * C, T, V, 1 if adjoint else 0, _stream())
     return out
 
 
@@ -74,9 +75,7 @@ def bn_fold(Wt, bt, gt, bet, mean_t, var_t, Wr, br, gr, ber, mean_r, var_r):
         _chk(t, n, optional=True)
     wfold = torch.empty(2 * Ci, cop(Co), device=Wt.device, dtype=torch.float32)
     bias = torch.empty(cop(Co), device=Wt.device, dtype=torch.float32)
-    call("coskad_bn_fold_f32", ptr(Wt), ptr(bt), ptr(gt), ptr(bet), ptr(mean_t), ptr(var_t),
-         ptr(Wr), ptr(br), ptr(gr), ptr(ber), ptr(mean_r), ptr(var_r), ptr(wfold), ptr(bias),
-         i32(Ci), i32(Co), _stream())
+    call("coskad_bn_fold_f32", Wt, bt, gt, bet, mean_t, var_t, Wr, br, gr, ber, mean_r, var_r, wfold, bias, Ci, Co, _stream())
     return wfold, bias
 
 
@@ -92,14 +91,13 @@ def layer_apply(x: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, bias: Tensor, C
         out = torch.empty(B, Co, T, V, device=x.device, dtype=torch.float32)
     else:
         _chk(out, "out", (B, Co, T, V))
-    call("coskad_layer_apply_f32", ptr(x), ptr(out), ptr(A), ptr(Tm), ptr(wfold), ptr(bias),
-         ptr(in_slope), ptr(out_slope), i32(B), i32(Ci), i32(Co), i32(T), i32(V), _stream(), tag=(Ci, Co))
+    call("coskad_layer_apply_f32", x, out, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V, _stream(), tag=(Ci, Co))
     return out
 
 
 def layer_first_pair_ok(Ci: int, Cm: int, Co: int, T: int, V: int) -> bool:
     """the first layer (2 -> Cm) and the layer behind it (Cm -> Co), folded, in one pass (csrc/eval_layer_bpc.hip, FIRST form)"""
-    return bool(_lib.lib().coskad_layer_first_pair_ok(i32(T), i32(V), i32(Ci), i32(Cm), i32(Co)))
+    return bool(_lib.lib().coskad_layer_first_pair_ok(T, V, Ci, Cm, Co))
 
 
 def layer_first_pair_apply(x: Tensor, A1: Tensor, T1: Tensor, wfold1: Tensor, bias1: Tensor, A2: Tensor, T2: Tensor, wfold2: Tensor,
@@ -111,28 +109,22 @@ def layer_first_pair_apply(x: Tensor, A1: Tensor, T1: Tensor, wfold1: Tensor, bi
     _chk(wfold1, "wfold1", (4, Cm)); _chk(bias1, "bias1", (Cm,)); _chk(wfold2, "wfold2", (2 * Cm, Co)); _chk(bias2, "bias2", (Co,))
     _chk(mid_slope, "mid_slope", (1,)); _chk(out_slope, "out_slope", (1,), optional=True)
     out = torch.empty(B, Co, T, V, device=x.device, dtype=torch.float32)
-    call("coskad_layer_first_pair_apply_f32", ptr(x), ptr(out), ptr(A1), ptr(T1), ptr(wfold1), ptr(bias1), ptr(A2), ptr(T2), ptr(wfold2),
-         ptr(bias2), ptr(mid_slope), ptr(out_slope), i32(B), i32(Cm), i32(Co), i32(T), i32(V), _stream())
+    call("coskad_layer_first_pair_apply_f32", x, out, A1, T1, wfold1, bias1, A2, T2, wfold2, bias2, mid_slope, out_slope, B, Cm, Co, T, V,
+         _stream())
     return out
 
 
 def layer_fits(Ci: int, Co: int, T: int, V: int) -> bool:
     """Do the LDS-resident tile kernels take a (Ci -> Co) layer at this geometry?  (pure host arithmetic)"""
-    fn = _lib.lib().coskad_layer_fits
-    fn.restype = ctypes.c_int
-    return bool(fn(i32(Ci), i32(Co), i32(T), i32(V)))
+    return bool(_lib.lib().coskad_layer_fits(Ci, Co, T, V))
 
 
 def stat_floats(Ci: int, Co: int) -> int:
-    fn = _lib.lib().coskad_stat_floats
-    fn.restype = ctypes.c_int
-    return fn(i32(Ci), i32(Co))
+    return _lib.lib().coskad_stat_floats(Ci, Co)
 
 
 def train_stats_ws_bytes(Ci: int) -> int:
-    fn = _lib.lib().coskad_train_stats_ws_bytes
-    fn.restype = ctypes.c_size_t
-    return fn(i32(Ci))
+    return _lib.lib().coskad_train_stats_ws_bytes(Ci)
 
 
 def layer_train_stats(x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t,
@@ -157,14 +149,12 @@ def layer_train_stats(x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t,
     bias = torch.empty(cop(Co), device=x.device, dtype=torch.float32)
     stat = torch.empty(stat_floats(Ci, Co), device=x.device, dtype=torch.float32)
     _chk(Z, "Z", tuple(x.shape), optional=True)
-    args = (ptr(x), ptr(A), ptr(Tm), ptr(in_slope), ptr(Wt), ptr(bt), ptr(gt),
-            ptr(bet), ptr(rm_t), ptr(rv_t), ptr(nbt_t), ptr(Wr), ptr(br), ptr(gr), ptr(ber), ptr(rm_r),
-            ptr(rv_r), ptr(nbt_r), ctypes.c_float(momentum), ptr(wfold), ptr(bias), ptr(stat), ptr(ws),
-            ctypes.c_size_t(ws.numel() * ws.element_size()), i32(B), i32(Ci), i32(Co), i32(T), i32(V), _stream())
+    args = (x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r, nbt_r, momentum, wfold, bias, stat, ws,
+            ws.numel() * ws.element_size(), B, Ci, Co, T, V, _stream())
     if Z is None:
         call("coskad_layer_train_stats_f32", *args)
     else:
-        call("coskad_layer_train_stats_z_f32", *args, ptr(Z))
+        call("coskad_layer_train_stats_z_f32", *args, Z)
     return wfold, bias, stat
 
 
@@ -178,8 +168,7 @@ def layer_train_moments(x, A, Tm, in_slope, ws, Z: Optional[Tensor] = None) -> T
     if ws is None or _bytes(ws) < need:
         raise ValueError(f"workspace too small: need {need} bytes")
     sums = torch.empty(2 * (Ci * Ci + Ci), device=x.device, dtype=torch.float64)
-    call("coskad_layer_train_moments_f32", ptr(x), ptr(A), ptr(Tm), ptr(in_slope), ptr(Z), ptr(sums), ptr(ws),
-         ctypes.c_size_t(_bytes(ws)), i32(B), i32(Ci), i32(T), i32(V), _stream())
+    call("coskad_layer_train_moments_f32", x, A, Tm, in_slope, Z, sums, ws, _bytes(ws), B, Ci, T, V, _stream())
     return sums
 
 
@@ -189,7 +178,7 @@ def layer_moment_sums(partials: Tensor, rows: int, Ci: int) -> Tensor:
     if partials.numel() < rows * 2 * (Ci * Ci + Ci):
         raise ValueError("layer_moment_sums: partials smaller than rows x 2 (Ci^2 + Ci)")
     sums = torch.empty(2 * (Ci * Ci + Ci), device=partials.device, dtype=torch.float64)
-    call("coskad_layer_moment_sums_f32", ptr(partials), i32(rows), i32(Ci), ptr(sums), _stream())
+    call("coskad_layer_moment_sums_f32", partials, rows, Ci, sums, _stream())
     return sums
 
 
@@ -204,9 +193,8 @@ def layer_train_fold_sums(sums, count, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, b
     wfold = torch.empty(2 * Ci, cop(Co), device=Wt.device, dtype=torch.float32)
     bias = torch.empty(cop(Co), device=Wt.device, dtype=torch.float32)
     stat = torch.empty(stat_floats(Ci, Co), device=Wt.device, dtype=torch.float32)
-    call("coskad_layer_train_fold_sums_f32", ptr(sums), ctypes.c_double(float(count)), ptr(Wt), ptr(bt), ptr(gt), ptr(bet), ptr(rm_t),
-         ptr(rv_t), ptr(nbt_t), ptr(Wr), ptr(br), ptr(gr), ptr(ber), ptr(rm_r), ptr(rv_r), ptr(nbt_r), ctypes.c_float(momentum),
-         ptr(wfold), ptr(bias), ptr(stat), i32(Ci), i32(Co), _stream())
+    call("coskad_layer_train_fold_sums_f32", sums, float(count), Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r, nbt_r,
+         momentum, wfold, bias, stat, Ci, Co, _stream())
     return wfold, bias, stat
 
 
@@ -219,21 +207,16 @@ def layer_bwd_stats(x_in, dU, A, Tm, in_slope, has_residual: bool, ws, Z=None):
     need = layer_bwd_ws_bytes(B, Ci, Co, T, V)
     if ws is None or _bytes(ws) < need:
         raise ValueError(f"workspace too small: need {need} bytes")
-    fn = _lib.lib().coskad_layer_bwd_stats_floats
-    fn.restype = ctypes.c_size_t
-    buf = torch.empty(fn(i32(B), i32(Ci), i32(Co), i32(T), i32(V)), device=x_in.device, dtype=torch.float32)
+    buf = torch.empty(_lib.lib().coskad_layer_bwd_stats_floats(B, Ci, Co, T, V), device=x_in.device, dtype=torch.float32)
     rows = ctypes.c_int(0)
-    call("coskad_layer_bwd_stats_f32", ptr(x_in), ptr(dU), ptr(A), ptr(Tm), ptr(in_slope), i32(1 if has_residual else 0), ptr(buf),
-         ctypes.c_size_t(_bytes(buf)), ctypes.byref(rows), ptr(ws), ctypes.c_size_t(_bytes(ws)), i32(B), i32(Ci), i32(Co), i32(T), i32(V),
-         _stream(), ptr(Z))
+    call("coskad_layer_bwd_stats_f32", x_in, dU, A, Tm, in_slope, 1 if has_residual else 0, buf, _bytes(buf), ctypes.byref(rows), ws,
+         _bytes(ws), B, Ci, Co, T, V, _stream(), Z)
     return buf, rows.value
 
 
 def chain_sums(buf: Tensor, rows: int, Ci: int, Co: int) -> Tensor:
     """The fp64 sums [P Co*Ci][Q Co*Ci][sdU Co] inside a backward chain buffer, as a view (all-reduce it in place for SyncBN)."""
-    fn = _lib.lib().coskad_layer_bwd_sums_offset
-    fn.restype = ctypes.c_size_t
-    off = fn(i32(rows), i32(Ci), i32(Co))
+    off = _lib.lib().coskad_layer_bwd_sums_offset(rows, Ci, Co)
     E = 2 * Co * Ci + Co
     return buf[off:off + 2 * E].view(torch.float64)
 
@@ -246,29 +229,22 @@ def layer_apply_z(Z, x, A, Tm, wfold, bias, Co, in_slope=None, out_slope=None, o
     if out is None:
         out = torch.empty(B, Co, T, V, device=x.device, dtype=torch.float32)
     _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T))
-    call("coskad_layer_apply_z_f32", ptr(Z), ptr(x), ptr(out), ptr(A), ptr(Tm), ptr(wfold), ptr(bias), ptr(in_slope), ptr(out_slope),
-         i32(B), i32(Ci), i32(Co), i32(T), i32(V), _stream())
+    call("coskad_layer_apply_z_f32", Z, x, out, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V, _stream())
     return out
 
 
 def layer_apply_next_ok(Ci: int, Co: int, T: int, V: int) -> bool:
     """Does csrc/fused_apply_next.hip take a (Ci -> Co) layer (apply + the next layer's statistics in one kernel)?"""
-    fn = _lib.lib().coskad_layer_apply_next_ok
-    fn.restype = ctypes.c_int
-    return bool(fn(i32(Ci), i32(Co), i32(T), i32(V)))
+    return bool(_lib.lib().coskad_layer_apply_next_ok(Ci, Co, T, V))
 
 
 def layer_apply_next_rows(B: int, Ci: int, Co: int) -> int:
     """Partial rows layer_apply_next writes for a batch of B clips (each 2 (Co^2 + Co) floats)."""
-    fn = _lib.lib().coskad_layer_apply_next_rows
-    fn.restype = ctypes.c_int
-    return fn(i32(B), i32(Ci), i32(Co))
+    return _lib.lib().coskad_layer_apply_next_rows(B, Ci, Co)
 
 
 def ftab_floats() -> int:
-    fn = _lib.lib().coskad_ftab_floats
-    fn.restype = ctypes.c_int
-    return fn()
+    return _lib.lib().coskad_ftab_floats()
 
 
 def build_ftabs(As, Ts, tabs) -> None:
@@ -282,7 +258,7 @@ def build_ftabs(As, Ts, tabs) -> None:
         _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T)); _chk(tab, "tab", (nf,))
     arr = ctypes.c_void_p * n
     call("coskad_build_ftab_f32", arr(*[t.data_ptr() for t in As]), arr(*[t.data_ptr() for t in Ts]),
-         arr(*[t.data_ptr() for t in tabs]), i32(n), i32(T), i32(V), _stream())
+         arr(*[t.data_ptr() for t in tabs]), n, T, V, _stream())
 
 
 def layer_apply_next(Z, x, wfold, bias, Co, in_slope, out_slope, ftab_next, partials, T, V, out=None, Z_next=None):
@@ -298,15 +274,14 @@ def layer_apply_next(Z, x, wfold, bias, Co, in_slope, out_slope, ftab_next, part
         Z_next = torch.empty(B, Co, T, V, device=x.device, dtype=torch.float32)
     _chk(out, "out", (B, Co, T, V)); _chk(Z_next, "Z_next", (B, Co, T, V))
     rows = layer_apply_next_rows(B, Ci, Co)
-    call("coskad_layer_apply_next_f32", ptr(Z), ptr(x), ptr(out), ptr(wfold), ptr(bias), ptr(in_slope), ptr(out_slope),
-         ptr(ftab_next), ptr(Z_next), ptr(partials), ctypes.c_size_t(_bytes(partials)), i32(B), i32(Ci), i32(Co), i32(T), i32(V),
-         _stream(), tag=(Ci, Co))
+    call("coskad_layer_apply_next_f32", Z, x, out, wfold, bias, in_slope, out_slope, ftab_next, Z_next, partials, _bytes(partials), B, Ci,
+         Co, T, V, _stream(), tag=(Ci, Co))
     return out, Z_next, rows
 
 
 def layer_apply_next_flat_ok(Ci: int, Co: int, T: int, V: int) -> bool:
     """apply + the next layer's statistics in one kernel on the 25-joint layout (csrc/fused_apply_flat.hip, NX form)"""
-    return bool(_lib.lib().coskad_layer_apply_next_flat_ok(i32(Ci), i32(Co), i32(T), i32(V)))
+    return bool(_lib.lib().coskad_layer_apply_next_flat_ok(Ci, Co, T, V))
 
 
 def layer_apply_next_flat(Z, x, wfold, bias, Co, in_slope, out_slope, A_next, T_next):
@@ -316,13 +291,12 @@ def layer_apply_next_flat(Z, x, wfold, bias, Co, in_slope, out_slope, A_next, T_
     _chk(x, "x"); _chk(Z, "Z", (B, Ci, T, V)); _chk(wfold, "wfold", (2 * Ci, cop(Co))); _chk(bias, "bias", (cop(Co),))
     _chk(in_slope, "in_slope", (1,), optional=True); _chk(out_slope, "out_slope", (1,))
     _chk(A_next, "A_next", (T, V, V)); _chk(T_next, "T_next", (V, T, T))
-    rows = int(_lib.lib().coskad_layer_apply_next_flat_rows(i32(B)))
+    rows = int(_lib.lib().coskad_layer_apply_next_flat_rows(B))
     out = torch.empty(B, Co, T, V, device=x.device, dtype=torch.float32)
     Zn = torch.empty(B, Co, T, V, device=x.device, dtype=torch.float32)
     partials = torch.empty(rows * 2 * (Co * Co + Co), device=x.device, dtype=torch.float32)
-    call("coskad_layer_apply_next_flat_f32", ptr(Z), ptr(x), ptr(out), ptr(wfold), ptr(bias), ptr(in_slope), ptr(out_slope), ptr(A_next),
-         ptr(T_next), ptr(Zn), ptr(partials), ctypes.c_size_t(_bytes(partials)), i32(B), i32(Ci), i32(Co), i32(T), i32(V), _stream(),
-         tag=(Ci, Co))
+    call("coskad_layer_apply_next_flat_f32", Z, x, out, wfold, bias, in_slope, out_slope, A_next, T_next, Zn, partials, _bytes(partials), B,
+         Ci, Co, T, V, _stream(), tag=(Ci, Co))
     return out, Zn, partials, rows
 
 
@@ -345,10 +319,8 @@ def layer_train_fold(partials, rows, B, T, V, Wt, bt, gt, bet, rm_t, rv_t, nbt_t
     wfold = torch.empty(2 * Ci, cop(Co), device=Wt.device, dtype=torch.float32)
     bias = torch.empty(cop(Co), device=Wt.device, dtype=torch.float32)
     stat = torch.empty(stat_floats(Ci, Co), device=Wt.device, dtype=torch.float32)
-    call("coskad_layer_train_fold_f32", ptr(partials), i32(rows), ptr(Wt), ptr(bt), ptr(gt), ptr(bet), ptr(rm_t), ptr(rv_t),
-         ptr(nbt_t), ptr(Wr), ptr(br), ptr(gr), ptr(ber), ptr(rm_r), ptr(rv_r), ptr(nbt_r), ctypes.c_float(momentum),
-         ptr(wfold), ptr(bias), ptr(stat), ptr(ws), ctypes.c_size_t(_bytes(ws)), i32(B), i32(Ci), i32(Co), i32(T), i32(V),
-         _stream())
+    call("coskad_layer_train_fold_f32", partials, rows, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r, nbt_r, momentum,
+         wfold, bias, stat, ws, _bytes(ws), B, Ci, Co, T, V, _stream())
     return wfold, bias, stat
 
 
@@ -356,14 +328,12 @@ def gather(src: Tensor, idx: Tensor) -> Tensor:
     """out[i] = src[idx[i]] (0 where idx < 0): operand streams of the fused encoder from the concatenated parameters."""
     _chk(src, "src"); _chk(idx, "idx", dtype=torch.int32)
     out = torch.empty(idx.shape, device=src.device, dtype=torch.float32)
-    call("coskad_gather_f32", ptr(src), ptr(idx), ptr(out), ctypes.c_size_t(idx.numel()), _stream())
+    call("coskad_gather_f32", src, idx, out, idx.numel(), _stream())
     return out
 
 
 def fused_encoder_out_floats() -> int:
-    fn = _lib.lib().coskad_fused_encoder_out_floats
-    fn.restype = ctypes.c_int
-    return fn()
+    return _lib.lib().coskad_fused_encoder_out_floats()
 
 
 def fused_encoder(x: Tensor, tab: Tensor, wreg: Tensor, slopes: Tensor, out: Optional[Tensor] = None) -> Tensor:
@@ -378,28 +348,22 @@ def fused_encoder(x: Tensor, tab: Tensor, wreg: Tensor, slopes: Tensor, out: Opt
         out = torch.empty(B, kp, device=x.device, dtype=torch.float32)
     else:
         _chk(out, "out", (B, kp))
-    call("coskad_fused_encoder_f32", ptr(x), ptr(out), ptr(tab), ptr(wreg), ptr(slopes), i32(B), i32(T), i32(V), _stream())
+    call("coskad_fused_encoder_f32", x, out, tab, wreg, slopes, B, T, V, _stream())
     return out
 
 
 def layer_bwd_ws_bytes(B, Ci, Co, T, V) -> int:
-    fn = _lib.lib().coskad_layer_bwd_ws_bytes
-    fn.restype = ctypes.c_size_t
-    return fn(i32(B), i32(Ci), i32(Co), i32(T), i32(V))
+    return _lib.lib().coskad_layer_bwd_ws_bytes(B, Ci, Co, T, V)
 
 
 def layer_bwd_below_rows(B: int, Ci: int, Co: int, below_Ci: int, T: int, V: int) -> int:
     """Partial rows the (Ci -> Co) backward data kernel writes for the layer below it (0: that kernel cannot form them)."""
-    fn = _lib.lib().coskad_layer_bwd_below_rows
-    fn.restype = ctypes.c_int
-    return fn(i32(B), i32(Ci), i32(Co), i32(below_Ci), i32(T), i32(V))
+    return _lib.lib().coskad_layer_bwd_below_rows(B, Ci, Co, below_Ci, T, V)
 
 
 def layer_bwd_below_floats(B: int, Ci: int, Co: int, below_Ci: int, T: int, V: int) -> int:
     """Floats of the chain buffer (partial rows + their fp64 sums) layer_bwd(..., below=...) fills for the layer below."""
-    fn = _lib.lib().coskad_layer_bwd_below_floats
-    fn.restype = ctypes.c_size_t
-    return fn(i32(B), i32(Ci), i32(Co), i32(below_Ci), i32(T), i32(V))
+    return _lib.lib().coskad_layer_bwd_below_floats(B, Ci, Co, below_Ci, T, V)
 
 
 def layer_bwd(x_in, dU, A, Tm, in_slope, stat, Wt, gt, Wr, gr, grads: dict, ws, need_dx=True,
@@ -425,11 +389,9 @@ def layer_bwd(x_in, dU, A, Tm, in_slope, stat, Wt, gt, Wr, gr, grads: dict, ws, 
     if need_dx and dIn is None:
         dIn = torch.empty_like(x_in)
     _chk(Z, "Z", (B, Ci, T, V), optional=True)
-    args = (ptr(x_in), ptr(dU), ptr(A), ptr(Tm), ptr(in_slope), ptr(stat), ptr(Wt), ptr(gt),
-            ptr(Wr), ptr(gr), ptr(dIn if need_dx else None), ptr(grads["A"]), ptr(grads["T"]), ptr(grads["Wt"]),
-            ptr(grads.get("bt")), ptr(grads["gt"]), ptr(grads["bet"]), ptr(grads.get("Wr")), ptr(grads.get("br")),
-            ptr(grads.get("gr")), ptr(grads.get("ber")), ptr(grads.get("slope_in")), ptr(ws),
-            ctypes.c_size_t(_bytes(ws)), i32(1 if accumulate else 0), i32(B), i32(Ci), i32(Co), i32(T), i32(V), _stream())
+    args = (x_in, dU, A, Tm, in_slope, stat, Wt, gt, Wr, gr, dIn if need_dx else None, grads["A"], grads["T"], grads["Wt"],
+            grads.get("bt"), grads["gt"], grads["bet"], grads.get("Wr"), grads.get("br"), grads.get("gr"), grads.get("ber"),
+            grads.get("slope_in"), ws, _bytes(ws), 1 if accumulate else 0, B, Ci, Co, T, V, _stream())
     if stats_in is not None or below is not None:
         if Z is None:
             raise ValueError("layer_bwd: chain mode needs the stored Z")
@@ -441,13 +403,12 @@ def layer_bwd(x_in, dU, A, Tm, in_slope, stat, Wt, gt, Wr, gr, grads: dict, ws, 
         cb = xb.shape[1] if xb is not None else 0
         _chk(xb, "below x", (B, cb, T, V), optional=True); _chk(zb, "below Z", (B, cb, T, V), optional=True); _chk(bs, "below_stats", optional=True)
         _chk(sb, "below in_slope", (1,), optional=True)
-        call("coskad_layer_bwd_chain_f32", *args, ptr(Z), ptr(sp), i32(srows), ctypes.c_size_t(_bytes(sp) if sp is not None else 0),
-             ptr(xb), ptr(zb), ptr(sb), i32(cb), ptr(bs),
-             ctypes.c_size_t(_bytes(bs) if bs is not None else 0), ctypes.c_double(float(stats_count)))
+        call("coskad_layer_bwd_chain_f32", *args, Z, sp, srows, _bytes(sp) if sp is not None else 0, xb, zb, sb, cb, bs,
+             _bytes(bs) if bs is not None else 0, float(stats_count))
     elif Z is None:
         call("coskad_layer_bwd_f32", *args)
     else:       # stored gcn(PReLU(x_in)) from layer_train_stats(..., Z=...): no mixing recompute in the backward kernels
-        call("coskad_layer_bwd_z_f32", *args, ptr(Z))
+        call("coskad_layer_bwd_z_f32", *args, Z)
     return dIn if need_dx else None
 
 
@@ -470,18 +431,14 @@ def layer_bwd_data(x_in, dU, A, Tm, in_slope, stat, Wt, gt, Wr, gr, grads: dict,
         raise ValueError(f"workspace too small: need {need} bytes")
     if need_dx and dIn is None:
         dIn = torch.empty_like(x_in)
-    call("coskad_layer_bwd_data_f32", ptr(x_in), ptr(dU), ptr(A), ptr(Tm), ptr(in_slope), ptr(stat), ptr(Wt), ptr(gt),
-         ptr(Wr), ptr(gr), ptr(dIn if need_dx else None), ptr(dZ), ptr(grads["Wt"]), ptr(grads.get("bt")),
-         ptr(grads["gt"]), ptr(grads["bet"]), ptr(grads.get("Wr")), ptr(grads.get("br")), ptr(grads.get("gr")),
-         ptr(grads.get("ber")), ptr(grads.get("slope_in")), ptr(ws), ctypes.c_size_t(_bytes(ws)),
-         i32(1 if accumulate else 0), i32(B), i32(Ci), i32(Co), i32(T), i32(V), _stream(), ptr(Z))
+    call("coskad_layer_bwd_data_f32", x_in, dU, A, Tm, in_slope, stat, Wt, gt, Wr, gr, dIn if need_dx else None, dZ, grads["Wt"],
+         grads.get("bt"), grads["gt"], grads["bet"], grads.get("Wr"), grads.get("br"), grads.get("gr"), grads.get("ber"),
+         grads.get("slope_in"), ws, _bytes(ws), 1 if accumulate else 0, B, Ci, Co, T, V, _stream(), Z)
     return dIn if need_dx else None
 
 
 def layer_gcn_params_ws_bytes(T, V) -> int:
-    fn = _lib.lib().coskad_layer_gcn_params_ws_bytes
-    fn.restype = ctypes.c_size_t
-    return fn(i32(T), i32(V))
+    return _lib.lib().coskad_layer_gcn_params_ws_bytes(T, V)
 
 
 def layer_gcn_params(x_in, in_slope, dZ, A, Tm, dA, dT, ws, accumulate=False):
@@ -491,8 +448,7 @@ def layer_gcn_params(x_in, in_slope, dZ, A, Tm, dA, dT, ws, accumulate=False):
     _chk(dA, "dA", (T, V, V)); _chk(dT, "dT", (V, T, T)); _chk(in_slope, "in_slope", (1,), optional=True)
     if ws is None or _bytes(ws) < layer_gcn_params_ws_bytes(T, V):
         raise ValueError("workspace too small")
-    call("coskad_layer_gcn_params_f32", ptr(x_in), ptr(in_slope), ptr(dZ), ptr(A), ptr(Tm), ptr(dA), ptr(dT), ptr(ws),
-         ctypes.c_size_t(_bytes(ws)), i32(1 if accumulate else 0), i32(B), i32(Ci), i32(T), i32(V), _stream())
+    call("coskad_layer_gcn_params_f32", x_in, in_slope, dZ, A, Tm, dA, dT, ws, _bytes(ws), 1 if accumulate else 0, B, Ci, T, V, _stream())
 
 
 def btlnk_fwd(U: Tensor, W: Tensor, bias: Optional[Tensor], slope: Optional[Tensor], ws=None) -> Tensor:
@@ -505,23 +461,17 @@ def btlnk_fwd(U: Tensor, W: Tensor, bias: Optional[Tensor], slope: Optional[Tens
     z = torch.empty(B, L, device=U.device, dtype=torch.float32)
     if L > 16:
         # 16 < L <= 512: the LDS-tiled MFMA GEMM of csrc/btlnk_wide.hip, K slices summed in a fixed order (any K)
-        fn = _lib.lib().coskad_btlnk_fwd_ws_bytes_l
-        fn.restype = ctypes.c_size_t
-        nbytes = fn(i32(B), i32(K), i32(L))
+        nbytes = _lib.lib().coskad_btlnk_fwd_ws_bytes_l(B, K, L)
         buf = ws.get(nbytes, U.device) if ws is not None else torch.empty(nbytes, dtype=torch.uint8, device=U.device)
-        call("coskad_btlnk_fwd_ws_f32", ptr(U), ptr(W), ptr(bias), ptr(slope), ptr(z), ptr(buf), ctypes.c_size_t(nbytes),
-             i32(B), i32(K), i32(L), _stream())
+        call("coskad_btlnk_fwd_ws_f32", U, W, bias, slope, z, buf, nbytes, B, K, L, _stream())
         return z
     if B >= BTLNK_SPLITK_MIN_B and K % 16 == 0:
         # blocks of 64 clips x 4 K slices (W operands shared by four clip tiles), fixed-order partial sums
-        fn = _lib.lib().coskad_btlnk_fwd_ws_bytes
-        fn.restype = ctypes.c_size_t
-        nbytes = fn(i32(B))
+        nbytes = _lib.lib().coskad_btlnk_fwd_ws_bytes(B)
         buf = ws.get(nbytes, U.device) if ws is not None else torch.empty(nbytes, dtype=torch.uint8, device=U.device)
-        call("coskad_btlnk_fwd_ws_f32", ptr(U), ptr(W), ptr(bias), ptr(slope), ptr(z), ptr(buf), ctypes.c_size_t(nbytes),
-             i32(B), i32(K), i32(L), _stream())
+        call("coskad_btlnk_fwd_ws_f32", U, W, bias, slope, z, buf, nbytes, B, K, L, _stream())
         return z
-    call("coskad_btlnk_fwd_f32", ptr(U), ptr(W), ptr(bias), ptr(slope), ptr(z), i32(B), i32(K), i32(L), _stream())
+    call("coskad_btlnk_fwd_f32", U, W, bias, slope, z, B, K, L, _stream())
     return z
 
 
@@ -530,9 +480,7 @@ BTLNK_LMAX = 512            # widest latent of the bottleneck and head kernels (
 
 
 def btlnk_bwd_ws_bytes(B, K, L) -> int:
-    fn = _lib.lib().coskad_btlnk_bwd_ws_bytes
-    fn.restype = ctypes.c_size_t
-    return fn(i32(B), i32(K), i32(L))
+    return _lib.lib().coskad_btlnk_bwd_ws_bytes(B, K, L)
 
 
 def btlnk_bwd(U, W, dz, slope, dW, db, dslope, ws, dU=None, accumulate=False):
@@ -546,16 +494,13 @@ def btlnk_bwd(U, W, dz, slope, dW, db, dslope, ws, dU=None, accumulate=False):
         raise ValueError(f"workspace too small: need {need} bytes")
     if dU is None:
         dU = torch.empty_like(U)
-    call("coskad_btlnk_bwd_f32", ptr(U), ptr(W), ptr(dz), ptr(slope), ptr(dU), ptr(dW), ptr(db), ptr(dslope), ptr(ws),
-         ctypes.c_size_t(_bytes(ws)), i32(1 if accumulate else 0), i32(B), i32(K), i32(L), _stream())
+    call("coskad_btlnk_bwd_f32", U, W, dz, slope, dU, dW, db, dslope, ws, _bytes(ws), 1 if accumulate else 0, B, K, L, _stream())
     return dU
 
 
 def btlnk_bwd_chain_ok(K: int, TV: int, below_Ci: int) -> bool:
     """coskad_btlnk_bwd_chain_f32 takes the shape: a 64-channel last layer over 16 / 32 input channels."""
-    fn = _lib.lib().coskad_btlnk_bwd_chain_ok
-    fn.restype = ctypes.c_int
-    return bool(fn(i32(K), i32(TV), i32(below_Ci)))
+    return bool(_lib.lib().coskad_btlnk_bwd_chain_ok(K, TV, below_Ci))
 
 
 def btlnk_bwd_chain(U, W, dz, slope, dW, db, dslope, ws, below_in, below_Z, below_in_slope, dU=None, accumulate=False):
@@ -574,17 +519,14 @@ def btlnk_bwd_chain(U, W, dz, slope, dW, db, dslope, ws, below_in, below_Z, belo
     if not btlnk_bwd_chain_ok(K, TV, Ci):
         raise ValueError(f"btlnk_bwd_chain: shape K={K} TV={TV} Ci={Ci} not supported")
     lib = _lib.lib()
-    lib.coskad_btlnk_bwd_chain_ws_bytes.restype = ctypes.c_size_t
-    lib.coskad_btlnk_bwd_chain_floats.restype = ctypes.c_size_t
-    need = lib.coskad_btlnk_bwd_chain_ws_bytes(i32(B), i32(K), i32(L), i32(TV))
+    need = lib.coskad_btlnk_bwd_chain_ws_bytes(B, K, L, TV)
     buf = ws.get(need, U.device)
-    stats = torch.empty(lib.coskad_btlnk_bwd_chain_floats(i32(B), i32(TV), i32(Ci)), device=U.device, dtype=torch.float32)
+    stats = torch.empty(lib.coskad_btlnk_bwd_chain_floats(B, TV, Ci), device=U.device, dtype=torch.float32)
     if dU is None:
         dU = torch.empty_like(U)
     rows = ctypes.c_int(0)
-    call("coskad_btlnk_bwd_chain_f32", ptr(U), ptr(W), ptr(dz), ptr(slope), ptr(dU), ptr(dW), ptr(db), ptr(dslope), ptr(buf),
-         ctypes.c_size_t(_bytes(buf)), i32(1 if accumulate else 0), i32(B), i32(K), i32(L), ptr(below_in), ptr(below_Z),
-         ptr(below_in_slope), i32(Ci), i32(TV), ptr(stats), ctypes.c_size_t(_bytes(stats)), ctypes.byref(rows), _stream())
+    call("coskad_btlnk_bwd_chain_f32", U, W, dz, slope, dU, dW, db, dslope, buf, _bytes(buf), 1 if accumulate else 0, B, K, L, below_in,
+         below_Z, below_in_slope, Ci, TV, stats, _bytes(stats), ctypes.byref(rows), _stream())
     return dU, (stats, rows.value)
 
 
@@ -627,10 +569,8 @@ def gemm(A: Tensor, B: Tensor, out: Optional[Tensor] = None, bias: Optional[Tens
     if (Mc, Nc) != (M, N) or bc != batch:
         raise ValueError(f"gemm: out has shape {tuple(out.shape)}, expected batch {batch} x {M} x {N}")
     _chk(bias, "bias", optional=True)
-    ll = ctypes.c_longlong
-    call("coskad_gemm_f32", ptr(A), ptr(B), ptr(out), ptr(bias), ll(sab), ll(sam), ll(sak), ll(sbb), ll(sbk), ll(sbn),
-         ll(scb), ll(scm), ll(scn), i32(M), i32(N), i32(K), i32(batch), i32(bias_mode), i32(bias_mod), i32(1 if relu else 0),
-         i32(0), i32(0), ll(0), i32(1 if accumulate else 0), _stream())
+    call("coskad_gemm_f32", A, B, out, bias, sab, sam, sak, sbb, sbk, sbn, scb, scm, scn, M, N, K, batch, bias_mode, bias_mod,
+         1 if relu else 0, 0, 0, 0, 1 if accumulate else 0, _stream())
     return out
 
 
@@ -645,10 +585,8 @@ def gemm_reduce(A: Tensor, B: Tensor, out: Tensor, target_chunks: int = 64, ktot
     chunk = max(1, (ba + target_chunks - 1) // target_chunks)
     chunks = (ba + chunk - 1) // chunk
     part = torch.empty(chunks, M, N, device=A.device, dtype=torch.float32)
-    ll = ctypes.c_longlong
-    call("coskad_gemm_f32", ptr(A), ptr(B), ptr(part), ptr(None), ll(sab), ll(sam), ll(sak), ll(sbb), ll(sbk), ll(sbn),
-         ll(0), ll(0), ll(0), i32(M), i32(N), i32(K), i32(ba), i32(0), i32(1), i32(0), i32(1), i32(chunk), ll(ktotal), i32(0), _stream())
-    call("coskad_gemm_sum_f32", ptr(part), i32(chunks), ctypes.c_size_t(M * N), ptr(out), i32(1 if accumulate else 0), _stream())
+    call("coskad_gemm_f32", A, B, part, None, sab, sam, sak, sbb, sbk, sbn, 0, 0, 0, M, N, K, ba, 0, 1, 0, 1, chunk, ktotal, 0, _stream())
+    call("coskad_gemm_sum_f32", part, chunks, M * N, out, 1 if accumulate else 0, _stream())
     return out
 
 
@@ -665,18 +603,14 @@ def gemm_rows_outer(G: Tensor, S: Tensor, out: Tensor, rows_per_piece: int = 256
     chunk = max(1, (nb + target_chunks - 1) // target_chunks)
     chunks = (nb + chunk - 1) // chunk
     part = torch.empty(chunks, M, N, device=G.device, dtype=torch.float32)
-    ll = ctypes.c_longlong
-    call("coskad_gemm_f32", ptr(G), ptr(S), ptr(part), ptr(None), ll(rows_per_piece * M), ll(1), ll(M),
-         ll(rows_per_piece * N), ll(N), ll(1), ll(0), ll(0), ll(0), i32(M), i32(N), i32(rows_per_piece), i32(nb), i32(0), i32(1),
-         i32(0), i32(1), i32(chunk), ll(R), i32(0), _stream())
-    call("coskad_gemm_sum_f32", ptr(part), i32(chunks), ctypes.c_size_t(M * N), ptr(out), i32(1 if accumulate else 0), _stream())
+    call("coskad_gemm_f32", G, S, part, None, rows_per_piece * M, 1, M, rows_per_piece * N, N, 1, 0, 0, 0, M, N, rows_per_piece, nb, 0, 1,
+         0, 1, chunk, R, 0, _stream())
+    call("coskad_gemm_sum_f32", part, chunks, M * N, out, 1 if accumulate else 0, _stream())
     return out
 
 
 def conv1x1_ok(M: int, K: int, P: int) -> bool:
-    fn = _lib.lib().coskad_conv1x1_ok
-    fn.restype = ctypes.c_int
-    return bool(fn(i32(M), i32(K), i32(P)))
+    return bool(_lib.lib().coskad_conv1x1_ok(M, K, P))
 
 
 def conv1x1(W: Tensor, x: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None, accumulate: bool = False,
@@ -699,13 +633,9 @@ def conv1x1(W: Tensor, x: Tensor, bias: Optional[Tensor] = None, out: Optional[T
         return out, None
     parts = None
     if want_stats:
-        fn = _lib.lib().coskad_conv1x1_stat_rows
-        fn.restype = ctypes.c_int
-        rows = fn(i32(M), i32(K), i32(P), i32(B))
+        rows = _lib.lib().coskad_conv1x1_stat_rows(M, K, P, B)
         parts = torch.empty(rows, M, 2, device=x.device, dtype=torch.float64)
-    ll = ctypes.c_longlong
-    call("coskad_conv1x1_f32", ptr(W), ll(sm), ll(sk), ptr(x), ptr(out), ptr(bias), ptr(parts), i32(M), i32(K), i32(P), i32(B),
-         i32(1 if accumulate else 0), _stream())
+    call("coskad_conv1x1_f32", W, sm, sk, x, out, bias, parts, M, K, P, B, 1 if accumulate else 0, _stream())
     return out, parts
 
 
@@ -718,9 +648,7 @@ def conv1x1_wgrad(G: Tensor, x: Tensor, out: Tensor, target_chunks: int = 64, ac
     B, M, P = G.shape
     K = x.shape[1]
     _chk(G, "G"); _chk(x, "x", (B, K, P)); _chk(out, "out", (M, K))
-    fn = _lib.lib().coskad_conv1x1_wgrad_ok
-    fn.restype = ctypes.c_int
-    if not fn(i32(M), i32(K), i32(P)) or G.data_ptr() % 16 or x.data_ptr() % 16:
+    if not _lib.lib().coskad_conv1x1_wgrad_ok(M, K, P) or G.data_ptr() % 16 or x.data_ptr() % 16:
         return gemm_reduce(G, x.transpose(1, 2), out, target_chunks=target_chunks, accumulate=accumulate)
     # the kernel's grid is (K tiles, M tiles, clip chunks): enough chunks for ~WGRAD_BLOCKS workgroups (narrow layers have ONE tile)
     tm, tk = (128, 128) if (M % 128 == 0 and K % 128 == 0) else ((64, 64) if M % 64 == 0 else (32, 64))
@@ -729,8 +657,8 @@ def conv1x1_wgrad(G: Tensor, x: Tensor, out: Tensor, target_chunks: int = 64, ac
     chunk = max(1, (B + target_chunks - 1) // target_chunks)
     chunks = (B + chunk - 1) // chunk
     part = torch.empty(chunks, M, K, device=G.device, dtype=torch.float32)
-    call("coskad_conv1x1_wgrad_f32", ptr(G), ptr(x), ptr(part), i32(M), i32(K), i32(P), i32(B), i32(chunk), _stream())
-    call("coskad_gemm_sum_f32", ptr(part), i32(chunks), ctypes.c_size_t(M * K), ptr(out), i32(1 if accumulate else 0), _stream())
+    call("coskad_conv1x1_wgrad_f32", G, x, part, M, K, P, B, chunk, _stream())
+    call("coskad_gemm_sum_f32", part, chunks, M * K, out, 1 if accumulate else 0, _stream())
     return out
 
 
@@ -761,9 +689,8 @@ def bn2_stats_parts(parts: Tensor, bn, count: int) -> Tensor:
     rows, C, _ = parts.shape
     _chk(parts, "parts", (rows, C, 2), dtype=torch.float64)
     stat = torch.empty(2 * C, device=parts.device, dtype=torch.float32)
-    call("coskad_bn2_stats_parts_f32", ptr(parts), i32(rows), ptr(stat), ptr(bn.running_mean), ptr(bn.running_var),
-         ptr(bn.num_batches_tracked), ctypes.c_float(bn_momentum(bn)), ctypes.c_float(bn.eps),
-         ctypes.c_double(float(count)), i32(C), _stream())
+    call("coskad_bn2_stats_parts_f32", parts, rows, stat, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn_momentum(bn), bn.eps,
+         float(count), C, _stream())
     return stat
 
 
@@ -774,9 +701,9 @@ def relu_bwd(out: Tensor, dout: Tensor, dbias: Optional[Tensor] = None, accumula
     g = torch.empty_like(out)
     slices = min(Nb, 64)
     part = torch.empty(slices, C, device=out.device, dtype=torch.float32)
-    call("coskad_relu_bwd_f32", ptr(out), ptr(dout), ptr(g), ptr(part), i32(Nb), i32(C), i32(P), i32(slices), _stream())
+    call("coskad_relu_bwd_f32", out, dout, g, part, Nb, C, P, slices, _stream())
     if dbias is not None:
-        call("coskad_gemm_sum_f32", ptr(part), i32(slices), ctypes.c_size_t(C), ptr(dbias), i32(1 if accumulate else 0), _stream())
+        call("coskad_gemm_sum_f32", part, slices, C, dbias, 1 if accumulate else 0, _stream())
     return g
 
 
@@ -784,7 +711,7 @@ def softmax_rows(x: Tensor) -> Tensor:
     n = x.shape[0]
     _chk(x, "x", (n, n))
     y = torch.empty_like(x)
-    call("coskad_softmax_rows_f32", ptr(x), ptr(y), i32(n), _stream())
+    call("coskad_softmax_rows_f32", x, y, n, _stream())
     return y
 
 
@@ -793,7 +720,7 @@ def softmax_rows_bwd(y: Tensor, dy: Tensor, out: Optional[Tensor] = None) -> Ten
     n = y.shape[0]
     _chk(y, "y", (n, n)); _chk(dy, "dy", (n, n)); _chk(out, "out", (n, n), optional=True)
     dx = torch.empty_like(y) if out is None else out
-    call("coskad_softmax_rows_bwd_f32", ptr(y), ptr(dy), ptr(dx), i32(n), _stream())
+    call("coskad_softmax_rows_bwd_f32", y, dy, dx, n, _stream())
     return dx
 
 
@@ -817,8 +744,7 @@ def plain_gcn_fwd(X: Tensor, W: Tensor, Ap: Tensor, bias: Optional[Tensor] = Non
     _chk(X, "X"); _chk(W, "W", (Ci, Co)); _chk(Ap, "Ap", (P, P)); _chk(bias, "bias", (Co,), optional=True)
     O = torch.empty(B, Co, P, device=X.device, dtype=torch.float32)
     S = torch.empty(B, min(Ci, Co), P, device=X.device, dtype=torch.float32) if save else None
-    call("coskad_plain_gcn_fwd_f32", ptr(X), ptr(W), ptr(Ap), ptr(bias), ptr(O), ptr(S), i32(B), i32(Ci), i32(Co), i32(P),
-         i32(grid_cap), _stream(), tag=(Ci, Co))
+    call("coskad_plain_gcn_fwd_f32", X, W, Ap, bias, O, S, B, Ci, Co, P, grid_cap, _stream(), tag=(Ci, Co))
     return O, S
 
 
@@ -833,22 +759,19 @@ def plain_gcn_bwd(X: Tensor, S: Optional[Tensor], O: Tensor, dO: Tensor, W: Tens
     Cn = min(Ci, Co)
     _chk(X, "X"); _chk(W, "W", (Ci, Co)); _chk(Ap, "Ap", (P, P)); _chk(O, "O", (B, Co, P)); _chk(dO, "dO", (B, Co, P))
     _chk(S, "S", (B, Cn, P), optional=Ci > Co); _chk(dW, "dW", (Ci, Co)); _chk(db, "db", (Co,), optional=True)
-    fn = _lib.lib().coskad_plain_gcn_ws_bytes
-    fn.restype = ctypes.c_size_t
-    nws = fn(i32(B), i32(Ci), i32(Co), i32(P), i32(grid_cap))
+    nws = _lib.lib().coskad_plain_gcn_ws_bytes(B, Ci, Co, P, grid_cap)
     ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=X.device)
     dX = torch.empty_like(X) if need_dx else None
     D = torch.empty(B, Cn, P, device=X.device, dtype=torch.float32) if need_da else None
-    call("coskad_plain_gcn_bwd_f32", ptr(X), ptr(S), ptr(O), ptr(dO), ptr(W), ptr(Ap), ptr(dX), ptr(dW), ptr(db), ptr(D), ptr(ws),
-         ctypes.c_size_t(nws), i32(B), i32(Ci), i32(Co), i32(P), i32(1 if need_dx else 0), i32(1 if need_da else 0),
-         i32(1 if accumulate else 0), i32(grid_cap), _stream(), tag=(Ci, Co))
+    call("coskad_plain_gcn_bwd_f32", X, S, O, dO, W, Ap, dX, dW, db, D, ws, nws, B, Ci, Co, P, 1 if need_dx else 0, 1 if need_da else 0,
+         1 if accumulate else 0, grid_cap, _stream(), tag=(Ci, Co))
     return dX, D
 
 
 def _bn2_ws(Nb: int, C: int, device, bwd: bool = False) -> Tensor:
-    fn = getattr(_lib.lib(), "coskad_bn2_bwd_ws_bytes" if bwd else "coskad_bn2_ws_bytes")
-    fn.restype = ctypes.c_size_t
-    return torch.empty(fn(i32(Nb), i32(C)), dtype=torch.uint8, device=device)
+    lib = _lib.lib()
+    nbytes = lib.coskad_bn2_bwd_ws_bytes(Nb, C) if bwd else lib.coskad_bn2_ws_bytes(Nb, C)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 def bn2_stats(x: Tensor, bn, training: bool) -> Tensor:
@@ -858,9 +781,8 @@ def bn2_stats(x: Tensor, bn, training: bool) -> Tensor:
     _chk(x, "x")
     stat = torch.empty(2 * C, device=x.device, dtype=torch.float32)
     ws = _bn2_ws(Nb, C, x.device)
-    call("coskad_bn2_stats_f32", ptr(x), ptr(stat), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-         ctypes.c_float(bn_momentum(bn) if training else 0.0), ctypes.c_float(bn.eps), i32(1 if training else 0),
-         ptr(ws), ctypes.c_size_t(ws.numel()), i32(Nb), i32(C), i32(P), _stream())
+    call("coskad_bn2_stats_f32", x, stat, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn_momentum(bn) if training else 0.0,
+         bn.eps, 1 if training else 0, ws, ws.numel(), Nb, C, P, _stream())
     return stat
 
 
@@ -869,16 +791,14 @@ def bn2_apply_prelu(Ct, Cr, stat_t, gt, bt, stat_r, gr, br, slope, drop_p: float
     Nb, C, P = Ct.shape
     _chk(Ct, "Ct"); _chk(Cr, "Cr", (Nb, C, P)); _chk(stat_t, "stat_t", (2 * C,)); _chk(stat_r, "stat_r", (2 * C,), optional=True)
     out = torch.empty_like(Ct)
-    call("coskad_bn2_apply_prelu_f32", ptr(Ct), ptr(Cr), ptr(stat_t), ptr(gt), ptr(bt), ptr(stat_r), ptr(gr), ptr(br), ptr(slope),
-         ptr(out), i32(Nb), i32(C), i32(P), _stream(), ctypes.c_float(drop_p), ctypes.c_ulonglong(drop_seed))
+    call("coskad_bn2_apply_prelu_f32", Ct, Cr, stat_t, gt, bt, stat_r, gr, br, slope, out, Nb, C, P, _stream(), drop_p, drop_seed)
     return out
 
 
 def dropout_mask(shape, drop_p: float, drop_seed: int, device) -> Tensor:
     """The mask bn2_apply_prelu / bn2_bwd apply for (drop_p, drop_seed): values 0 or 1 / (1 - p), in element order."""
     out = torch.empty(shape, device=device, dtype=torch.float32)
-    call("coskad_dropout_mask_f32", ptr(out), ctypes.c_size_t(out.numel()), ctypes.c_float(drop_p), ctypes.c_ulonglong(drop_seed),
-         _stream())
+    call("coskad_dropout_mask_f32", out, out.numel(), drop_p, drop_seed, _stream())
     return out
 
 
@@ -898,16 +818,13 @@ def bn2_bwd(Ct, Cr, dOut, stat_t, gt, bt, stat_r, gr, br, slope, training: bool,
     _chk(dgt, "dgt", (C,)); _chk(dbt, "dbt", (C,)); _chk(dgr, "dgr", (C,), optional=True); _chk(dbr, "dbr", (C,), optional=True)
     _chk(dslope, "dslope", (1,))
     ws = _bn2_ws(Nb, C, Ct.device, bwd=True)
-    call("coskad_bn2_bwd_f32", ptr(Ct), ptr(Cr), ptr(dOut), ptr(stat_t), ptr(gt), ptr(bt), ptr(stat_r), ptr(gr), ptr(br), ptr(slope),
-         ptr(dCt), ptr(dCr), ptr(dgt), ptr(dbt), ptr(dgr), ptr(dbr), ptr(dslope), i32(1 if training else 0), ptr(ws),
-         ctypes.c_size_t(ws.numel()), i32(Nb), i32(C), i32(P), _stream(), ctypes.c_float(drop_p), ctypes.c_ulonglong(drop_seed))
+    call("coskad_bn2_bwd_f32", Ct, Cr, dOut, stat_t, gt, bt, stat_r, gr, br, slope, dCt, dCr, dgt, dbt, dgr, dbr, dslope,
+         1 if training else 0, ws, ws.numel(), Nb, C, P, _stream(), drop_p, drop_seed)
     return dCt, dCr, dgt, dbt, dgr, dbr, dslope
 
 
 def mlp_head_ws_floats(B: int, H: int, L: int) -> int:
-    fn = _lib.lib().coskad_mlp_head_ws_floats
-    fn.restype = ctypes.c_size_t
-    return fn(i32(B), i32(H), i32(L))
+    return _lib.lib().coskad_mlp_head_ws_floats(B, H, L)
 
 
 def mlp_head_fwd(y1, gamma, beta, running_mean, running_var, nbt, W2, b2, training: bool, momentum: float = 0.1,
@@ -921,9 +838,8 @@ def mlp_head_fwd(y1, gamma, beta, running_mean, running_var, nbt, W2, b2, traini
     _chk(nbt, "num_batches_tracked", (), dtype=torch.int64, optional=True)
     z = torch.empty(B, L, device=y1.device, dtype=torch.float32)
     stat = torch.empty(mlp_head_ws_floats(B, H, L), device=y1.device, dtype=torch.float32)
-    call("coskad_mlp_head_fwd_f32", ptr(y1), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), ptr(nbt),
-         ctypes.c_float(momentum), ctypes.c_float(eps), i32(1 if training else 0), ptr(W2), ptr(b2), ptr(z), ptr(stat),
-         i32(B), i32(H), i32(L), _stream())
+    call("coskad_mlp_head_fwd_f32", y1, gamma, beta, running_mean, running_var, nbt, momentum, eps, 1 if training else 0, W2, b2, z, stat,
+         B, H, L, _stream())
     return z, stat
 
 
@@ -938,9 +854,8 @@ def mlp_head_bwd(y1, stat, gamma, beta, W2, dz, grads: dict, training: bool, acc
     _chk(grads.get("b2"), "db2", (L,), optional=True)
     dy1 = torch.empty_like(y1)
     red = torch.empty(mlp_head_ws_floats(B, H, L), device=y1.device, dtype=torch.float32)
-    call("coskad_mlp_head_bwd_f32", ptr(y1), ptr(stat), ptr(gamma), ptr(beta), ptr(W2), ptr(dz), ptr(dy1), ptr(grads["gamma"]),
-         ptr(grads["beta"]), ptr(grads["W2"]), ptr(grads.get("b2")), ptr(red), i32(1 if training else 0),
-         i32(1 if accumulate else 0), i32(B), i32(H), i32(L), _stream())
+    call("coskad_mlp_head_bwd_f32", y1, stat, gamma, beta, W2, dz, dy1, grads["gamma"], grads["beta"], grads["W2"], grads.get("b2"), red,
+         1 if training else 0, 1 if accumulate else 0, B, H, L, _stream())
     return dy1
 
 
@@ -961,9 +876,7 @@ def head_count_slot(L: int) -> int:
 
 
 def head_ws(B: int, device, L: int = 16) -> Tensor:
-    fn = _lib.lib().coskad_head_ws_floats_l
-    fn.restype = ctypes.c_size_t
-    return torch.empty(fn(i32(B), i32(L)), device=device, dtype=torch.float32)
+    return torch.empty(_lib.lib().coskad_head_ws_floats_l(B, L), device=device, dtype=torch.float32)
 
 
 def mse_head(z, c, need_grad=True, need_score=False, acc=None, upstream=1.0, ws=None):
@@ -975,8 +888,7 @@ def mse_head(z, c, need_grad=True, need_score=False, acc=None, upstream=1.0, ws=
     dz = torch.empty_like(z) if need_grad else None
     score = torch.empty(B, device=z.device, dtype=torch.float32) if need_score else None
     stats = torch.empty(S, device=z.device, dtype=torch.float32)
-    call("coskad_mse_head_f32", ptr(z), ptr(c), ptr(dz), ptr(score), ptr(stats), ptr(acc), ctypes.c_float(upstream),
-         ptr(ws), i32(B), i32(L), _stream())
+    call("coskad_mse_head_f32", z, c, dz, score, stats, acc, upstream, ws, B, L, _stream())
     return stats, dz, score
 
 
@@ -991,8 +903,7 @@ def mahalanobis_head(z, c, VI, need_grad=True, need_score=False, acc=None, gram=
     dz = torch.empty_like(z) if need_grad else None
     score = torch.empty(B, device=z.device, dtype=torch.float32) if need_score else None
     stats = torch.empty(S, device=z.device, dtype=torch.float32)
-    call("coskad_mahalanobis_head_f32", ptr(z), ptr(c), ptr(VI), ptr(dz), ptr(score), ptr(stats), ptr(acc), ptr(gram),
-         i32(int(gram_accumulate)), ctypes.c_float(upstream), ptr(ws), i32(B), i32(L), _stream())
+    call("coskad_mahalanobis_head_f32", z, c, VI, dz, score, stats, acc, gram, int(gram_accumulate), upstream, ws, B, L, _stream())
     return stats, dz, score
 
 
@@ -1006,8 +917,7 @@ def poincare_head(z, c, need_grad=True, need_zh=False, need_score=False, acc=Non
     zh = torch.empty_like(z) if need_zh else None
     score = torch.empty(B, device=z.device, dtype=torch.float32) if (need_score and c is not None) else None
     stats = torch.empty(S, device=z.device, dtype=torch.float32)
-    call("coskad_poincare_head_f32", ptr(z), ptr(c), ptr(dz), ptr(zh), ptr(score), ptr(stats), ptr(acc),
-         ctypes.c_float(upstream), ptr(ws), i32(B), i32(L), _stream())
+    call("coskad_poincare_head_f32", z, c, dz, zh, score, stats, acc, upstream, ws, B, L, _stream())
     return stats, dz, zh, score
 
 
@@ -1015,7 +925,7 @@ def poincare_dist(zh, c):
     B, L = zh.shape
     _chk(zh, "zh"); _chk(c, "c", (L,))
     score = torch.empty(B, device=zh.device, dtype=torch.float32)
-    call("coskad_poincare_dist_f32", ptr(zh), ptr(c), ptr(score), i32(B), i32(L), _stream())
+    call("coskad_poincare_dist_f32", zh, c, score, B, L, _stream())
     return score
 
 
@@ -1024,12 +934,12 @@ def poincare_logmap0(y):
     B, L = y.shape
     _chk(y, "y")
     out = torch.empty_like(y)
-    call("coskad_poincare_logmap0_f32", ptr(y), ptr(out), i32(B), i32(L), _stream())
+    call("coskad_poincare_logmap0_f32", y, out, B, L, _stream())
     return out
 
 
 def lowrank_fold_ok(latent: int, TV: int) -> bool:
-    return bool(_lib.lib().coskad_lowrank_fold_ok(i32(latent), i32(TV)))
+    return bool(_lib.lib().coskad_lowrank_fold_ok(latent, TV))
 
 
 def lowrank_fold_fwd(X: Tensor, G: Tensor, bn_t, bn_r, bias_t, bias_r, n_pos: float):
@@ -1045,10 +955,8 @@ def lowrank_fold_fwd(X: Tensor, G: Tensor, bn_t, bn_r, bias_t, bias_r, n_pos: fl
     xx = torch.empty(2, Co, K, K, device=dev, dtype=torch.float64)
     args = []
     for bn, cb in ((bn_t, bias_t), (bn_r, bias_r)):
-        args += [ptr(bn.weight), ptr(bn.bias), ptr(cb), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                 ctypes.c_float(bn_momentum(bn)), ctypes.c_float(bn.eps)]
-    call("coskad_lowrank_fold_fwd_f32", ptr(X), ptr(G), *args, ctypes.c_double(n_pos), ptr(Mw), ptr(Mb), ptr(saved), ptr(xbar), ptr(xx),
-         i32(Co), i32(TV), _stream())
+        args += [bn.weight, bn.bias, cb, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn_momentum(bn), bn.eps]
+    call("coskad_lowrank_fold_fwd_f32", X, G, *args, n_pos, Mw, Mb, saved, xbar, xx, Co, TV, _stream())
     return Mw, Mb, (saved, xbar, xx)
 
 
@@ -1062,8 +970,7 @@ def lowrank_fold_bwd(X: Tensor, G: Tensor, dMw: Tensor, dMb: Tensor, ctx, gamma_
     dgamma = torch.empty(2, Co, device=dev, dtype=torch.float32)
     dbeta = torch.empty(Co, device=dev, dtype=torch.float32)
     dGc = torch.empty(Co, K, K, device=dev, dtype=torch.float64)
-    call("coskad_lowrank_fold_bwd_f32", ptr(X), ptr(G), ptr(dMw), ptr(dMb), ptr(saved), ptr(xbar), ptr(xx), ptr(gamma_t), ptr(gamma_r),
-         ctypes.c_double(n_pos), ptr(dX), ptr(dgamma), ptr(dbeta), ptr(dGc), i32(Co), i32(TV), _stream())
+    call("coskad_lowrank_fold_bwd_f32", X, G, dMw, dMb, saved, xbar, xx, gamma_t, gamma_r, n_pos, dX, dgamma, dbeta, dGc, Co, TV, _stream())
     return dX, dgamma, dbeta, dGc.sum(0)
 
 
@@ -1077,7 +984,7 @@ def narrow_conv_fwd(U: Tensor, in_slope: Optional[Tensor], W: Tensor) -> Tensor:
     J = W.shape[0]
     _chk(U, "U"); _chk(W, "W", (J, Ci)); _chk(in_slope, "in_slope", (1,), optional=True)
     out = torch.empty(B, J, T, V, device=U.device, dtype=torch.float32)
-    call("coskad_narrow_conv_fwd_f32", ptr(U), ptr(in_slope), ptr(W), ptr(out), i32(B), i32(Ci), i32(J), i32(T * V), _stream())
+    call("coskad_narrow_conv_fwd_f32", U, in_slope, W, out, B, Ci, J, T * V, _stream())
     return out
 
 
@@ -1087,20 +994,19 @@ def narrow_conv_bwd(U: Tensor, in_slope: Optional[Tensor], W: Tensor, dOut: Tens
     B, Ci, T, V = U.shape
     J = W.shape[0]
     _chk(U, "U"); _chk(W, "W", (J, Ci)); _chk(dOut, "dOut", (B, J, T, V)); _chk(in_slope, "in_slope", (1,), optional=True)
-    rows = _lib.lib().coskad_narrow_conv_rows(i32(B), i32(T * V))
+    rows = _lib.lib().coskad_narrow_conv_rows(B, T * V)
     E = J * Ci + 1
     part = torch.empty(rows, E, device=U.device, dtype=torch.float32)
     dU = torch.empty_like(U)
-    call("coskad_narrow_conv_bwd_f32", ptr(U), ptr(in_slope), ptr(W), ptr(dOut), ptr(dU), ptr(part), ctypes.c_size_t(part.numel()),
-         i32(B), i32(Ci), i32(J), i32(T * V), _stream())
+    call("coskad_narrow_conv_bwd_f32", U, in_slope, W, dOut, dU, part, part.numel(), B, Ci, J, T * V, _stream())
     sums = torch.empty(E, device=U.device, dtype=torch.float32)
-    call("coskad_gemm_sum_f32", ptr(part), i32(rows), ctypes.c_size_t(E), ptr(sums), i32(0), _stream())
+    call("coskad_gemm_sum_f32", part, rows, E, sums, 0, _stream())
     return dU, sums
 
 
 def commute_ok(T: int, V: int, Ci: int, Co: int) -> bool:
     """the (C_in -> C_out) layers csrc/commute_layer.hip runs by commutation (convolutions first, mixing on C_out channels)"""
-    return bool(_lib.lib().coskad_commute_ok(i32(T), i32(V), i32(Ci), i32(Co)))
+    return bool(_lib.lib().coskad_commute_ok(T, V, Ci, Co))
 
 
 _commute_ws: dict = {}
@@ -1108,8 +1014,7 @@ _commute_ws: dict = {}
 
 def _commute_scratch(B: int, T: int, V: int, dev) -> Tensor:
     lib = _lib.lib()
-    lib.coskad_commute_ws_floats.restype = ctypes.c_size_t
-    n = int(lib.coskad_commute_ws_floats(i32(B), i32(T), i32(V)))
+    n = int(lib.coskad_commute_ws_floats(B, T, V))
     key = (str(dev), T, V)
     ws = _commute_ws.get(key)
     if ws is None or ws.numel() < n:
@@ -1150,11 +1055,9 @@ def commute_fwd(U_prev: Tensor, in_slope: Optional[Tensor], Wt: Tensor, Wr: Tens
         _chk(An, "A_next", (T, V, V)); _chk(Tn, "T_next", (V, T, T)); _chk(slope_out, "slope_out", (1,))
         Zn = torch.empty(B, 16, T, V, device=dev, dtype=torch.float32)
         pn = torch.empty(768 * 2 * (16 * 16 + 16), device=dev, dtype=torch.float32)
-    call("coskad_commute_fwd_f32", ptr(U_prev), ptr(in_slope), ptr(Wt), ptr(Wr), ptr(A), ptr(Tm), ptr(gamma_t), ptr(beta_t),
-         ptr(gamma_r), ptr(beta_r), ptr(bias_t), ptr(bias_r), ptr(rm_t), ptr(rv_t), ptr(rm_r), ptr(rv_r), ptr(nbt_t), ptr(nbt_r),
-         ctypes.c_float(momentum), ctypes.c_float(eps), ptr(YR), ptr(Zy), ptr(U), ptr(stat), ptr(ws), ctypes.c_size_t(ws.numel()),
-         ptr(An), ptr(Tn), ptr(slope_out if next_layer is not None else None), ptr(Zn), ptr(pn), ctypes.byref(rows),
-         i32(B), i32(T), i32(V), _stream())
+    call("coskad_commute_fwd_f32", U_prev, in_slope, Wt, Wr, A, Tm, gamma_t, beta_t, gamma_r, beta_r, bias_t, bias_r, rm_t, rv_t, rm_r,
+         rv_r, nbt_t, nbt_r, momentum, eps, YR, Zy, U, stat, ws, ws.numel(), An, Tn, slope_out if next_layer is not None else None, Zn, pn,
+         ctypes.byref(rows), B, T, V, _stream())
     pending = (Zn, pn, int(rows.value)) if next_layer is not None else None
     return U, (U_prev, in_slope, Wt, Wr, A, Tm, YR, Zy, stat), pending
 
@@ -1184,13 +1087,11 @@ def commute_bwd(saved, dU: Tensor, into: dict, below=None):
         bx, bz = below
         _chk(bx, "below.x", (B, 2, T, V)); _chk(bz, "below.Z", (B, 2, T, V))
         lib = _lib.lib()
-        lib.coskad_commute_below_floats.restype = ctypes.c_size_t
-        rows = int(lib.coskad_commute_below_rows(i32(B)))
-        buf = torch.empty(int(lib.coskad_commute_below_floats(i32(B))), device=U_prev.device, dtype=torch.float32)
-    call("coskad_commute_bwd_f32", ptr(U_prev), ptr(in_slope), ptr(Wt), ptr(Wr), ptr(A), ptr(Tm), ptr(YR), ptr(Zy), ptr(stat), ptr(dU), ptr(d_in),
-         ptr(into["A"]), ptr(into["T"]), ptr(into["Wt"]), ptr(into["Wr"]), ptr(into["gt"]), ptr(into["bet"]), ptr(into["gr"]),
-         ptr(into["ber"]), ptr(dsl), ptr(ws), ctypes.c_size_t(ws.numel()), ptr(bx), ptr(bz), ptr(buf),
-         ctypes.c_size_t(buf.numel() if buf is not None else 0), i32(B), i32(T), i32(V), _stream())
+        rows = int(lib.coskad_commute_below_rows(B))
+        buf = torch.empty(int(lib.coskad_commute_below_floats(B)), device=U_prev.device, dtype=torch.float32)
+    call("coskad_commute_bwd_f32", U_prev, in_slope, Wt, Wr, A, Tm, YR, Zy, stat, dU, d_in, into["A"], into["T"], into["Wt"], into["Wr"],
+         into["gt"], into["bet"], into["gr"], into["ber"], dsl, ws, ws.numel(), bx, bz, buf, buf.numel() if buf is not None else 0, B, T, V,
+         _stream())
     return d_in, ((buf, rows) if below is not None else None)
 
 
@@ -1214,14 +1115,13 @@ def ps_head_forward(mean_raw: Tensor, var_raw: Tensor, generator=None):
     kappa = torch.empty(B, device=dev, dtype=torch.float32)
     conc = torch.empty(B, 2, device=dev, dtype=torch.float32)
     total = torch.empty(B, device=dev, dtype=torch.float32)
-    call("coskad_ps_head_prep_f32", ptr(mean_raw), i32(ldm), ptr(var_raw), i32(ldv), ptr(mu), ptr(kappa), ptr(conc), ptr(total),
-         i32(B), i32(L), _stream())
+    call("coskad_ps_head_prep_f32", mean_raw, ldm, var_raw, ldv, mu, kappa, conc, total, B, L, _stream())
     x = torch._sample_dirichlet(conc, generator) if generator is not None else torch._sample_dirichlet(conc)
     eps = torch.randn(B, L - 1, device=dev, dtype=torch.float32, generator=generator)
     z = torch.empty(B, L, device=dev, dtype=torch.float32)
     kl = torch.empty(B, device=dev, dtype=torch.float32)
     ik = torch.empty(B, device=dev, dtype=torch.float32)
-    call("coskad_ps_head_sample_f32", ptr(x), ptr(eps), ptr(mu), ptr(kappa), ptr(z), ptr(kl), ptr(ik), i32(B), i32(L), _stream())
+    call("coskad_ps_head_sample_f32", x, eps, mu, kappa, z, kl, ik, B, L, _stream())
     return z, kl, ik, (mean_raw, var_raw, mu, kappa, conc, total, x, eps)
 
 
@@ -1237,23 +1137,23 @@ def ps_head_backward(saved, dz: Tensor, w_kl: float, w_exp: float, d_mean_raw: O
         d_mean_raw = torch.empty(B, L, device=dz.device, dtype=torch.float32)
     if d_var_raw is None:
         d_var_raw = torch.empty(B, 1, device=dz.device, dtype=torch.float32)
-    call("coskad_ps_head_bwd_f32", ptr(dz), ptr(x), ptr(g), ptr(eps), ptr(mu), ptr(kappa), ptr(mean_raw), i32(_rows(mean_raw, "mean_raw", L)),
-         ptr(var_raw), i32(_rows(var_raw, "var_raw", 1)), ctypes.c_float(w_kl), ctypes.c_float(w_exp), ptr(d_mean_raw),
-         i32(_rows(d_mean_raw, "d_mean_raw", L)), ptr(d_var_raw), i32(_rows(d_var_raw, "d_var_raw", 1)), i32(B), i32(L), _stream())
+    call("coskad_ps_head_bwd_f32", dz, x, g, eps, mu, kappa, mean_raw, _rows(mean_raw, "mean_raw", L), var_raw,
+         _rows(var_raw, "var_raw", 1), w_kl, w_exp, d_mean_raw, _rows(d_mean_raw, "d_mean_raw", L), d_var_raw,
+         _rows(d_var_raw, "d_var_raw", 1), B, L, _stream())
     return d_mean_raw, d_var_raw
 
 
 def center_finalize(acc, eps: float, L: int):
     _chk(acc, "acc", (head_slots(L),))
     c = torch.empty(L, device=acc.device, dtype=torch.float32)
-    call("coskad_center_finalize_f32", ptr(acc), ptr(c), ctypes.c_float(eps), i32(L), _stream())
+    call("coskad_center_finalize_f32", acc, c, eps, L, _stream())
     return c
 
 
 def midpoint_finalize(acc, L: int):
     _chk(acc, "acc", (head_slots(L),))
     c = torch.empty(L, device=acc.device, dtype=torch.float32)
-    call("coskad_midpoint_finalize_f32", ptr(acc), ptr(c), i32(L), _stream())
+    call("coskad_midpoint_finalize_f32", acc, c, L, _stream())
     return c
 
 
@@ -1261,7 +1161,7 @@ def sqnorm(p, mask, scale: float, ws=None):
     _chk(p, "p"); _chk(mask, "mask", p.shape, optional=True)
     ws = torch.empty(256, device=p.device, dtype=torch.float32) if ws is None else ws
     out = torch.empty(1, device=p.device, dtype=torch.float32)
-    call("coskad_sqnorm_f32", ptr(p), ptr(mask), ctypes.c_size_t(p.numel()), ctypes.c_float(scale), ptr(out), ptr(ws), _stream())
+    call("coskad_sqnorm_f32", p, mask, p.numel(), scale, out, ws, _stream())
     return out
 
 
@@ -1269,9 +1169,7 @@ def adam(p, g, m, v, mask, lr, beta1, beta2, eps, step, gscale=1.0, reg_coef=0.0
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _chk(t, n, p.shape)
     _chk(mask, "mask", p.shape, optional=True)
-    call("coskad_adam_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(mask), ctypes.c_size_t(p.numel()), ctypes.c_float(lr),
-         ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), i32(step), ctypes.c_float(gscale),
-         ctypes.c_float(reg_coef), _stream())
+    call("coskad_adam_f32", p, g, m, v, mask, p.numel(), lr, beta1, beta2, eps, step, gscale, reg_coef, _stream())
 
 
 def adam_pow(p, g, m, v, mask, lr, beta1, beta2, eps, b1pow, b2pow, gscale=1.0, reg_coef=0.0):
@@ -1279,15 +1177,13 @@ def adam_pow(p, g, m, v, mask, lr, beta1, beta2, eps, b1pow, b2pow, gscale=1.0, 
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _chk(t, n, p.shape)
     _chk(mask, "mask", p.shape, optional=True)
-    call("coskad_adam_pow_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(mask), ctypes.c_size_t(p.numel()), ctypes.c_float(lr),
-         ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_float(b1pow), ctypes.c_float(b2pow),
-         ctypes.c_float(gscale), ctypes.c_float(reg_coef), _stream())
+    call("coskad_adam_pow_f32", p, g, m, v, mask, p.numel(), lr, beta1, beta2, eps, b1pow, b2pow, gscale, reg_coef, _stream())
 
 
 def prelu_fwd(u: Tensor, slope: Tensor) -> Tensor:
     _chk(u, "u"); _chk(slope, "slope", (1,))
     out = torch.empty_like(u)
-    call("coskad_prelu_fwd_f32", ptr(u), ptr(slope), ptr(out), ctypes.c_size_t(u.numel()), _stream())
+    call("coskad_prelu_fwd_f32", u, slope, out, u.numel(), _stream())
     return out
 
 
@@ -1295,8 +1191,7 @@ def prelu_bwd(u: Tensor, dout: Tensor, slope: Tensor, dslope: Optional[Tensor] =
     _chk(u, "u"); _chk(dout, "dout", u.shape); _chk(slope, "slope", (1,)); _chk(dslope, "dslope", (1,), optional=True)
     du = torch.empty_like(u)
     ws = torch.empty(1024, device=u.device, dtype=torch.float32)
-    call("coskad_prelu_bwd_f32", ptr(u), ptr(dout), ptr(slope), ptr(du), ptr(dslope), ptr(ws),
-         i32(1 if accumulate else 0), ctypes.c_size_t(u.numel()), _stream())
+    call("coskad_prelu_bwd_f32", u, dout, slope, du, dslope, ws, 1 if accumulate else 0, u.numel(), _stream())
     return du
 
 
@@ -1308,8 +1203,8 @@ def rec_head(U: Tensor, x: Tensor, slope: Tensor, need_grad: bool = True, need_x
     xrec = torch.empty_like(U) if need_xrec else None
     loss = torch.empty(1, device=U.device, dtype=torch.float32)
     ws = torch.empty(2048, device=U.device, dtype=torch.float32)
-    call("coskad_rec_head_f32", ptr(U), ptr(x), ptr(slope), ptr(xrec), ptr(dU), ptr(loss), ptr(dslope if need_grad else None),
-         ctypes.c_float(upstream), ptr(ws), i32(1 if accumulate else 0), ctypes.c_size_t(U.numel()), _stream())
+    call("coskad_rec_head_f32", U, x, slope, xrec, dU, loss, dslope if need_grad else None, upstream, ws, 1 if accumulate else 0, U.numel(),
+         _stream())
     return loss, dU, xrec
 
 
@@ -1325,7 +1220,7 @@ def rev_btlnk_fwd(z: Tensor, W: Tensor, bias: Optional[Tensor]) -> Tensor:
     if not rev_btlnk_ok(N, L):
         return gemm(z, W.t(), bias=bias, bias_mode=2 if bias is not None else 0)
     H = torch.empty(B, N, device=z.device, dtype=torch.float32)
-    call("coskad_rev_btlnk_fwd_f32", ptr(z), ptr(W), ptr(bias), ptr(H), i32(B), i32(N), i32(L), _stream())
+    call("coskad_rev_btlnk_fwd_f32", z, W, bias, H, B, N, L, _stream())
     return H
 
 
@@ -1351,14 +1246,11 @@ def rev_btlnk_bwd(dH: Tensor, z: Tensor, W: Tensor, dW: Tensor, db: Optional[Ten
         if dz is None:
             return gemm(dH, W)
         return gemm(dH, W, out=dz, accumulate=True)
-    fn = _lib.lib().coskad_rev_btlnk_ws_floats
-    fn.restype = ctypes.c_size_t
-    ws = torch.empty(fn(i32(B), i32(N), i32(L)), device=dH.device, dtype=torch.float32)
+    ws = torch.empty(_lib.lib().coskad_rev_btlnk_ws_floats(B, N, L), device=dH.device, dtype=torch.float32)
     acc_dz = dz is not None
     if dz is None:
         dz = torch.empty(B, L, device=dH.device, dtype=torch.float32)
-    call("coskad_rev_btlnk_bwd_f32", ptr(dH), ptr(z), ptr(W), ptr(dz), i32(1 if acc_dz else 0), ptr(dW), ptr(db),
-         i32(1 if accumulate else 0), ptr(ws), i32(B), i32(N), i32(L), _stream())
+    call("coskad_rev_btlnk_bwd_f32", dH, z, W, dz, 1 if acc_dz else 0, dW, db, 1 if accumulate else 0, ws, B, N, L, _stream())
     return dz
 
 
@@ -1366,13 +1258,10 @@ def gcn_bwd_params(x: Tensor, dZ: Tensor, A: Tensor, Tm: Tensor):
     """(dA, dT) of ConvTemporalGraphical given its input and output gradient."""
     N, C, T, V = x.shape
     _chk(x, "x"); _chk(dZ, "dZ", x.shape); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T))
-    fn = _lib.lib().coskad_gcn_bwd_params_ws_bytes
-    fn.restype = ctypes.c_size_t
-    nbytes = fn(i32(T), i32(V))
+    nbytes = _lib.lib().coskad_gcn_bwd_params_ws_bytes(T, V)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     dA, dT = torch.empty_like(A), torch.empty_like(Tm)
-    call("coskad_gcn_bwd_params_f32", ptr(x), ptr(dZ), ptr(A), ptr(Tm), ptr(dA), ptr(dT), ptr(ws),
-         ctypes.c_size_t(nbytes), i32(0), i32(N * C), i32(T), i32(V), _stream())
+    call("coskad_gcn_bwd_params_f32", x, dZ, A, Tm, dA, dT, ws, nbytes, 0, N * C, T, V, _stream())
     return dA, dT
 
 
@@ -1382,9 +1271,7 @@ def gcn_bwd_params_dx(x: Tensor, dZ: Tensor, A: Tensor, Tm: Tensor, add: Optiona
     dA / dT: destinations (e.g. views of a flat gradient buffer) instead of fresh tensors; accumulate: add to them."""
     N, C, T, V = x.shape
     _chk(x, "x"); _chk(dZ, "dZ", x.shape); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T)); _chk(add, "add", x.shape, optional=True)
-    fn = _lib.lib().coskad_gcn_bwd_params_ws_bytes
-    fn.restype = ctypes.c_size_t
-    nbytes = fn(i32(T), i32(V))
+    nbytes = _lib.lib().coskad_gcn_bwd_params_ws_bytes(T, V)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     if accumulate and (dA is None or dT is None):
         raise ValueError("gcn_bwd_params_dx: accumulate needs the dA and dT to add to")
@@ -1392,8 +1279,7 @@ def gcn_bwd_params_dx(x: Tensor, dZ: Tensor, A: Tensor, Tm: Tensor, add: Optiona
     dT = torch.empty_like(Tm) if dT is None else dT
     _chk(dA, "dA", (T, V, V)); _chk(dT, "dT", (V, T, T))
     dX = torch.empty_like(x)
-    call("coskad_gcn_bwd_params_dx_f32", ptr(x), ptr(dZ), ptr(A), ptr(Tm), ptr(dA), ptr(dT), ptr(dX), ptr(add), ptr(ws),
-         ctypes.c_size_t(nbytes), i32(1 if accumulate else 0), i32(N * C), i32(T), i32(V), _stream())
+    call("coskad_gcn_bwd_params_dx_f32", x, dZ, A, Tm, dA, dT, dX, add, ws, nbytes, 1 if accumulate else 0, N * C, T, V, _stream())
     return dA, dT, dX
 
 
@@ -1402,9 +1288,7 @@ def adam_dev(p, g, m, v, mask, hyper, beta1, beta2, eps, gscale=1.0, reg_coef=0.
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _chk(t, n, p.shape)
     _chk(mask, "mask", p.shape, optional=True); _chk(hyper, "hyper", (4,))
-    call("coskad_adam_dev_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(mask), ctypes.c_size_t(p.numel()), ptr(hyper),
-         ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_float(gscale),
-         ctypes.c_float(reg_coef), _stream())
+    call("coskad_adam_dev_f32", p, g, m, v, mask, p.numel(), hyper, beta1, beta2, eps, gscale, reg_coef, _stream())
 
 
 def gather_transform(xy, mats, index, T, V):
@@ -1414,6 +1298,5 @@ def gather_transform(xy, mats, index, T, V):
     _chk(xy, "xy", (N, 2, T * V)); _chk(mats, "mats", (mats.shape[0], 3, 3)); _chk(index, "index", dtype=torch.int64)
     B = index.numel()
     out = torch.empty(B, 2, T, V, device=xy.device, dtype=torch.float32)
-    call("coskad_gather_transform_f32", ptr(xy), ptr(index), ptr(mats), ptr(out), i32(B), i32(N), i32(mats.shape[0]),
-         i32(T * V), _stream())
+    call("coskad_gather_transform_f32", xy, index, mats, out, B, N, mats.shape[0], T * V, _stream())
     return out
