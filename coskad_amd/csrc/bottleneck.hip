@@ -11,6 +11,7 @@
 //             lane) and uses it three ways: PReLU(U) as the B operand of dW += dz^T X, U's sign
 //             as the mask of dU = (dz W) * PReLU'(U), and U itself for the slope gradient.
 #include "tile_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 
@@ -350,12 +351,6 @@ int launch_btlnk_reduce(const float* partials, int P, size_t E, float* out, cons
 
 // btlnk_wide.hip: 16 < L <= kBtlWideMax
 constexpr int kBtlWideMax = 512;
-size_t wide_btlnk_fwd_ws_bytes(int B, int K, int L);
-size_t wide_btlnk_bwd_ws_bytes(int B, int K, int L);
-int wide_btlnk_fwd(const float* U, const float* W, const float* bias, const float* slope, float* z, void* ws, int B, int K, int L,
-                   hipStream_t stream);
-int wide_btlnk_bwd(const float* U, const float* W, const float* dz, const float* slope, float* dU, float* dW, float* db,
-                   float* dslope, void* ws, int accumulate, int B, int K, int L, hipStream_t stream);
 
 }  // namespace coskad
 

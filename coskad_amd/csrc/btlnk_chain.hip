@@ -29,6 +29,7 @@
 //   * Everything a workgroup sums (dW columns, P, Q, s, the slope gradient) stays in accumulators for the launch; one partial
 //     row / dW slab per workgroup, summed in fp64 in a fixed order by the reduce launches (deterministic, no atomics).
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace bc {
@@ -293,10 +294,6 @@ static inline size_t sums_offset(int rows, int E) { return ((size_t)rows * E + 1
 
 }  // namespace bc
 
-// bottleneck.hip
-int launch_btlnk_reduce(const float* partials, int P, size_t E, float* out, const float* dz, int B, int L, float* db,
-                        const float* dap, int nda, float* dslope, int accumulate, hipStream_t stream, const float* rows,
-                        int RP, int RE, double* rsum);
 }  // namespace coskad
 
 using namespace coskad;

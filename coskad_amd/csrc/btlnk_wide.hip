@@ -15,6 +15,7 @@
 // DX and DW stay two passes over U: fusing the dW contraction into the dU pass would hold an L x (K tile)
 // accumulator per block across the clip loop -- 512 x 128 floats = 256 registers per lane at L = 512 on top of the dU tile.
 #include "common.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace bw {
@@ -229,10 +230,6 @@ int wide_btlnk_fwd(const float* U, const float* W, const float* bias, const floa
   hipLaunchKernelGGL(bw::k_wfwd_sum, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, stream, part, bias, z, B, L, ks);
   return check_launch("btlnk_fwd_sum (wide)");
 }
-
-int launch_btlnk_reduce(const float* partials, int P, size_t E, float* out, const float* dz, int B, int L, float* db,
-                        const float* dap, int nda, float* dslope, int accumulate, hipStream_t stream, const float* rows,
-                        int RP, int RE, double* rsum);
 
 int wide_btlnk_bwd(const float* U, const float* W, const float* dz, const float* slope, float* dU, float* dW, float* db,
                    float* dslope, void* ws, int accumulate, int B, int K, int L, hipStream_t stream) {

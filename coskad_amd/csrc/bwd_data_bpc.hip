@@ -13,6 +13,7 @@
 // k_bwd_data_f keeps the clip image, both mixing tables (44 KB at 25 joints) and the coefficient matrices in LDS: one 16-wave
 // block per CU, every phase behind a block-wide barrier (385 / 273 / 171 us per call at B = 4096).
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 #ifndef BDB_SKIP   // timing-only builds (wrong results; tools/bd_phases.sh): 1 K-pass products, 2 dA (+ X halves, temporal mix), 4 spatial adjoint, 8 dT,
 #define BDB_SKIP 0 // 16 temporal adjoint, 32 row pass.  32 -> 64 at B = 4096: 145 / 66 / 53 / 66 / 26 / 7 us on a 124 us floor of streaming + barriers

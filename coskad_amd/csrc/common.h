@@ -57,14 +57,6 @@ struct ProbeScope {   // brackets ONE kernel launch with events when the probe i
   bool armed_ = false;
 };
 
-// gcn_window.hip: the mixing kernels of the window lengths 8, 16 and 24 (coskad_window_ok), behind the entry points of
-// stsgcn_fwd.hip / stsgcn_bwd.hip.  dX NULL: parameter gradients only.
-int launch_window_gcn(const float* in, float* out, const float* Aw, const float* Tw, int rows, int T, int V, int adjoint,
-                      hipStream_t st);
-int launch_window_params(const float* x, const float* dZ, const float* Aw, const float* Tw, float* dA, float* dT, void* ws,
-                         int accumulate, int rows, int T, int V, hipStream_t st, float* dX, const float* add);
-size_t window_params_ws_bytes(int T, int V);
-
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 

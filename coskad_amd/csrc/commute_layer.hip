@@ -18,16 +18,9 @@
 // the layout whose layers run unfused kernels; at 17 joints the chained kernels of fused_bwd.hip / fused_apply_next_bpc.hip already hold
 // the layer on chip and the same rewrite costs the chain more than it saves.
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
-
-// fused_apply_flat.hip: [Y; R] = [Wt; Wr] PReLU(in), Zy = gcn(Y), per-workgroup row sums of Zy, Zy^2, R, R^2
-int launch_commute_apply_mix(const float* in, float* out, const float* wt, const float* wr, const float* in_slope, const float* Aw,
-                             const float* Tw, float* zy, float* mixpart, int B, int Ci, int Jo, int TV_, hipStream_t st, int* rows_out);
-
-// fwd_moments_bpc.hip: the next layer's statistics pass with this layer's combine formed on the way in
-int launch_combine_moments_bpc(const float* Zy, const float* YR, const float* stat, float* U, const float* Aw, const float* Tw,
-                               const float* slope, float* partials, int B, int T_, int V_, float* Zout, hipStream_t st, int* rows_out);
 
 namespace cm {
 

@@ -12,6 +12,7 @@
 // 32-channel activation between them kept on chip -- 262 us against 72 + 182 for the two launches: these kernels wait on their own phase
 // chain at two waves per SIMD, not on HBM, so the saved round trip buys nothing.)  LDS: 32 rows (38.6 KB; 64 output channels: 64 rows).
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace ev {

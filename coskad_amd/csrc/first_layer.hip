@@ -14,6 +14,7 @@
 //                   the four waves split the dU rows of the clip, partial dZ meets in LDS; every thread keeps its share of
 //                   the dA / dT sums in registers for the whole launch; rows [dA][dT] as k_reduce_gcn reads them
 #include "mfma_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fl {

@@ -10,6 +10,7 @@
 // Replaces k_layer_apply_z (streaming strip GEMM, <= 32 output channels) and k_layer_apply_m (LDS tile kernel that
 // re-mixes X although Z is stored) at T = 12, V = 17, 16 / 32 input channels.
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fa {

@@ -8,6 +8,7 @@
 // barrier per k-step separates "every wave has read rows 4s.." from "rows 4s.. take the next group's quarter".
 // Built for 32 -> 64 channels at T = 12, V = 17 (layer 4 of the default stack).
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fpc {

@@ -7,6 +7,7 @@
 // 25-joint layout (T V = 300: 19 tiles, 58 KB of LDS per workgroup, two workgroups per CU), 16 / 32 input and 16 / 32 / 64
 // output channels; replaces the streaming strip GEMM (k_layer_apply_z: nothing staged, every operand fetched per strip) there.
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fpf {

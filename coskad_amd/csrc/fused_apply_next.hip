@@ -13,6 +13,7 @@
 // Replaces k_fwd_moments of layers 2..4 (a second read of every activation, block-per-tile staging and barriers) and
 // k_first_apply / k_layer_apply_ring of layers 1..3 at T = 12, V = 17, <= 32 output channels.
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 #ifndef FN_ABLATE
 #define FN_ABLATE 0   // timing-only builds (tools/bench_apply_next.py): bit 0 U rows, 1 Gram x, 2 temporal, 3 spatial, 4 Z rows, 5 Gram z, 6 GEMM
@@ -386,11 +387,6 @@ int launch_build_ftab(const float* const* A, const float* const* Tm, float* cons
   return check_launch("build_ftab");
 }
 
-// fused_apply_next_bpc.hip: one clip per workgroup for the three layer shapes of the default stack
-int apply_next_bpc_rows(int B);
-int launch_layer_apply_next_bpc(const float* Z, const float* in, float* out, const float* wfold, const float* bias,
-                                const float* in_slope, const float* out_slope, const float* ftab, float* Znext, float* partials,
-                                int B, int Ci, int Co, hipStream_t st);
 // (the three layer shapes of the default stack: 78 / 76 / 108 us against 87 / 86 / 116 us of the wave-per-clip kernel below,
 // B = 4096 on one box; the train step 1.572 -> 1.539 ms)
 static bool apply_next_bpc_on(int Ci, int Co) { return (Ci == 2 && Co == 32) || (Ci == 32 && Co == 16) || (Ci == 16 && Co == 32); }

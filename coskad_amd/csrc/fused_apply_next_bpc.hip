@@ -12,6 +12,7 @@
 //   spatial mix   frames round-robin (likewise)
 // with a workgroup barrier between the phases (six per clip + one per k-step).
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fnb {

@@ -28,6 +28,7 @@
 // L2-resident (COSKAD_HOT) the kernel loses 45 us: the fp32 MFMA issue of its ~550 products per wave and clip is half its time.
 // Per-workgroup partial sums of dA / dT live in the workspace (summed in a fixed order by k_reduce_fused: deterministic).
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fb {
@@ -43,7 +44,7 @@ using namespace ff;
 constexpr int PR_A = 0, PR_XA = 12, PR_XB = 13, PR_C = 14, PR_T = 15, PR_N = 32, EROW = PR_N * 256;
 // dA, dT (+)= sum over the P lane-major partial rows (fp64, fixed order); one extra block sums the slope partials; blocks beyond
 // that one sum the partial rows the data kernel wrote for the layer below (backward chain: brows [bP][bE] -> bout [bE], the
-// k_reduce_partials_d of that layer's call riding in this launch)
+// k_reduce_partials of that layer's call riding in this launch)
 constexpr int RE = 32;   // columns per block of k_reduce_fused: 1024 / RE row slices (256 + 66 blocks at the default stack's widths)
 __global__ __launch_bounds__(1024) void k_reduce_fused(const float* __restrict__ partials, int P, float* __restrict__ dA,
                                                        float* __restrict__ dT, const float* __restrict__ dap, int ndap,

@@ -11,6 +11,7 @@
 // accumulator registers; the four waves of a block add theirs into one [P][Q][s] row at the very end (fixed order).
 // Replaces k_bwd_reduce_z (block-per-tile: LDS images + a block barrier per 68-position slab) for these shapes.
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fs {

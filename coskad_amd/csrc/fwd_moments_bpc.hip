@@ -9,6 +9,7 @@
 // `ds_read_b64` products of fused_apply_next_bpc.hip over flat positions, their 38 double k-steps dealt to the waves; the next
 // clip's rows travel in registers.  One partial row [MX][sumX][MZ][sumZ] per workgroup (k_reduce_partials + k_train_fold finish).
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace fm {

@@ -11,6 +11,7 @@
 // multiplies), and every wave owns its sums from the first tile to the last: no combine, each wave writes its own part of the
 // workgroup's partial row ([dA | dT], summed by k_reduce_gcn in a fixed order).  168 us per call.
 #include "fused_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace gp {

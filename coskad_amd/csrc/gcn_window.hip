@@ -21,6 +21,7 @@
 // kernel sums the rows per column in fp64 in a fixed order (common.h: column_sum_f64).
 #include "common.h"
 #include "mfma_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace {

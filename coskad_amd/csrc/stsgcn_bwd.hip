@@ -23,7 +23,7 @@
 //                    (GEMMs with K = rows (clip,channel) -> MFMA f32).
 #include "mfma_ops.h"
 #include "fused_ops.h"
-#include <cstdlib>
+#include "layer_launch.h"
 
 namespace coskad {
 
@@ -248,15 +248,6 @@ __global__ __launch_bounds__((Geo<T, V>::Block), (Geo<T, V>::Block <= 512 && NTO
   store_outer<NTO, NTC>(pacc, scratch, dst, Ci, Co, Ci);
   store_outer<NTO, NTC>(qacc, scratch, dst + Co * Ci, Ci, Co, Ci);
   store_rowsums<NTO>(srow, scratch, dst + 2 * Co * Ci, Co);
-}
-
-constexpr int kRedCols = 16;   // columns per block of the partial-row sums (common.h: column_sum_f64)
-__global__ __launch_bounds__(1024) void k_reduce_partials_d(const float* __restrict__ partials, int P, int E,
-                                                             double* __restrict__ out) {
-  __shared__ double sh[1024];
-  const int e = blockIdx.x * kRedCols + (threadIdx.x % kRedCols);
-  const double t = column_sum_f64<kRedCols>(partials, P, (size_t)E, e, e < E, sh);
-  if ((int)threadIdx.x < kRedCols && e < E) out[e] = t;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1220,14 +1211,6 @@ __global__ __launch_bounds__(1024) void k_reduce_gcn(const float* __restrict__ p
   }
 }
 
-static int nb_for(int rows_per_clip, int B, int LD, int budget) {
-  int nb = rows_per_clip >= 64 ? 1 : 64 / rows_per_clip;
-  if (nb < 1) nb = 1;
-  while (nb > 1 && (size_t)nb * rows_per_clip * LD * 4 > (size_t)budget) --nb;
-  if (nb > B) nb = B;
-  return nb;
-}
-
 // workspace layout (bytes): [partials: kMaxGridBwd * Emax floats][red: Emax doubles][coef floats][da partials]
 struct BwdWs {
   float* partials;
@@ -1238,40 +1221,6 @@ struct BwdWs {
   float* dz;
 };
 
-// fused_bwd.hip
-int layer_bwd_below_rows(int T_, int V_, int B, int Ci, int Co, int below_Ci);
-int launch_layer_bwd_bpc(const float* in, const float* Zg, const float* dU, const float* coef, const float* in_slope, float* dIn,
-                         float* btab, float* partials, float* dap, int B, int Ci, int Co, hipStream_t st, int* rows_out,
-                         const float* below_z, const float* below_x, const float* below_slope, int below_Ci, float* below_stats);
-bool layer_bwd_fused_ok(int T_, int V_, int Ci, int Co);
-// fused_stats.hip
-bool bwd_stats_ring_ok(int T_, int V_, int Ci, int Co);
-int launch_bwd_stats_ring(const float* in, const float* Zg, const float* dU, const float* in_slope, float* partials, int B,
-                          int Ci, int Co, hipStream_t st, int* rows_out);
-bool bwd_stats_bpc_ok(int T_, int V_, int Ci, int Co);
-bool bwd_stats_flat_ok(int TV_, int Ci, int Co);
-int launch_bwd_stats_flat(const float* in, const float* Zg, const float* dU, const float* in_slope, float* partials, int B,
-                          int Ci, int Co, int TV_, hipStream_t st, int* rows_out);
-int launch_bwd_stats_bpc(const float* in, const float* Zg, const float* dU, const float* in_slope, float* partials, int B,
-                         int Ci, int Co, hipStream_t st, int* rows_out);
-// bwd_data_bpc.hip
-bool bwd_data_bpc_ok(int T_, int V_, int Ci, int Co);
-int launch_bwd_data_bpc(const float* in, const float* Zg, const float* dU, const float* Aw, const float* Tw, const float* coef,
-                        const float* in_slope, float* dIn, float* dZout, float* dap, int B, int Ci, int Co, int T_, int V_,
-                        hipStream_t st, int* rows_out, float* gpart);
-// gcn_params_bpc.hip
-bool gcn_params_bpc_ok(int T_, int V_);
-int launch_gcn_params_bpc(const float* in, const float* in_slope, const float* dz, const float* Aw, const float* Tw, float* partials,
-                          int rows_total, int T_, int V_, hipStream_t st, int* rows_out);
-// first_layer.hip
-bool first_layer_ok(int T_, int V_, int Ci, int Co);
-int launch_first_stats(const float* in, const float* Zg, const float* dU, const float* in_slope, float* partials, int B, int Ci,
-                       int Co, int TVr, int need_q, int max_rows, hipStream_t st, int* rows_out);
-int launch_first_bwd(const float* in, const float* Zg, const float* dU, const float* Aw, const float* Tw, const float* coef,
-                     const float* in_slope, float* partials, int B, int Ci, int Co, int T, int V, int max_rows, hipStream_t st,
-                     int* rows_out);
-int launch_reduce_fused(const float* partials, int rows, float* dA, float* dT, const float* dap, float* dslope, int accumulate,
-                        hipStream_t st, const float* brows, int bE, double* bout);
 // chain buffer of a layer's stage-1 sums: [rows][E] partial rows, then (8-byte aligned) their E fp64 sums
 static inline size_t chain_sums_offset(int rows, int E) { return ((size_t)rows * E + 1) / 2 * 2; }
 constexpr size_t kFusedRowFloats = 32 * 256;   // lane-major partial row of fused_bwd.hip (fb::EROW)
@@ -1305,30 +1254,38 @@ static BwdWs carve(void* ws, int B, int Ci, int Co, int T, int V) {
   return w;
 }
 
+#ifdef COSKAD_ABLATE   // the phase-ablation builds' kernels take one more argument, the phase switch (tools/ablate_bwd.py)
+#define ABL_ARG(x) , x
+#else
+#define ABL_ARG(x)
+#endif
+
 // Stage 4 of the layer backward: dA, dT from the layer input (pre-activation + producer slope) and the stored dZ.
-// partials: >= min(512, tiles) * (T*V*V + V*T*T) floats.
+// partials: >= min(512, tiles) * (T*V*V + V*T*T) floats.  dap (optional): `ndap` block partials of the producer's slope gradient,
+// summed into a.g.dslope_in by one more block of the reduction.  a.Co only tags the probe (0 from the entry point of its own).
 template <int T, int V>
-static int launch_layer_gcn_params(const float* in, const float* in_slope, const float* dz, const float* Aw,
-                                   const float* Tw, float* dA, float* dT, float* partials, int accumulate, int B,
-                                   int Ci, int Co_tag, hipStream_t st, const float* dap = nullptr, int ndap = 0,
-                                   float* dslope = nullptr) {
+static int launch_layer_gcn_params(const LayerBwdArgs& a, const float* dz, float* partials, const float* dap, int ndap) {
   constexpr int kBlock = Geo<T, V>::Block;   // threads per block of this geometry
   constexpr int LD = Geo<T, V>::LD;
   const int E = T * V * V + V * T * T;
+  hipStream_t st = a.stream;
+  auto reduce = [&](int rows) {
+    hipLaunchKernelGGL(k_reduce_gcn, dim3(ceil_div(E, kGcnCols) + (dap ? 1 : 0)), dim3(1024), 0, st, partials, rows, T * V * V,
+                       V * T * T, a.g.dA, a.g.dT, dap, ndap, a.g.dslope_in, a.accumulate);
+    return check_launch("bwd_gcn_reduce");
+  };
   // Both products sum over rows = (clip, channel) and the mixing is per row, so a tile is ANY run of consecutive rows
   // of the [B*C_in, T*V] matrix: 16-row tiles (one MFMA row tile) keep two images + tables under a third of the LDS
   // -> three blocks per CU.  The kernel is told "C_in = 1, B = rows".
-  const int rows_total = B * Ci;
+  const int rows_total = a.B * a.Ci;
   if (gcn_params_bpc_ok(T, V)) {
     // the 25-joint layout: one 32-row tile per four-wave workgroup, the tables as operands from L2 (gcn_params_bpc.hip)
     int rows_p = 0, rc_;
     {
-      ProbeScope probe(KID_GCN_PARAMS, Ci, Co_tag, st);
-      if ((rc_ = launch_gcn_params_bpc(in, in_slope, dz, Aw, Tw, partials, rows_total, T, V, st, &rows_p))) return rc_;
+      ProbeScope probe(KID_GCN_PARAMS, a.Ci, a.Co, st);
+      if ((rc_ = launch_gcn_params_bpc(a.in, a.in_slope, dz, a.A, a.Tm, partials, rows_total, T, V, st, &rows_p))) return rc_;
     }
-    hipLaunchKernelGGL(k_reduce_gcn, dim3(ceil_div(E, kGcnCols) + (dap ? 1 : 0)), dim3(1024), 0, st, partials, rows_p, T * V * V,
-                       V * T * T, dA, dT, dap, ndap, dslope, accumulate);
-    return check_launch("bwd_gcn_reduce");
+    return reduce(rows_p);
   }
   const int rt = kBlock > 512 ? 32 : 16;       // (16-wave blocks, one per CU: twice the rows per barrier round; 3.20 -> 3.16 ms on the 25-joint step)
   const int RTILE = rows_total < rt ? rows_total : rt;
@@ -1341,303 +1298,286 @@ static int launch_layer_gcn_params(const float* in, const float* in_slope, const
   auto k = k_bwd_gcn_params<T, V>;
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   {
-    ProbeScope probe(KID_GCN_PARAMS, Ci, Co_tag, st);
-#ifdef COSKAD_ABLATE
-    static int ablg = -1;
-    if (ablg < 0) { const char* e = getenv("COSKAD_ABLG"); ablg = e ? atoi(e) : 0; }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, in, dz, Aw, Tw, in_slope, partials, rows_total, 1, NB, (float*)nullptr,
-                       (const float*)nullptr, ablg);
-#else
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, in, dz, Aw, Tw, in_slope, partials, rows_total, 1, NB, (float*)nullptr,
-                       (const float*)nullptr);
-#endif
+    ProbeScope probe(KID_GCN_PARAMS, a.Ci, a.Co, st);
+    static const int ablg = ablate_env("COSKAD_ABLG", 0);
+    (void)ablg;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, a.in, dz, a.A, a.Tm, a.in_slope, partials, rows_total, 1, NB, (float*)nullptr,
+                       (const float*)nullptr ABL_ARG(ablg));
   }
   int rc;
   if ((rc = check_launch("bwd_gcn_params"))) return rc;
-  hipLaunchKernelGGL(k_reduce_gcn, dim3(ceil_div(E, kGcnCols) + (dap ? 1 : 0)), dim3(1024), 0, st, partials, grid, T * V * V,
-                     V * T * T, dA, dT, dap, ndap, dslope, accumulate);
+  return reduce(grid);
+}
+
+// ---- stage 1: the batch reductions P = sum dU.Z^T, Q = sum dU.X^T, sdU as partial rows -------------------------------------------
+// LDS floats of the two tile kernels of this file for nb clips per tile
+template <int T, int V>
+static size_t red_z_lds(const LayerBwdArgs& a, int nb) {   // k_bwd_reduce_z: X (+ Z) and a dU chunk resident, no mixing tables
+  size_t img = (size_t)(a.Wr ? 2 : 1) * nb * a.Ci * RedGeo<T, V>::LDZ + (size_t)nb * a.Co * RedGeo<T, V>::LDCZ;
+  if (img < (size_t)Geo<T, V>::Scratch) img = Geo<T, V>::Scratch;
+  return img * sizeof(float);
+}
+template <int T, int V>
+static size_t red_lds(const LayerBwdArgs& a, int nb) {     // k_bwd_reduce: the X image, a dU chunk and both mixing tables
+  size_t img = (size_t)nb * a.Ci * Geo<T, V>::LD + (size_t)nb * a.Co * RedGeo<T, V>::LDC;
+  if (img < (size_t)Geo<T, V>::Scratch) img = Geo<T, V>::Scratch;
+  return (img + (size_t)T * V * V + (size_t)V * T * T) * sizeof(float);
+}
+
+// what both tile kernels share: clips per tile under the LDS cap that lets `per CU` blocks stay resident, and the persistent grid
+struct RedPlan {
+  int NB, grid;
+  size_t lds;
+};
+template <class LdsOf>
+static RedPlan plan_reduce(const LayerBwdArgs& a, int kBlock, LdsOf lds_of) {
+  // blocks per CU: three when the accumulators are small enough for 6 waves/SIMD and the images fit a third of
+  // the LDS (fewer clips per tile if need be), else two  (16-wave blocks: at most two per CU)
+  const bool three = ceil_div(a.Co, 16) * ceil_div(a.Ci, 16) <= 2 && kBlock <= 512;
+  const size_t cap = three ? (size_t)52 * 1024 : (size_t)76 * 1024;   // (LDS is allocated in coarse granules)
+  RedPlan p;
+  p.NB = a.Ci >= 32 ? 1 : 32 / a.Ci;
+  if (p.NB > a.B) p.NB = a.B;
+  while (p.NB > 1 && lds_of(p.NB) > cap) --p.NB;
+  p.lds = lds_of(p.NB);
+  p.grid = 256 * ((three && p.lds <= cap) ? 3 : (p.lds <= (size_t)80 * 1024 ? 2 : 1));
+  const int ntiles = ceil_div(a.B, p.NB);
+  if (p.grid > ntiles) p.grid = ntiles;
+  return p;
+}
+
+// the stored-Z tile kernel: one dU pass with X and Z both resident.  Returns the rows written (< 0: an error)
+template <int T, int V>
+static int stage1_tile_z(const LayerBwdArgs& a, float* partials) {
+  const RedPlan p = plan_reduce(a, Geo<T, V>::Block, [&](int nb) { return red_z_lds<T, V>(a, nb); });
+  if (p.lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", p.lds);
+  {
+    ProbeScope probe(KID_BWD_REDUCE, a.Ci, a.Co, a.stream);
+    with_tiles(ceil_div(a.Co, 16), [&](auto NTO) {
+      with_tiles(ceil_div(a.Ci, 16), [&](auto NTC) {
+        auto k = k_bwd_reduce_z<T, V, decltype(NTO)::value, decltype(NTC)::value>;
+        if (p.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        hipLaunchKernelGGL(k, dim3(p.grid), dim3(Geo<T, V>::Block), p.lds, a.stream, a.in, a.Z, a.dU, a.in_slope, partials, a.B, a.Ci,
+                           a.Co, p.NB, (int)(a.Wr != nullptr));
+      });
+    });
+  }
+  const int rc = check_launch("bwd_reduce_z");
+  return rc ? rc : p.grid;
+}
+
+// the two-pass tile kernel (Z recomputed, or taken as stored where one clip's X + Z images exceed the LDS: 64 input channels at 25
+// joints, the default-width decoder on the NTU layout)
+template <int T, int V>
+static int stage1_tile(const LayerBwdArgs& a, float* partials) {
+  const RedPlan p = plan_reduce(a, Geo<T, V>::Block, [&](int nb) { return red_lds<T, V>(a, nb); });
+  if (p.lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", p.lds);
+  {
+    ProbeScope probe(KID_BWD_REDUCE, a.Ci, a.Co, a.stream);
+    with_tiles(ceil_div(a.Co, 16), [&](auto NTO) {
+      with_tiles(ceil_div(a.Ci, 16), [&](auto NTC) {
+        auto k = k_bwd_reduce<T, V, decltype(NTO)::value, decltype(NTC)::value>;
+        if (p.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        hipLaunchKernelGGL(k, dim3(p.grid), dim3(Geo<T, V>::Block), p.lds, a.stream, a.in, a.dU, a.A, a.Tm, a.in_slope, partials, a.B,
+                           a.Ci, a.Co, p.NB, (int)(a.Wr != nullptr), a.Z);
+      });
+    });
+  }
+  const int rc = check_launch("bwd_reduce");
+  return rc ? rc : p.grid;
+}
+
+// stored Z, through another file's kernel where one is built for the shape.  Returns the rows written, 0 where none is built (the
+// tile kernels of this file then run), < 0 on an error
+static int stage1_elsewhere(const LayerBwdArgs& a, float* partials, int T, int V) {
+  const int need_q = a.Wr != nullptr;
+  int rows = 0, rc;
+  if (first_layer_ok(T, V, a.Ci, a.Co))
+    // a handful of input channels (the first layer): plain FMAs on full-line loads (first_layer.hip)
+    rc = launch_first_stats(a.in, a.Z, a.dU, a.in_slope, partials, a.B, a.Ci, a.Co, T * V, need_q, kMaxGridBwd, a.stream, &rows);
+  else if (bwd_stats_bpc_ok(T, V, a.Ci, a.Co))
+    // default geometry, 32 input channels and a wide output (the top layer): one clip per workgroup (fused_stats.hip)
+    rc = launch_bwd_stats_bpc(a.in, a.Z, a.dU, a.in_slope, partials, a.B, a.Ci, a.Co, a.stream, &rows);
+  else if (bwd_stats_flat_ok(T * V, a.Ci, a.Co))
+    // the 25-joint layout: the same scheme over flat positions (fused_stats.hip)
+    rc = launch_bwd_stats_flat(a.in, a.Z, a.dU, a.in_slope, partials, a.B, a.Ci, a.Co, T * V, a.stream, &rows);
+  else if (bwd_stats_ring_ok(T, V, a.Ci, a.Co))
+    // default geometry, 16 / 32 input channels: wave-per-clip reductions (fused_stats.hip)
+    rc = launch_bwd_stats_ring(a.in, a.Z, a.dU, a.in_slope, partials, a.B, a.Ci, a.Co, a.stream, &rows);
+  else
+    return 0;
+  return rc ? rc : rows;
+}
+
+// Picks the route and runs it.  Returns the partial rows written to `partials` (0: none, the sums came with the call -- they rode
+// in the reduction launch of the layer above, k_reduce_fused), < 0 on an error
+template <int T, int V>
+static int stage1_reductions(const LayerBwdArgs& a, float* partials) {
+  if (a.chain.stats) return 0;
+  if (a.Z) {
+    const int rows = stage1_elsewhere(a, partials, T, V);
+    if (rows) return rows;
+    if (red_z_lds<T, V>(a, 1) <= (size_t)kMaxLdsBytes) return stage1_tile_z<T, V>(a, partials);
+  }
+  return stage1_tile<T, V>(a, partials);
+}
+
+// the fp64 sums of stage 1's partial rows: into the workspace, or behind the rows of the caller's chain buffer (a stats-only call)
+static int sum_stage1_rows(const LayerBwdArgs& a, const BwdWs& w, int rows) {
+  const int E = 2 * a.Co * a.Ci + a.Co;
+  float* out = a.stats_only.out;
+  launch_reduce_partials(w.partials, rows, E, out ? reinterpret_cast<double*>(out + chain_sums_offset(rows, E)) : w.red, a.stream);
+  const int rc = check_launch("bwd_reduce_partials");
+  if (rc) return rc;
+  if (a.stats_only.rows_out) *a.stats_only.rows_out = rows;
+  return COSKAD_OK;
+}
+
+// ---- stage 2: the fold (parameter gradients of both branches, the coefficient matrices of stage 3) -------------------------------
+// fused: the fused data kernel's operand tables are built by extra blocks of the launch (parameter-only work)
+static int stage2_fold(const LayerBwdArgs& a, const BwdWs& w, int TV, bool fused) {
+  const int Ci = a.Ci, Co = a.Co;
+  const LayerGrads& g = a.g;
+  const size_t fold_lds = (size_t)(6 * Co + 2 * Co * Ci + Co) * sizeof(double) + (size_t)(4 * Co * Ci + 2 * Ci + 4 * Co) * sizeof(float);
+  if (fold_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_bwd_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds);
+  const int tab_blocks = fused ? ceil_div(ff::BTAB_F4 * 4, 1024) : 0;
+  const int NF = Co >= 32 ? 8 : (Co >= 16 ? 4 : 1);          // fold blocks (slices of the output channels / K pairs)
+  const double* red = a.chain.stats ? reinterpret_cast<const double*>(a.chain.stats + chain_sums_offset(a.chain.rows, 2 * Co * Ci + Co)) : w.red;
+  hipLaunchKernelGGL(k_bwd_fold, dim3(NF + tab_blocks), dim3(1024), fold_lds, a.stream, red, a.stats_count > 0.0 ? a.stats_count : (double)a.B * TV,
+                     a.stat, a.Wt, a.gt, a.Wr, a.gr, g.dWt, g.dbt, g.dgt, g.dbet, g.dWr, g.dbr, g.dgr, g.dber, w.coef, Ci, Co, a.accumulate,
+                     a.A, a.Tm, w.btab, NF);
+  return check_launch("bwd_fold");
+}
+
+// block partials of the producer's slope gradient go to the workspace where that gradient is asked for
+static float* slope_partials(const LayerBwdArgs& a, const BwdWs& w) { return (a.g.dslope_in && a.in_slope) ? w.dap : nullptr; }
+
+// ---- stages 3 + 4 in one kernel (fused_bwd.hip) for the stored-Z path at the shapes it is built for: dZ never leaves the CU -----
+static int stage34_fused(const LayerBwdArgs& a, const BwdWs& w) {
+  int rows = 0, rc;
+  float* dap = slope_partials(a, w);
+  const Below& b = a.below;
+  if ((rc = launch_layer_bwd_bpc(a.in, a.Z, a.dU, w.coef, a.in_slope, a.g.dIn, w.btab, w.partials, dap, a.B, a.Ci, a.Co, a.stream, &rows,
+                                 b.Z, b.in, b.slope, b.Ci, b.stats)))
+    return rc;
+  const int bE = 2 * a.Ci * b.Ci + a.Ci;
+  return launch_reduce_fused(w.partials, rows, a.g.dA, a.g.dT, dap, a.g.dslope_in, a.accumulate, a.stream, b.stats, bE,
+                             b.stats ? reinterpret_cast<double*>(b.stats + chain_sums_offset(rows, bE)) : nullptr);
+}
+
+// ---- the same for a handful of input channels and no input gradient (the first layer: first_layer.hip) --------------------------
+static int stage34_first(const LayerBwdArgs& a, const BwdWs& w, int T, int V) {
+  int rows = 0, rc;
+  if ((rc = launch_first_bwd(a.in, a.Z, a.dU, a.A, a.Tm, w.coef, a.in_slope, w.partials, a.B, a.Ci, a.Co, T, V, kMaxGridBwd, a.stream, &rows)))
+    return rc;
+  hipLaunchKernelGGL(k_reduce_gcn, dim3(ceil_div(T * V * V + V * T * T, kGcnCols)), dim3(1024), 0, a.stream, w.partials, rows, T * V * V,
+                     V * T * T, a.g.dA, a.g.dT, (const float*)nullptr, 0, (float*)nullptr, a.accumulate);
   return check_launch("bwd_gcn_reduce");
 }
 
-template <int T, int V>
-static int launch_layer_bwd(const float* in, const float* dU, const float* Aw, const float* Tw,
-                            const float* in_slope, const float* stat, const float* Wt, const float* gs,
-                            const float* Wr, const float* gr, float* dIn, float* dA, float* dT, float* dWt,
-                            float* dbt, float* dgs, float* dbs, float* dWr, float* dbr, float* dgr,
-                            float* dbr2, float* dslope_in, void* ws, size_t ws_bytes, int accumulate,
-                            int B, int Ci, int Co, hipStream_t st, float* dz_ext = nullptr,
-                            const float* Zg = nullptr, const float* stats_in = nullptr, int stats_in_rows = 0,
-                            const float* below_in = nullptr, const float* below_z = nullptr, const float* below_slope = nullptr,
-                            int below_Ci = 0, float* below_stats = nullptr, double stats_count = 0.0, float* stats_out = nullptr,
-                            int* stats_rows_out = nullptr) {
-  // stats_count: positions the stage-1 sums cover (0: this batch, B T V; SyncBN: all ranks' batches);
-  // stats_out: run stage 1 ONLY, into that chain buffer (partial rows, then their fp64 sums); *stats_rows_out = rows written
-  // stats_in: this layer's stage-1 partial rows, written by the call for the layer above (stage 1 is then skipped);
-  // below_*: the layer below's input / stored Z and the buffer its partial rows go to (fused data kernel only)
-  constexpr int kBlock = Geo<T, V>::Block;   // threads per block of this geometry
-  constexpr int kScratchFloats = Geo<T, V>::Scratch;
-  // dz_ext != NULL: dZ goes to the caller's buffer and stage 4 (dA, dT) is left to coskad_layer_gcn_params_f32
-  constexpr int LD = Geo<T, V>::LD, TV = Geo<T, V>::TV;
-  if (Ci > 64 || Co > 64) return fail(COSKAD_ERR_SHAPE, "layer_bwd: channels (%d,%d) > 64 not supported", Ci, Co);
-  if (ws_bytes < layer_bwd_ws_bytes(B, Ci, Co, T, V))
-    return fail(COSKAD_ERR_WORKSPACE, "layer_bwd: workspace %zu < %zu bytes", ws_bytes, layer_bwd_ws_bytes(B, Ci, Co, T, V));
-  BwdWs w = carve(ws, B, Ci, Co, T, V);
-  if (dz_ext) w.dz = dz_ext;
-  if (stats_out) w.partials = stats_out;
-  auto red_of = [&](int rows_, int E_) { return stats_out ? reinterpret_cast<double*>(stats_out + chain_sums_offset(rows_, E_)) : w.red; };
-  int rc;
-  // 1. reductions
+// ---- stage 3, the data path: dIn, dZ and the slope partials.  Both forms return the blocks of the data kernel (= slope partials
+// for stage 4's reduction), < 0 on an error ---------------------------------------------------------------------------------------
+// The 25-joint layout, stored Z: one clip per four-wave workgroup (bwd_data_bpc.hip), dA / dT in the same kernel (dZ never leaves the
+// CU): 16 -> 32 226 -> 207 us, 32 -> 64 471 -> 457 us at B = 4096 (32 channels: the dT sums in LDS, the next clip's first group no
+// longer carried -- with all 76 sum registers beside the two K-pass accumulator sets the kernel spilled 116 B per lane and ran
+// 480 us).  Returns 0 when stage 4 is done with it.  -DCOSKAD_ABLATE, COSKAD_V25_SPLIT=1: the two-kernel form with the dZ round trip
+static int stage3_data_bpc(const LayerBwdArgs& a, const BwdWs& w, int T, int V) {
+  static const bool split = ablate_env("COSKAD_V25_SPLIT", 0) == 1;
+  float* dap = slope_partials(a, w);
+  int grid_d = 0, rc;
   {
-    const int E = 2 * Co * Ci + Co;
-    int NB = Ci >= 32 ? 1 : 32 / Ci;
-    if (NB > B) NB = B;
-    auto red_lds = [&](int nb_) {
-      size_t img = (size_t)nb_ * Ci * LD + (size_t)nb_ * Co * RedGeo<T, V>::LDC;
-      if (img < (size_t)kScratchFloats) img = kScratchFloats;
-      return (img + (size_t)T * V * V + (size_t)V * T * T) * sizeof(float);
-    };
-    const int nto = ceil_div(Co, 16), ntc = ceil_div(Ci, 16);
-    const int need_q = Wr != nullptr;
-    auto zlds = [&](int nb_) {
-      size_t img = (size_t)(need_q ? 2 : 1) * nb_ * Ci * RedGeo<T, V>::LDZ + (size_t)nb_ * Co * RedGeo<T, V>::LDCZ;
-      if (img < (size_t)kScratchFloats) img = kScratchFloats;
-      return img * sizeof(float);
-    };
-    // stored Z: one dU pass with X and Z both resident, no mixing tables in LDS.  When one clip's X + Z images exceed
-    // the LDS (64 input channels at 25 joints: the default-width decoder on the NTU layout) the two-pass kernel below
-    // runs instead; it takes the stored Z as well.
-    if (stats_in) {
-      // summed already: the partial rows rode in the reduction launch of the layer above (k_reduce_fused)
-    } else if (Zg && first_layer_ok(T, V, Ci, Co)) {
-      // a handful of input channels (the first layer): plain FMAs on full-line loads (first_layer.hip)
-      int rows = 0;
-      if ((rc = launch_first_stats(in, Zg, dU, in_slope, w.partials, B, Ci, Co, TV, need_q, kMaxGridBwd, st, &rows))) return rc;
-      hipLaunchKernelGGL(k_reduce_partials_d, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, w.partials, rows, E, red_of(rows, E));
-      if ((rc = check_launch("bwd_reduce_partials"))) return rc;
-      if (stats_rows_out) *stats_rows_out = rows;
-    } else if (Zg && bwd_stats_bpc_ok(T, V, Ci, Co)) {
-      // default geometry, 32 input channels and a wide output (the top layer): one clip per workgroup (fused_stats.hip)
-      int rows = 0;
-      if ((rc = launch_bwd_stats_bpc(in, Zg, dU, in_slope, w.partials, B, Ci, Co, st, &rows))) return rc;
-      hipLaunchKernelGGL(k_reduce_partials_d, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, w.partials, rows, E, red_of(rows, E));
-      if ((rc = check_launch("bwd_reduce_partials"))) return rc;
-      if (stats_rows_out) *stats_rows_out = rows;
-    } else if (Zg && bwd_stats_flat_ok(T * V, Ci, Co)) {
-      // the 25-joint layout: the same scheme over flat positions (fused_stats.hip)
-      int rows = 0;
-      if ((rc = launch_bwd_stats_flat(in, Zg, dU, in_slope, w.partials, B, Ci, Co, T * V, st, &rows))) return rc;
-      hipLaunchKernelGGL(k_reduce_partials_d, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, w.partials, rows, E, red_of(rows, E));
-      if ((rc = check_launch("bwd_reduce_partials"))) return rc;
-      if (stats_rows_out) *stats_rows_out = rows;
-    } else if (Zg && bwd_stats_ring_ok(T, V, Ci, Co)) {
-      // default geometry, 16 / 32 input channels: wave-per-clip reductions (fused_stats.hip)
-      int rows = 0;
-      if ((rc = launch_bwd_stats_ring(in, Zg, dU, in_slope, w.partials, B, Ci, Co, st, &rows))) return rc;
-      hipLaunchKernelGGL(k_reduce_partials_d, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, w.partials, rows, E, red_of(rows, E));
-      if ((rc = check_launch("bwd_reduce_partials"))) return rc;
-      if (stats_rows_out) *stats_rows_out = rows;
-    } else if (Zg && zlds(1) <= (size_t)kMaxLdsBytes) {
-      const bool three_z = nto * ntc <= 2 && kBlock <= 512;   // (16-wave blocks: at most two per CU)
-      const size_t cap = three_z ? (size_t)52 * 1024 : (size_t)76 * 1024;
-      int NBz = NB;
-      while (NBz > 1 && zlds(NBz) > cap) --NBz;
-      const size_t ldsz = zlds(NBz);
-      if (ldsz > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", ldsz);
-      const int ntl = ceil_div(B, NBz);
-      int gridz = 256 * ((three_z && ldsz <= cap) ? 3 : (ldsz <= (size_t)80 * 1024 ? 2 : 1));
-      if (gridz > ntl) gridz = ntl;
-#define LAUNCH_RZ(NTO, NTC)                                                                              \
-  do {                                                                                                  \
-    auto k = k_bwd_reduce_z<T, V, NTO, NTC>;                                                            \
-    if (ldsz > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz); \
-    hipLaunchKernelGGL(k, dim3(gridz), dim3(kBlock), ldsz, st, in, Zg, dU, in_slope, w.partials, B, Ci, Co, NBz, need_q); \
-  } while (0)
-#define LAUNCH_RZ_O(NTO)                                         \
-  do {                                                           \
-    if (ntc == 1) LAUNCH_RZ(NTO, 1);                             \
-    else if (ntc == 2) LAUNCH_RZ(NTO, 2);                        \
-    else if (ntc == 3) LAUNCH_RZ(NTO, 3);                        \
-    else LAUNCH_RZ(NTO, 4);                                      \
-  } while (0)
-      {
-        ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
-        if (nto == 1) LAUNCH_RZ_O(1);
-        else if (nto == 2) LAUNCH_RZ_O(2);
-        else if (nto == 3) LAUNCH_RZ_O(3);
-        else LAUNCH_RZ_O(4);
-      }
-#undef LAUNCH_RZ_O
-#undef LAUNCH_RZ
-      if ((rc = check_launch("bwd_reduce_z"))) return rc;
-      hipLaunchKernelGGL(k_reduce_partials_d, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, w.partials, gridz, E, red_of(gridz, E));
-      if ((rc = check_launch("bwd_reduce_partials"))) return rc;
-      if (stats_rows_out) *stats_rows_out = gridz;
-    } else {
-    // blocks per CU: three when the accumulators are small enough for 6 waves/SIMD and the images fit a third of
-    // the LDS (fewer clips per tile if need be), else two
-    const bool three = nto * ntc <= 2 && kBlock <= 512;
-    const size_t lds_cap = three ? (size_t)52 * 1024 : (size_t)76 * 1024;   // (LDS is allocated in coarse granules)
-    while (NB > 1 && red_lds(NB) > lds_cap) --NB;
-    const size_t lds = red_lds(NB);
-    if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", lds);
-    const int ntiles = ceil_div(B, NB);
-    int grid = 256 * ((three && lds <= lds_cap) ? 3 : (lds <= (size_t)80 * 1024 ? 2 : 1));
-    if (grid > ntiles) grid = ntiles;
-#define LAUNCH_R(NTO, NTC)                                                                              \
-  do {                                                                                                  \
-    auto k = k_bwd_reduce<T, V, NTO, NTC>;                                                              \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, in, dU, Aw, Tw, in_slope, w.partials, B,    \
-                       Ci, Co, NB, need_q, Zg);                                                         \
-  } while (0)
-#define LAUNCH_R_O(NTO)                                          \
-  do {                                                           \
-    if (ntc == 1) LAUNCH_R(NTO, 1);                              \
-    else if (ntc == 2) LAUNCH_R(NTO, 2);                         \
-    else if (ntc == 3) LAUNCH_R(NTO, 3);                         \
-    else LAUNCH_R(NTO, 4);                                       \
-  } while (0)
-    {
-    ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
-    if (nto == 1) LAUNCH_R_O(1);
-    else if (nto == 2) LAUNCH_R_O(2);
-    else if (nto == 3) LAUNCH_R_O(3);
-    else LAUNCH_R_O(4);
-    }
-#undef LAUNCH_R_O
-#undef LAUNCH_R
-    if ((rc = check_launch("bwd_reduce"))) return rc;
-    hipLaunchKernelGGL(k_reduce_partials_d, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, w.partials, grid, E, red_of(grid, E));
-    if ((rc = check_launch("bwd_reduce_partials"))) return rc;
-    if (stats_rows_out) *stats_rows_out = grid;
-    }
-  }
-  if (stats_out) return 0;
-  // 2. fold
-  const size_t fold_lds = (size_t)(6 * Co + 2 * Co * Ci + Co) * sizeof(double) + (size_t)(4 * Co * Ci + 2 * Ci + 4 * Co) * sizeof(float);
-  if (fold_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_bwd_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds);
-  const bool fused = Zg && dIn && in_slope && !dz_ext && layer_bwd_fused_ok(T, V, Ci, Co);
-  if (below_stats && !fused) return fail(COSKAD_ERR_SHAPE, "layer_bwd_chain: the layer below's reductions need the fused data kernel");
-  // the fused data kernel's operand tables are built by extra blocks of the fold launch (parameter-only work)
-  const int tab_blocks = fused ? ceil_div(ff::BTAB_F4 * 4, 1024) : 0;
-  const int NF = Co >= 32 ? 8 : (Co >= 16 ? 4 : 1);          // fold blocks (slices of the output channels / K pairs)
-  const double* red = stats_in ? reinterpret_cast<const double*>(stats_in + chain_sums_offset(stats_in_rows, 2 * Co * Ci + Co)) : w.red;
-  hipLaunchKernelGGL(k_bwd_fold, dim3(NF + tab_blocks), dim3(1024), fold_lds, st, red, stats_count > 0.0 ? stats_count : (double)B * TV, stat,
-                     Wt, gs, Wr, gr, dWt, dbt, dgs, dbs, dWr, dbr, dgr, dbr2, w.coef, Ci, Co, accumulate, Aw, Tw, w.btab, NF);
-  if ((rc = check_launch("bwd_fold"))) return rc;
-  // 3 + 4 in one kernel (fused_bwd.hip) for the stored-Z path at the shapes it is built for: dZ never leaves the CU
-  if (fused) {
-    int rows = 0;
-    float* dap = (dslope_in && in_slope) ? w.dap : nullptr;
-    if ((rc = launch_layer_bwd_bpc(in, Zg, dU, w.coef, in_slope, dIn, w.btab, w.partials, dap, B, Ci, Co, st, &rows, below_z, below_in,
-                                   below_slope, below_Ci, below_stats)))
+    ProbeScope probe(KID_BWD_DATA, a.Ci, a.Co, a.stream);
+    if ((rc = launch_bwd_data_bpc(a.in, a.Z, a.dU, a.A, a.Tm, w.coef, a.in_slope, a.g.dIn, w.dz, dap, a.B, a.Ci, a.Co, T, V, a.stream, &grid_d,
+                                  split ? nullptr : w.partials)))
       return rc;
-    const int bE = 2 * Ci * below_Ci + Ci;
-    return launch_reduce_fused(w.partials, rows, dA, dT, dap, dslope_in, accumulate, st, below_stats, bE,
-                               below_stats ? reinterpret_cast<double*>(below_stats + chain_sums_offset(rows, bE)) : nullptr);
   }
-  if (Zg && !dIn && !dz_ext && first_layer_ok(T, V, Ci, Co)) {
-    int rows = 0;
-    if ((rc = launch_first_bwd(in, Zg, dU, Aw, Tw, w.coef, in_slope, w.partials, B, Ci, Co, T, V, kMaxGridBwd, st, &rows))) return rc;
-    hipLaunchKernelGGL(k_reduce_gcn, dim3(ceil_div(T * V * V + V * T * T, kGcnCols)), dim3(1024), 0, st, w.partials, rows, T * V * V,
-                       V * T * T, dA, dT, (const float*)nullptr, 0, (float*)nullptr, accumulate);
-    return check_launch("bwd_gcn_reduce");
-  }
-  // 3. data path
-  int grid_d;
-  const float* dap_sum = nullptr;   // block partials of the producer's slope gradient (summed by stage 4's reduce)
-  if (Zg && dIn && !dz_ext && bwd_data_bpc_ok(T, V, Ci, Co)) {
-    // the 25-joint layout, stored Z: one clip per four-wave workgroup (bwd_data_bpc.hip)
-    // dA / dT in the same kernel (dZ never leaves the CU): 16 -> 32 226 -> 207 us, 32 -> 64 471 -> 457 us at B = 4096 (32 channels: the dT
-    // sums in LDS, the next clip's first group no longer carried -- with all 76 sum registers beside the two K-pass accumulator sets the
-    // kernel spilled 116 B per lane and ran 480 us).  COSKAD_V25_SPLIT=1: the two-kernel form with the dZ round trip (A/B)
-    static const int force = [] { const char* e = getenv("COSKAD_V25_SPLIT"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-    const bool split = force == 1;
-    float* dap = (dslope_in && in_slope) ? w.dap : nullptr;
-    {
-      ProbeScope probe(KID_BWD_DATA, Ci, Co, st);
-      if ((rc = launch_bwd_data_bpc(in, Zg, dU, Aw, Tw, w.coef, in_slope, dIn, w.dz, dap, B, Ci, Co, T, V, st, &grid_d,
-                                    split ? nullptr : w.partials)))
-        return rc;
-    }
-    if (!split) {
-      hipLaunchKernelGGL(k_reduce_gcn, dim3(ceil_div(T * V * V + V * T * T, kGcnCols) + (dap ? 1 : 0)), dim3(1024), 0, st, w.partials, grid_d,
-                         T * V * V, V * T * T, dA, dT, dap, grid_d, dslope_in, accumulate);
-      return check_launch("bwd_gcn_reduce");
-    }
-    dap_sum = dap;
-  } else {
-    int NB = Ci >= 32 ? 1 : 32 / Ci;
-    if (NB > B && !(Ci == 16 && dIn != nullptr)) NB = B;   // (the two-clip single-read kernel keeps its 32-row image)
-    const int CiP = round_up(Ci, 16), KZ = round_up(Ci, 4), K1 = round_up(Co, 4);
-    const size_t lds = ((size_t)NB * Ci * LD + (size_t)T * V * V + (size_t)V * T * T + 2 * (size_t)(KZ + K1) * CiP +
-                        2 * CiP) * sizeof(float);
-    if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", lds);
-    const int ntl = ceil_div(B, NB);
-    const int per_cu = (int)((size_t)kMaxLdsBytes / lds);
-    grid_d = 256 * (per_cu < 1 ? 1 : (per_cu > 2048 / kBlock ? 2048 / kBlock : per_cu));   // (a CU holds 32 waves)
-    if (grid_d > ntl) grid_d = ntl;
-    float* dap = (dslope_in && in_slope) ? w.dap : nullptr;
-#define LAUNCH_D(OTI)                                                                                   \
-  do {                                                                                                  \
-    auto k = k_bwd_data<T, V, OTI>;                                                                     \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid_d), dim3(kBlock), lds, st, in, dU, Aw, Tw, w.coef, in_slope, dIn,    \
-                       w.dz, dap, B, Ci, Co, NB, Zg);                                                   \
-  } while (0)
-#ifdef COSKAD_ABLATE
-    static int abl = -1;
-    if (abl < 0) { const char* e = getenv("COSKAD_ABL"); abl = e ? atoi(e) : 0; }
-#define ABL_ARG , abl
-#else
-#define ABL_ARG
-#endif
-#define LAUNCH_DF(OTI, NBF_)                                                                                  \
-  do {                                                                                                  \
-    auto k = k_bwd_data_f<T, V, OTI, NBF_>;                                                             \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid_d), dim3(kBlock), lds, st, in, dU, Aw, Tw, w.coef, in_slope, dIn,    \
-                       w.dz, dap, B, Ci, Co, Zg ABL_ARG);                                               \
-  } while (0)
-#ifdef COSKAD_ABLATE
-    static int fused_ok = -1;
-    if (fused_ok < 0) { const char* e = getenv("COSKAD_BWD_UNFUSED"); fused_ok = (e && e[0] == '1') ? 0 : 1; }
-#else
-    constexpr int fused_ok = 1;
-#endif
-    constexpr bool strips_fit = (Geo<T, V>::TV + 31) / 32 <= kBlock / 64;
-    // single-read variant: tiles of 32 rows = one clip of >= 32 channels, or two clips of exactly 16
-    const bool two_clip = Ci == 16;            // NB was kept at 2 above
-    if (fused_ok && strips_fit && (NB == 1 || two_clip) && dIn != nullptr && CiP <= 64) {
-      ProbeScope probe(KID_BWD_DATA, Ci, Co, st);
-      if constexpr (strips_fit) {
-        if (two_clip) LAUNCH_DF(1, 2);
-        else if (CiP == 16) LAUNCH_DF(1, 1);   // (one clip of < 16 channels: only when the batch is a single clip)
-        else if (CiP == 32) LAUNCH_DF(2, 1);
-        else if (CiP == 48) LAUNCH_DF(3, 1);
-        else LAUNCH_DF(4, 1);
-      }
-    } else
-    {
+  if (split) return grid_d;
+  hipLaunchKernelGGL(k_reduce_gcn, dim3(ceil_div(T * V * V + V * T * T, kGcnCols) + (dap ? 1 : 0)), dim3(1024), 0, a.stream, w.partials, grid_d,
+                     T * V * V, V * T * T, a.g.dA, a.g.dT, dap, grid_d, a.g.dslope_in, a.accumulate);
+  return check_launch("bwd_gcn_reduce");
+}
+
+// the tile kernels of this file
+template <int T, int V>
+static int stage3_data_tile(const LayerBwdArgs& a, const BwdWs& w) {
+  constexpr int kBlock = Geo<T, V>::Block;   // threads per block of this geometry
+  constexpr int LD = Geo<T, V>::LD;
+  const int B = a.B, Ci = a.Ci, Co = a.Co;
+  float* dIn = a.g.dIn;
+  hipStream_t st = a.stream;
+  int NB = Ci >= 32 ? 1 : 32 / Ci;
+  if (NB > B && !(Ci == 16 && dIn != nullptr)) NB = B;   // (the two-clip single-read kernel keeps its 32-row image)
+  const int CiP = round_up(Ci, 16), KZ = round_up(Ci, 4), K1 = round_up(Co, 4);
+  const size_t lds = ((size_t)NB * Ci * LD + (size_t)T * V * V + (size_t)V * T * T + 2 * (size_t)(KZ + K1) * CiP +
+                      2 * CiP) * sizeof(float);
+  if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", lds);
+  const int ntl = ceil_div(B, NB);
+  const int per_cu = (int)((size_t)kMaxLdsBytes / lds);
+  int grid_d = 256 * (per_cu < 1 ? 1 : (per_cu > 2048 / kBlock ? 2048 / kBlock : per_cu));   // (a CU holds 32 waves)
+  if (grid_d > ntl) grid_d = ntl;
+  float* dap = slope_partials(a, w);
+  static const int abl = ablate_env("COSKAD_ABL", 0);
+  static const bool fused_ok = ablate_env("COSKAD_BWD_UNFUSED", 0) != 1;
+  (void)abl;
+  constexpr bool strips_fit = (Geo<T, V>::TV + 31) / 32 <= kBlock / 64;
+  // single-read variant: tiles of 32 rows = one clip of >= 32 channels, or two clips of exactly 16
+  const bool two_clip = Ci == 16;            // NB was kept at 2 above
+  {
     ProbeScope probe(KID_BWD_DATA, Ci, Co, st);
-    if (CiP == 16) LAUNCH_D(1);
-    else if (CiP == 32) LAUNCH_D(2);
-    else if (CiP == 48) LAUNCH_D(3);
-    else LAUNCH_D(4);
+    if (fused_ok && strips_fit && (NB == 1 || two_clip) && dIn != nullptr && CiP <= 64) {
+      if constexpr (strips_fit) {
+        auto launch_f = [&](auto OTI, auto NBF) {
+          auto k = k_bwd_data_f<T, V, decltype(OTI)::value, decltype(NBF)::value>;
+          if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          hipLaunchKernelGGL(k, dim3(grid_d), dim3(kBlock), lds, st, a.in, a.dU, a.A, a.Tm, w.coef, a.in_slope, dIn, w.dz, dap, B, Ci, Co,
+                             a.Z ABL_ARG(abl));
+        };
+        if (two_clip) launch_f(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
+        else   // (one clip of < 16 channels: only when the batch is a single clip)
+          with_tiles(CiP / 16, [&](auto OTI) { launch_f(OTI, std::integral_constant<int, 1>{}); });
+      }
+    } else {
+      with_tiles(CiP / 16, [&](auto OTI) {
+        auto k = k_bwd_data<T, V, decltype(OTI)::value>;
+        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k, dim3(grid_d), dim3(kBlock), lds, st, a.in, a.dU, a.A, a.Tm, w.coef, a.in_slope, dIn, w.dz, dap, B, Ci, Co, NB,
+                           a.Z);
+      });
     }
-#undef LAUNCH_D
-    if ((rc = check_launch("bwd_data"))) return rc;
-    if (dap && dz_ext) {   // split call: stage 4 is not ours, finish the slope gradient here
-      hipLaunchKernelGGL(k_sum_to, dim3(1), dim3(256), 0, st, dap, grid_d, dslope_in, accumulate);
-      if ((rc = check_launch("bwd_dslope"))) return rc;
-    }
-    dap_sum = dap;
   }
-  // 4. gcn parameter gradients
-  if (!dz_ext)
-    return launch_layer_gcn_params<T, V>(in, in_slope, w.dz, Aw, Tw, dA, dT, w.partials, accumulate, B, Ci, Co, st,
-                                         dap_sum, grid_d, dslope_in);
-  return COSKAD_OK;
+  int rc;
+  if ((rc = check_launch("bwd_data"))) return rc;
+  if (dap && a.dz_ext) {   // split call: stage 4 is not ours, finish the slope gradient here
+    hipLaunchKernelGGL(k_sum_to, dim3(1), dim3(256), 0, st, dap, grid_d, a.g.dslope_in, a.accumulate);
+    if ((rc = check_launch("bwd_dslope"))) return rc;
+  }
+  return grid_d;
+}
+
+// ---- the driver ------------------------------------------------------------------------------------------------------------------
+template <int T, int V>
+static int launch_layer_bwd(const LayerBwdArgs& a) {
+  const int B = a.B, Ci = a.Ci, Co = a.Co;
+  if (Ci > 64 || Co > 64) return fail(COSKAD_ERR_SHAPE, "layer_bwd: channels (%d,%d) > 64 not supported", Ci, Co);
+  if (a.ws_bytes < layer_bwd_ws_bytes(B, Ci, Co, T, V))
+    return fail(COSKAD_ERR_WORKSPACE, "layer_bwd: workspace %zu < %zu bytes", a.ws_bytes, layer_bwd_ws_bytes(B, Ci, Co, T, V));
+  BwdWs w = carve(a.ws, B, Ci, Co, T, V);
+  if (a.dz_ext) w.dz = a.dz_ext;
+  if (a.stats_only.out) w.partials = a.stats_only.out;
+  int rc;
+  const int rows = stage1_reductions<T, V>(a, w.partials);
+  if (rows < 0) return rows;
+  if (rows && (rc = sum_stage1_rows(a, w, rows))) return rc;
+  if (a.stats_only.out) return COSKAD_OK;
+  const bool stored = a.Z && !a.dz_ext;   // the routes below take the stored Z and run stage 4 themselves
+  const bool fused = stored && a.g.dIn && a.in_slope && layer_bwd_fused_ok(T, V, Ci, Co);
+  if (a.below.stats && !fused) return fail(COSKAD_ERR_SHAPE, "layer_bwd_chain: the layer below's reductions need the fused data kernel");
+  if ((rc = stage2_fold(a, w, T * V, fused))) return rc;
+  if (fused) return stage34_fused(a, w);
+  if (stored && !a.g.dIn && first_layer_ok(T, V, Ci, Co)) return stage34_first(a, w, T, V);
+  const int grid_d = (stored && a.g.dIn && bwd_data_bpc_ok(T, V, Ci, Co)) ? stage3_data_bpc(a, w, T, V) : stage3_data_tile<T, V>(a, w);
+  if (grid_d <= 0 || a.dz_ext) return grid_d < 0 ? grid_d : COSKAD_OK;   // an error; stage 4 done already, or a call of its own
+  return launch_layer_gcn_params<T, V>(a, w.dz, w.partials, slope_partials(a, w), grid_d);
 }
 
 }  // namespace coskad
@@ -1657,14 +1597,49 @@ static int launch_gcn_bwd_params(const float* x, const float* dZ, const float* A
   float* partials = reinterpret_cast<float*>(ws);
   auto k = k_bwd_gcn_params<T, V>;
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#ifdef COSKAD_ABLATE
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, x, dZ, Aw, Tw, (const float*)nullptr, partials, rows, 1, NB, dX, dX_add, 0);
-#else
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, x, dZ, Aw, Tw, (const float*)nullptr, partials, rows, 1, NB, dX, dX_add);
-#endif
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, x, dZ, Aw, Tw, (const float*)nullptr, partials, rows, 1, NB, dX, dX_add ABL_ARG(0));
   hipLaunchKernelGGL(k_reduce_to_f32, dim3(ceil_div(T * V * V, 64)), dim3(1024), 0, st, partials, grid, E, 0, T * V * V, dA, accumulate);
   hipLaunchKernelGGL(k_reduce_to_f32, dim3(ceil_div(V * T * T, 64)), dim3(1024), 0, st, partials, grid, E, T * V * V, V * T * T, dT, accumulate);
   return check_launch("gcn_bwd_params");
+}
+
+// ---- what the layer entry points share: the argument checks (messages under the entry's own name) and the (T, V) dispatch ---------
+enum : unsigned {
+  kNeedDU = 1,         // dU
+  kNeedFold = 2,       // the stat block, the main branch and its gradients; a residual weight comes with its BatchNorm and gradients
+  kNeedGcnGrads = 4,   // dA, dT
+  kNeedDz = 8,         // the caller's dZ buffer
+  kNeedZ = 16,         // the stored Z
+  kNeedStatsOut = 32,  // the chain buffer of a stats-only call and its row count
+  kNeedCo = 64,        // a layer (Ci -> Co); without it the sizes are those of stage 4 alone: B and Ci <= 64
+};
+static int check_layer_bwd(const char* who, const LayerBwdArgs& a, unsigned need) {
+  const LayerGrads& g = a.g;
+  bool null = !a.in || !a.A || !a.Tm || !a.ws;
+  if (need & kNeedDU) null = null || !a.dU;
+  if (need & kNeedFold) null = null || !a.stat || !a.Wt || !a.gt || !g.dWt || !g.dgt || !g.dbet;
+  if (need & kNeedGcnGrads) null = null || !g.dA || !g.dT;
+  if (need & kNeedDz) null = null || !a.dz_ext;
+  if (need & kNeedZ) null = null || !a.Z;
+  if (need & kNeedStatsOut) null = null || !a.stats_only.out || !a.stats_only.rows_out;
+  if (null) return fail(COSKAD_ERR_ARG, "%s: null pointer", who);
+  if (need & kNeedFold) {
+    if (a.Wr && (!a.gr || !g.dWr || !g.dgr || !g.dber)) return fail(COSKAD_ERR_ARG, "%s: residual grads missing", who);
+    if (!a.Wr && a.Ci != a.Co) return fail(COSKAD_ERR_ARG, "%s: identity residual needs Ci == Co", who);
+  }
+  if (!(need & kNeedCo)) {
+    if (a.B <= 0 || a.Ci <= 0 || a.Ci > 64) return fail(COSKAD_ERR_ARG, "%s: B=%d Ci=%d", who, a.B, a.Ci);
+  } else if (a.B <= 0 || a.Ci <= 0 || a.Co <= 0) {
+    return fail(COSKAD_ERR_ARG, "%s: B=%d Ci=%d Co=%d", who, a.B, a.Ci, a.Co);
+  }
+  return COSKAD_OK;
+}
+constexpr unsigned kNeedLayer = kNeedDU | kNeedFold | kNeedCo;   // a whole layer backward
+
+static int dispatch_layer_bwd(const LayerBwdArgs& a, int T, int V) {
+#define CALL(T_, V_) return launch_layer_bwd<T_, V_>(a)
+  COSKAD_DISPATCH_TV(T, V, CALL);
+#undef CALL
 }
 }  // namespace coskad
 
@@ -1692,8 +1667,6 @@ int coskad_layer_fits(int Ci, int Co, int T, int V) {
   const size_t cap = (size_t)kMaxLdsBytes;
   return data <= cap && red <= cap && fwd <= cap;
 }
-
-int coskad_window_ok(int T, int V);   // gcn_window.hip
 
 size_t coskad_gcn_bwd_params_ws_bytes(int T, int V) {
   if (coskad_window_ok(T, V)) return window_params_ws_bytes(T, V);   // one partial row per workgroup of its persistent grid
@@ -1730,45 +1703,32 @@ int coskad_gcn_bwd_params_dx_f32(const float* x, const float* dZ, const float* A
 #undef CALL
 }
 
-int coskad_layer_bwd_f32(const float* in, const float* dU, const float* A, const float* Tm,
-                         const float* in_slope, const float* stat, const float* Wt, const float* gamma_t,
-                         const float* Wr, const float* gamma_r, float* dIn, float* dA, float* dT, float* dWt,
-                         float* dbt, float* dgamma_t, float* dbeta_t, float* dWr, float* dbr,
-                         float* dgamma_r, float* dbeta_r, float* dslope_in, void* ws, size_t ws_bytes,
-                         int accumulate, int B, int Ci, int Co, int T, int V, hipStream_t stream) {
-  if (!in || !dU || !A || !Tm || !stat || !Wt || !gamma_t || !dA || !dT || !dWt || !dgamma_t || !dbeta_t || !ws)
-    return fail(COSKAD_ERR_ARG, "layer_bwd: null pointer");
-  if (Wr && (!gamma_r || !dWr || !dgamma_r || !dbeta_r)) return fail(COSKAD_ERR_ARG, "layer_bwd: residual grads missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_bwd: identity residual needs Ci == Co");
-  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_bwd: B=%d Ci=%d Co=%d", B, Ci, Co);
-  ProbeScope layer_probe(KID_LAYER_BWD, Ci, Co, stream);   // bench.py: the whole layer backward (all its launches)
-#define CALL(T_, V_)                                                                                       \
-  return launch_layer_bwd<T_, V_>(in, dU, A, Tm, in_slope, stat, Wt, gamma_t, Wr, gamma_r, dIn, dA, dT, dWt, \
-                                  dbt, dgamma_t, dbeta_t, dWr, dbr, dgamma_r, dbeta_r, dslope_in, ws,      \
-                                  ws_bytes, accumulate, B, Ci, Co, stream)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
-}
-
-/* The same with Z = gcn(PReLU(in)) as stored by coskad_layer_train_stats_z_f32 (NULL: recompute it). */
+/* One layer's backward.  Z = gcn(PReLU(in)) as stored by coskad_layer_train_stats_z_f32 (NULL: recompute it). */
 int coskad_layer_bwd_z_f32(const float* in, const float* dU, const float* A, const float* Tm,
                          const float* in_slope, const float* stat, const float* Wt, const float* gamma_t,
                          const float* Wr, const float* gamma_r, float* dIn, float* dA, float* dT, float* dWt,
                          float* dbt, float* dgamma_t, float* dbeta_t, float* dWr, float* dbr,
                          float* dgamma_r, float* dbeta_r, float* dslope_in, void* ws, size_t ws_bytes,
                          int accumulate, int B, int Ci, int Co, int T, int V, hipStream_t stream, const float* Z) {
-  if (!in || !dU || !A || !Tm || !stat || !Wt || !gamma_t || !dA || !dT || !dWt || !dgamma_t || !dbeta_t || !ws)
-    return fail(COSKAD_ERR_ARG, "layer_bwd: null pointer");
-  if (Wr && (!gamma_r || !dWr || !dgamma_r || !dbeta_r)) return fail(COSKAD_ERR_ARG, "layer_bwd: residual grads missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_bwd: identity residual needs Ci == Co");
-  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_bwd: B=%d Ci=%d Co=%d", B, Ci, Co);
+  const LayerBwdArgs a{
+      .in = in, .dU = dU, .A = A, .Tm = Tm, .in_slope = in_slope, .stat = stat, .Wt = Wt, .gt = gamma_t, .Wr = Wr, .gr = gamma_r, .Z = Z,
+      .g = {.dIn = dIn, .dA = dA, .dT = dT, .dWt = dWt, .dbt = dbt, .dgt = dgamma_t, .dbet = dbeta_t, .dWr = dWr, .dbr = dbr,
+            .dgr = dgamma_r, .dber = dbeta_r, .dslope_in = dslope_in},
+      .ws = ws, .ws_bytes = ws_bytes, .accumulate = accumulate, .B = B, .Ci = Ci, .Co = Co, .stream = stream};
+  if (int rc = check_layer_bwd("layer_bwd", a, kNeedLayer | kNeedGcnGrads)) return rc;
   ProbeScope layer_probe(KID_LAYER_BWD, Ci, Co, stream);   // bench.py: the whole layer backward (all its launches)
-#define CALL(T_, V_)                                                                                       \
-  return launch_layer_bwd<T_, V_>(in, dU, A, Tm, in_slope, stat, Wt, gamma_t, Wr, gamma_r, dIn, dA, dT, dWt, \
-                                  dbt, dgamma_t, dbeta_t, dWr, dbr, dgamma_r, dbeta_r, dslope_in, ws,      \
-                                  ws_bytes, accumulate, B, Ci, Co, stream, nullptr, Z)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
+  return dispatch_layer_bwd(a, T, V);
+}
+
+/* The same, Z recomputed. */
+int coskad_layer_bwd_f32(const float* in, const float* dU, const float* A, const float* Tm,
+                         const float* in_slope, const float* stat, const float* Wt, const float* gamma_t,
+                         const float* Wr, const float* gamma_r, float* dIn, float* dA, float* dT, float* dWt,
+                         float* dbt, float* dgamma_t, float* dbeta_t, float* dWr, float* dbr,
+                         float* dgamma_r, float* dbeta_r, float* dslope_in, void* ws, size_t ws_bytes,
+                         int accumulate, int B, int Ci, int Co, int T, int V, hipStream_t stream) {
+  return coskad_layer_bwd_z_f32(in, dU, A, Tm, in_slope, stat, Wt, gamma_t, Wr, gamma_r, dIn, dA, dT, dWt, dbt, dgamma_t, dbeta_t, dWr,
+                                dbr, dgamma_r, dbeta_r, dslope_in, ws, ws_bytes, accumulate, B, Ci, Co, T, V, stream, nullptr);
 }
 
 /* coskad_layer_bwd_z_f32 inside a chain of layers.  The batch reductions of a layer's backward (stage 1: P = sum dU.Z^T,
@@ -1795,36 +1755,35 @@ int coskad_layer_bwd_chain_f32(const float* in, const float* dU, const float* A,
                                const float* stats_in, int stats_in_rows, size_t stats_in_bytes, const float* below_in,
                                const float* below_Z, const float* below_in_slope, int below_Ci, float* below_stats,
                                size_t below_stats_bytes, double stats_count) {
-  if (!in || !dU || !A || !Tm || !stat || !Wt || !gamma_t || !dA || !dT || !dWt || !dgamma_t || !dbeta_t || !ws || !Z)
-    return fail(COSKAD_ERR_ARG, "layer_bwd_chain: null pointer");
-  if (Wr && (!gamma_r || !dWr || !dgamma_r || !dbeta_r)) return fail(COSKAD_ERR_ARG, "layer_bwd_chain: residual grads missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_bwd_chain: identity residual needs Ci == Co");
-  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_bwd_chain: B=%d Ci=%d Co=%d", B, Ci, Co);
-  if (stats_in && stats_in_rows <= 0) return fail(COSKAD_ERR_ARG, "layer_bwd_chain: stats_in_rows=%d", stats_in_rows);
-  if (stats_in && ((size_t)stats_in & 7)) return fail(COSKAD_ERR_ARG, "layer_bwd_chain: stats_in must be 8-byte aligned");
+  const char* who = "layer_bwd_chain";
+  LayerBwdArgs a{
+      .in = in, .dU = dU, .A = A, .Tm = Tm, .in_slope = in_slope, .stat = stat, .Wt = Wt, .gt = gamma_t, .Wr = Wr, .gr = gamma_r, .Z = Z,
+      .g = {.dIn = dIn, .dA = dA, .dT = dT, .dWt = dWt, .dbt = dbt, .dgt = dgamma_t, .dbet = dbeta_t, .dWr = dWr, .dbr = dbr,
+            .dgr = dgamma_r, .dber = dbeta_r, .dslope_in = dslope_in},
+      .ws = ws, .ws_bytes = ws_bytes, .accumulate = accumulate, .B = B, .Ci = Ci, .Co = Co, .stream = stream,
+      .chain = {.stats = stats_in, .rows = stats_in_rows}, .stats_count = stats_count};
+  if (int rc = check_layer_bwd(who, a, kNeedLayer | kNeedGcnGrads | kNeedZ)) return rc;
+  if (stats_in && stats_in_rows <= 0) return fail(COSKAD_ERR_ARG, "%s: stats_in_rows=%d", who, stats_in_rows);
+  if (stats_in && ((size_t)stats_in & 7)) return fail(COSKAD_ERR_ARG, "%s: stats_in must be 8-byte aligned", who);
   if (stats_in) {   // the fold reads the fp64 sums behind the partial rows: a short buffer must not become an out-of-bounds read
     const size_t E = 2 * (size_t)Co * Ci + Co;
     const size_t need = chain_sums_offset(stats_in_rows, (int)E) * sizeof(float) + E * sizeof(double);
-    if (stats_in_bytes < need) return fail(COSKAD_ERR_WORKSPACE, "layer_bwd_chain: stats_in %zu < %zu bytes", stats_in_bytes, need);
+    if (stats_in_bytes < need) return fail(COSKAD_ERR_WORKSPACE, "%s: stats_in %zu < %zu bytes", who, stats_in_bytes, need);
   }
-  if (below_stats && ((size_t)below_stats & 7)) return fail(COSKAD_ERR_ARG, "layer_bwd_chain: below_stats must be 8-byte aligned");
+  if (below_stats && ((size_t)below_stats & 7)) return fail(COSKAD_ERR_ARG, "%s: below_stats must be 8-byte aligned", who);
   if (below_stats) {
-    if (!below_in || !below_Z) return fail(COSKAD_ERR_ARG, "layer_bwd_chain: below_in / below_Z missing");
+    if (!below_in || !below_Z) return fail(COSKAD_ERR_ARG, "%s: below_in / below_Z missing", who);
     const int rows = layer_bwd_below_rows(T, V, B, Ci, Co, below_Ci);
-    if (rows == 0) return fail(COSKAD_ERR_SHAPE, "layer_bwd_chain: (%d -> %d) cannot form the reductions of a layer with %d input channels", Ci, Co, below_Ci);
+    if (rows == 0) return fail(COSKAD_ERR_SHAPE, "%s: (%d -> %d) cannot form the reductions of a layer with %d input channels", who, Ci, Co, below_Ci);
     const int bE = 2 * Ci * below_Ci + Ci;
     const size_t need = chain_sums_offset(rows, bE) * sizeof(float) + (size_t)bE * sizeof(double);
-    if (below_stats_bytes < need) return fail(COSKAD_ERR_WORKSPACE, "layer_bwd_chain: below_stats %zu < %zu bytes", below_stats_bytes, need);
+    if (below_stats_bytes < need) return fail(COSKAD_ERR_WORKSPACE, "%s: below_stats %zu < %zu bytes", who, below_stats_bytes, need);
+    a.below = {.in = below_in, .Z = below_Z, .slope = below_in_slope, .Ci = below_Ci, .stats = below_stats};
+  } else {
+    a.below.Ci = below_Ci;
   }
   ProbeScope layer_probe(KID_LAYER_BWD, Ci, Co, stream);
-#define CALL(T_, V_)                                                                                       \
-  return launch_layer_bwd<T_, V_>(in, dU, A, Tm, in_slope, stat, Wt, gamma_t, Wr, gamma_r, dIn, dA, dT, dWt, \
-                                  dbt, dgamma_t, dbeta_t, dWr, dbr, dgamma_r, dbeta_r, dslope_in, ws,      \
-                                  ws_bytes, accumulate, B, Ci, Co, stream, nullptr, Z, stats_in, stats_in_rows, \
-                                  below_stats ? below_in : nullptr, below_stats ? below_Z : nullptr,                  \
-                                  below_stats ? below_in_slope : nullptr, below_Ci, below_stats, stats_count)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
+  return dispatch_layer_bwd(a, T, V);
 }
 
 /* Stage 1 of coskad_layer_bwd_z_f32 ALONE, into a chain buffer (SyncBN: the caller adds the other ranks' fp64 sums in place, then
@@ -1840,19 +1799,15 @@ size_t coskad_layer_bwd_sums_offset(int rows, int Ci, int Co) { return chain_sum
 int coskad_layer_bwd_stats_f32(const float* in, const float* dU, const float* A, const float* Tm, const float* in_slope,
                                int has_residual, float* stats_out, size_t stats_out_bytes, int* rows_out, void* ws, size_t ws_bytes,
                                int B, int Ci, int Co, int T, int V, hipStream_t stream, const float* Z) {
-  if (!in || !dU || !A || !Tm || !stats_out || !rows_out || !ws) return fail(COSKAD_ERR_ARG, "layer_bwd_stats: null pointer");
-  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_bwd_stats: B=%d Ci=%d Co=%d", B, Ci, Co);
+  const LayerBwdArgs a{.in = in, .dU = dU, .A = A, .Tm = Tm, .in_slope = in_slope,
+                       .Wr = has_residual ? in : nullptr,   // stage 1 only asks whether the residual branch exists
+                       .Z = Z, .ws = ws, .ws_bytes = ws_bytes, .B = B, .Ci = Ci, .Co = Co, .stream = stream,
+                       .stats_only = {.out = stats_out, .rows_out = rows_out}};
+  if (int rc = check_layer_bwd("layer_bwd_stats", a, kNeedDU | kNeedStatsOut | kNeedCo)) return rc;
   if ((size_t)stats_out & 7) return fail(COSKAD_ERR_ARG, "layer_bwd_stats: stats_out must be 8-byte aligned");
   if (stats_out_bytes < coskad_layer_bwd_stats_floats(B, Ci, Co, T, V) * sizeof(float))
     return fail(COSKAD_ERR_WORKSPACE, "layer_bwd_stats: stats_out %zu bytes too small", stats_out_bytes);
-  const float* wr_tag = has_residual ? in : nullptr;   // stage 1 only asks whether the residual branch exists
-#define CALL(T_, V_)                                                                                                      \
-  return launch_layer_bwd<T_, V_>(in, dU, A, Tm, in_slope, nullptr, nullptr, nullptr, wr_tag, nullptr, nullptr, nullptr, nullptr, \
-                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, \
-                                  0, B, Ci, Co, stream, nullptr, Z, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0.0,  \
-                                  stats_out, rows_out)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
+  return dispatch_layer_bwd(a, T, V);
 }
 
 /* Stages 1-3 of coskad_layer_bwd_f32 with dZ [B,Ci,T,V] written to the caller's buffer; stage 4 is
@@ -1863,17 +1818,13 @@ int coskad_layer_bwd_data_f32(const float* in, const float* dU, const float* A, 
                               float* dgamma_t, float* dbeta_t, float* dWr, float* dbr, float* dgamma_r,
                               float* dbeta_r, float* dslope_in, void* ws, size_t ws_bytes, int accumulate, int B,
                               int Ci, int Co, int T, int V, hipStream_t stream, const float* Z) {
-  if (!in || !dU || !A || !Tm || !stat || !Wt || !gamma_t || !dZ || !dWt || !dgamma_t || !dbeta_t || !ws)
-    return fail(COSKAD_ERR_ARG, "layer_bwd_data: null pointer");
-  if (Wr && (!gamma_r || !dWr || !dgamma_r || !dbeta_r)) return fail(COSKAD_ERR_ARG, "layer_bwd_data: residual grads missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_bwd_data: identity residual needs Ci == Co");
-  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_bwd_data: B=%d Ci=%d Co=%d", B, Ci, Co);
-#define CALL(T_, V_)                                                                                              \
-  return launch_layer_bwd<T_, V_>(in, dU, A, Tm, in_slope, stat, Wt, gamma_t, Wr, gamma_r, dIn, nullptr, nullptr, dWt, \
-                                  dbt, dgamma_t, dbeta_t, dWr, dbr, dgamma_r, dbeta_r, dslope_in, ws, ws_bytes,   \
-                                  accumulate, B, Ci, Co, stream, dZ, Z)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
+  const LayerBwdArgs a{
+      .in = in, .dU = dU, .A = A, .Tm = Tm, .in_slope = in_slope, .stat = stat, .Wt = Wt, .gt = gamma_t, .Wr = Wr, .gr = gamma_r, .Z = Z,
+      .g = {.dIn = dIn, .dWt = dWt, .dbt = dbt, .dgt = dgamma_t, .dbet = dbeta_t, .dWr = dWr, .dbr = dbr, .dgr = dgamma_r,
+            .dber = dbeta_r, .dslope_in = dslope_in},
+      .ws = ws, .ws_bytes = ws_bytes, .accumulate = accumulate, .B = B, .Ci = Ci, .Co = Co, .stream = stream, .dz_ext = dZ};
+  if (int rc = check_layer_bwd("layer_bwd_data", a, kNeedLayer | kNeedDz)) return rc;
+  return dispatch_layer_bwd(a, T, V);
 }
 
 size_t coskad_layer_gcn_params_ws_bytes(int T, int V) { return coskad_gcn_bwd_params_ws_bytes(T, V); }
@@ -1883,10 +1834,12 @@ size_t coskad_layer_gcn_params_ws_bytes(int T, int V) { return coskad_gcn_bwd_pa
 int coskad_layer_gcn_params_f32(const float* in, const float* in_slope, const float* dZ, const float* A,
                                 const float* Tm, float* dA, float* dT, void* ws, size_t ws_bytes, int accumulate,
                                 int B, int Ci, int T, int V, hipStream_t stream) {
-  if (!in || !dZ || !A || !Tm || !dA || !dT || !ws) return fail(COSKAD_ERR_ARG, "layer_gcn_params: null pointer");
-  if (B <= 0 || Ci <= 0 || Ci > 64) return fail(COSKAD_ERR_ARG, "layer_gcn_params: B=%d Ci=%d", B, Ci);
+  const LayerBwdArgs a{.in = in, .A = A, .Tm = Tm, .in_slope = in_slope, .g = {.dA = dA, .dT = dT}, .ws = ws, .ws_bytes = ws_bytes,
+                       .accumulate = accumulate, .B = B, .Ci = Ci, .stream = stream,
+                       .dz_ext = const_cast<float*>(dZ)};   // (read only: stage 4 alone)
+  if (int rc = check_layer_bwd("layer_gcn_params", a, kNeedDz | kNeedGcnGrads)) return rc;
   if (ws_bytes < coskad_layer_gcn_params_ws_bytes(T, V)) return fail(COSKAD_ERR_WORKSPACE, "layer_gcn_params: workspace too small");
-#define CALL(T_, V_) return launch_layer_gcn_params<T_, V_>(in, in_slope, dZ, A, Tm, dA, dT, reinterpret_cast<float*>(ws), accumulate, B, Ci, 0, stream)
+#define CALL(T_, V_) return launch_layer_gcn_params<T_, V_>(a, dZ, reinterpret_cast<float*>(ws), nullptr, 0)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL
 }

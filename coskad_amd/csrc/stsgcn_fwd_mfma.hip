@@ -3,7 +3,7 @@
 // Persistent blocks; the mixing matrices and the folded conv weights are loaded into LDS once
 // per block; gcn and both 1x1 convs run on v_mfma_f32_16x16x4_f32.
 #include "mfma_ops.h"
-#include <cstdlib>
+#include "layer_launch.h"
 
 namespace coskad {
 
@@ -220,12 +220,7 @@ int launch_layer_apply_m(const float* in, float* out, const float* Aw, const flo
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, in, out, Aw, Tw, wfold, bias, in_slope,   \
                        out_slope, B, Ci, Co, CoP, NB, dbg, Zg);                                     \
   } while (0)
-#ifdef COSKAD_ABLATE   // phase-ablation builds only (tools/ablate_bwd.py): the product library has no runtime switches
-  static int dbg = -1;
-  if (dbg < 0) { const char* e = getenv("COSKAD_DBG"); dbg = e ? atoi(e) : 0; }
-#else
-  constexpr int dbg = 0;
-#endif
+  static const int dbg = ablate_env("COSKAD_DBG", 0);   // phase-ablation builds only (tools/ablate_bwd.py)
   ProbeScope probe(KID_LAYER_APPLY, Ci, Co, st);
   if (CoP == 16) LAUNCH_OTI(1);
   else if (CoP == 32) LAUNCH_OTI(2);
@@ -241,23 +236,6 @@ template int launch_layer_apply_m<12, 25>(const float*, float*, const float*, co
 template int launch_layer_apply_m<12, 14>(const float*, float*, const float*, const float*, const float*, const float*, const float*, const float*, int, int, int, hipStream_t, const float*);
 template int launch_layer_apply_m<12, 18>(const float*, float*, const float*, const float*, const float*, const float*, const float*, const float*, int, int, int, hipStream_t, const float*);
 
-}  // namespace coskad
-
-namespace coskad {
-// fused_apply.hip
-bool layer_apply_ring_ok(int T_, int V_, int Ci, int Co);
-int launch_layer_apply_ring(const float* Z, const float* in, float* out, const float* wfold, const float* bias,
-                            const float* in_slope, int B, int Ci, int Co, hipStream_t st);
-// fused_apply_bpc.hip
-int launch_layer_apply_bpc(const float* Z, const float* in, float* out, const float* wfold, const float* bias,
-                           const float* in_slope, int B, int Ci, int Co, hipStream_t st);
-// first_layer.hip
-int launch_first_apply(const float* Z, const float* in, float* out, const float* wfold, const float* bias, const float* in_slope,
-                       int B, int Ci, int Co, int TVr, hipStream_t st);
-// fused_apply_flat.hip
-bool layer_apply_flat_ok(int TV_, int Ci, int Co);
-int launch_layer_apply_flat(const float* Z, const float* in, float* out, const float* wfold, const float* bias,
-                            const float* in_slope, int B, int Ci, int Co, int TV_, hipStream_t st);
 }  // namespace coskad
 
 using namespace coskad;

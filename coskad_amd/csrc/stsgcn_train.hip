@@ -14,6 +14,7 @@
 //   k_reduce_partials: fp64 sum over blocks (deterministic: fixed order, no atomics)
 //   k_train_fold    : stats -> folded weights, saved stats for backward, running-stat update
 #include "mfma_ops.h"
+#include "layer_launch.h"
 
 namespace coskad {
 
@@ -273,66 +274,49 @@ __global__ __launch_bounds__(1024) void k_train_fold(
   TFOLD_STAMP(4);
 }
 
-// rows of the tile kernels that keep ONE Ci-row image (+1024 floats scratch) in LDS
-static int pick_nb_rows(int rows_per_clip, int B, int LD, int budget_bytes) {
-  int nb = rows_per_clip >= 64 ? 1 : 64 / rows_per_clip;
-  if (nb < 1) nb = 1;
-  while (nb > 1 && (size_t)nb * rows_per_clip * LD * 4 > (size_t)budget_bytes) --nb;
-  if (nb > B) nb = B;
-  return nb;
-}
-
-// first_layer.hip
-int launch_first_moments(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B, int Ci,
-                         int T, int V, float* Zout, int max_rows, hipStream_t st, int* rows_out);
-// fwd_moments_bpc.hip
-bool fwd_moments_bpc_ok(int T_, int V_, int Ci);
-int launch_fwd_moments_bpc(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B, int Ci,
-                           int T_, int V_, int need_x, float* Zout, hipStream_t st, int* rows_out);
-
 size_t train_stats_ws_bytes(int Ci) {
   const size_t E = 2 * ((size_t)Ci * Ci + Ci);
   return kMaxGrid * E * sizeof(float) + round_up((int)(E * sizeof(double)), 256) + 256;
 }
 
-// moment partials [rows][2 (Ci^2 + Ci)] -> fp64 sums (fixed order) -> statistics, folded weights, running-stat update
-static int launch_reduce_fold(const float* partials, int rows, double* red, double npos, const float* Wt, const float* bt,
-                              const float* gs, const float* bs, float* rm_s, float* rv_s, long long* nbt_s, const float* Wr,
-                              const float* br, const float* gr, const float* brr, float* rm_r, float* rv_r, long long* nbt_r,
-                              float momentum, float* wfold, float* bias, float* stat, int Ci, int Co, hipStream_t st) {
+void launch_reduce_partials(const float* partials, int rows, int E, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_reduce_partials, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, partials, rows, E, out);
+}
+
+// moment partials [rows][2 (Ci^2 + Ci)] -> fp64 sums `red` (fixed order) -> statistics, folded weights, running-stat update.
+// partials NULL: `red` holds the sums already (SyncBN, summed over the ranks); p.Wt NULL: the sums only
+static int launch_reduce_fold(const float* partials, int rows, double* red, double npos, const BnConvParams& p, const FoldOut& o,
+                              int Ci, int Co, hipStream_t st) {
   const int E = 2 * (Ci * Ci + Ci);
   int rc = 0;
-  const bool self_sum = partials && Wt && E <= kFoldSelfSum;   // the fold sums the (tiny) table itself
-  if (partials && !self_sum) {                           // (NULL: `red` holds the sums already -- SyncBN, summed over the ranks)
-    hipLaunchKernelGGL(k_reduce_partials, dim3(ceil_div(E, kRedCols)), dim3(1024), 0, st, partials, rows, E, red);
+  const bool self_sum = partials && p.Wt && E <= kFoldSelfSum;   // the fold sums the (tiny) table itself
+  if (partials && !self_sum) {
+    launch_reduce_partials(partials, rows, E, red, st);
     if ((rc = check_launch("reduce_partials"))) return rc;
   }
-  if (!Wt) return 0;                                     // sums only
+  if (!p.Wt) return 0;
   const size_t fold_lds = (2 * (size_t)Ci * Ci + 2 * Ci) * sizeof(double) + (4 * (size_t)Co * Ci + 4 * Co) * sizeof(float);
   if (fold_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_train_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds);
   const int fold_blocks = Co >= 32 ? 8 : (Co >= 16 ? 4 : 1);
-  hipLaunchKernelGGL(k_train_fold, dim3(fold_blocks), dim3(1024), fold_lds, st, red, npos, Wt, bt, gs, bs, rm_s,
-                     rv_s, nbt_s, Wr, br, gr, brr, rm_r, rv_r, nbt_r, momentum, wfold, bias, stat, Ci,
+  hipLaunchKernelGGL(k_train_fold, dim3(fold_blocks), dim3(1024), fold_lds, st, red, npos, p.Wt, p.bt, p.gt, p.bet, p.rm_t,
+                     p.rv_t, p.nbt_t, p.Wr, p.br, p.gr, p.ber, p.rm_r, p.rv_r, p.nbt_r, p.momentum, o.wfold, o.bias, o.stat, Ci,
                      Co, round_up(Co, 16), self_sum ? partials : (const float*)nullptr, rows);
   return check_launch("train_fold");
 }
 
+// The statistics pass of one layer: Z = gcn(PReLU(in)) (stored where a.Zout is given), its moments as partial rows, then the fold.
+// a.sums != NULL: stop behind the fp64 moment sums (written there; a.p and a.out unused) -- the caller adds the other ranks'
 template <int T, int V>
-static int launch_train_stats(const float* in, const float* Aw, const float* Tw, const float* in_slope,
-                              const float* Wt, const float* bt, const float* gs, const float* bs,
-                              float* rm_s, float* rv_s, long long* nbt_s, const float* Wr,
-                              const float* br, const float* gr, const float* brr, float* rm_r,
-                              float* rv_r, long long* nbt_r, float momentum, float* wfold, float* bias,
-                              float* stat, void* ws, size_t ws_bytes, int B, int Ci, int Co,
-                              hipStream_t st, float* Zout = nullptr, double* sums_out = nullptr, int need_x_sums = 1) {
-  // sums_out != NULL: stop behind the fp64 moment sums (written there; Wt .. stat unused) -- the caller adds the other ranks'
+static int launch_train_stats(const LayerStatsArgs& a) {
   constexpr int kBlock = Geo<T, V>::Block;   // threads per block of this geometry
   constexpr int kScratchFloats = Geo<T, V>::Scratch;
   constexpr int TV = Geo<T, V>::TV, LD = TV + 2;   // k_fwd_moments' row stride
   static_assert(TV % 4 == 0, "the moments kernel stages with float4 and needs TV + 2 == 2 (mod 4)");
+  const int B = a.B, Ci = a.Ci, Co = a.Co;
+  hipStream_t st = a.stream;
   if (Ci > 64) return fail(COSKAD_ERR_SHAPE, "train_stats: C_in=%d > 64 not supported", Ci);
-  if (ws_bytes < train_stats_ws_bytes(Ci))
-    return fail(COSKAD_ERR_WORKSPACE, "train_stats: workspace %zu < %zu bytes", ws_bytes, train_stats_ws_bytes(Ci));
+  if (a.ws_bytes < train_stats_ws_bytes(Ci))
+    return fail(COSKAD_ERR_WORKSPACE, "train_stats: workspace %zu < %zu bytes", a.ws_bytes, train_stats_ws_bytes(Ci));
   const int E = 2 * (Ci * Ci + Ci);
   int NB = Ci >= 32 ? 1 : 32 / Ci;   // 32 rows per tile (2 MFMA row tiles)
   if (NB > B) NB = B;
@@ -343,43 +327,60 @@ static int launch_train_stats(const float* in, const float* Aw, const float* Tw,
   // persistent blocks: as many 512-thread blocks per CU as LDS (coarse granules: keep a margin) and VGPRs allow
   const int per_cu = lds <= (size_t)52 * 1024 && Ci <= 32 && kBlock <= 512 ? 3 : (lds <= (size_t)80 * 1024 ? 2 : 1);
   const int grid = ntiles < 256 * per_cu ? ntiles : 256 * per_cu;
-  float* partials = reinterpret_cast<float*>(ws);
-  double* red = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + round_up((int)(kMaxGrid * (size_t)E * sizeof(float)), 256));
-  const int need_x = sums_out ? need_x_sums : (Wr != nullptr);
-  const int ntc = ceil_div(Ci, 16);
+  float* partials = reinterpret_cast<float*>(a.ws);
+  double* red = reinterpret_cast<double*>(reinterpret_cast<char*>(a.ws) + round_up((int)(kMaxGrid * (size_t)E * sizeof(float)), 256));
+  const int need_x = a.sums ? 1 : (a.p.Wr != nullptr);
   int rows = grid;
-  if (Zout && Ci <= 4 && TV % 4 == 0) {
+  if (a.Zout && Ci <= 4 && TV % 4 == 0) {
     // a handful of input channels (the first layer): plain FMAs, one clip per wave (first_layer.hip)
-    int rc1 = launch_first_moments(in, Aw, Tw, in_slope, partials, B, Ci, T, V, Zout, kMaxGrid, st, &rows);
+    int rc1 = launch_first_moments(a.in, a.A, a.Tm, a.in_slope, partials, B, Ci, T, V, a.Zout, kMaxGrid, st, &rows);
     if (rc1) return rc1;
-  } else if (Zout && fwd_moments_bpc_ok(T, V, Ci)) {
+  } else if (a.Zout && fwd_moments_bpc_ok(T, V, Ci)) {
     // the 25-joint layout, 16 / 32 channels: one clip per four-wave workgroup, mixing operands in registers (fwd_moments_bpc.hip)
     ProbeScope probe(KID_FWD_MOMENTS, Ci, Co, st);
-    int rc1 = launch_fwd_moments_bpc(in, Aw, Tw, in_slope, partials, B, Ci, T, V, need_x, Zout, st, &rows);
+    int rc1 = launch_fwd_moments_bpc(a.in, a.A, a.Tm, a.in_slope, partials, B, Ci, T, V, need_x, a.Zout, st, &rows);
     if (rc1) return rc1;
   } else {
-#define LAUNCH_M(NTC)                                                                           \
-  do {                                                                                          \
-    auto k = k_fwd_moments<T, V, NTC>;                                                          \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, in, Aw, Tw, in_slope, partials, B, Ci, NB, need_x, Zout); \
-  } while (0)
-  {
-  ProbeScope probe(KID_FWD_MOMENTS, Ci, Co, st);
-  if (ntc == 1) LAUNCH_M(1);
-  else if (ntc == 2) LAUNCH_M(2);
-  else if (ntc == 3) LAUNCH_M(3);
-  else LAUNCH_M(4);
-  }
-#undef LAUNCH_M
+    ProbeScope probe(KID_FWD_MOMENTS, Ci, Co, st);
+    with_tiles(ceil_div(Ci, 16), [&](auto NTC) {
+      auto k = k_fwd_moments<T, V, decltype(NTC)::value>;
+      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, a.in, a.A, a.Tm, a.in_slope, partials, B, Ci, NB, need_x, a.Zout);
+    });
   }
   int rc = check_launch("fwd_moments");
   if (rc) return rc;
-  if (sums_out)
-    return launch_reduce_fold(partials, rows, sums_out, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, Ci, Co, st);
-  return launch_reduce_fold(partials, rows, red, (double)B * TV, Wt, bt, gs, bs, rm_s, rv_s, nbt_s, Wr, br, gr, brr, rm_r, rv_r,
-                            nbt_r, momentum, wfold, bias, stat, Ci, Co, st);
+  if (a.sums) return launch_reduce_fold(partials, rows, a.sums, 0.0, BnConvParams{}, FoldOut{}, Ci, Co, st);
+  return launch_reduce_fold(partials, rows, red, (double)B * TV, a.p, a.out, Ci, Co, st);
+}
+
+// ---- what the entry points share: the argument checks, under the entry's own name ------------------------------------------------
+enum : unsigned {
+  kNeedInput = 1,     // in, A, T: a statistics pass runs
+  kNeedPartials = 2,  // the moment partial rows of the previous layer's kernel
+  kNeedSums = 4,      // the fp64 moment sums (in or out)
+  kNeedFold = 8,      // the main branch with its BatchNorm, the fold's outputs; a residual weight comes with its BatchNorm
+  kNeedWs = 16,
+};
+static int check_layer_stats(const char* who, const LayerStatsArgs& a, unsigned need) {
+  bool null = false;
+  if (need & kNeedInput) null = null || !a.in || !a.A || !a.Tm;
+  if (need & kNeedPartials) null = null || !a.partials;
+  if (need & kNeedSums) null = null || !a.sums;
+  if (need & kNeedFold) null = null || !a.p.Wt || !a.p.gt || !a.p.bet || !a.out.wfold || !a.out.bias || !a.out.stat;
+  if (need & kNeedWs) null = null || !a.ws;
+  if (null) return fail(COSKAD_ERR_ARG, "%s: null pointer", who);
+  if (need & kNeedFold) {
+    if (a.p.Wr && (!a.p.gr || !a.p.ber)) return fail(COSKAD_ERR_ARG, "%s: residual BN missing", who);
+    if (!a.p.Wr && a.Ci != a.Co) return fail(COSKAD_ERR_ARG, "%s: identity residual needs Ci == Co", who);
+  }
+  return COSKAD_OK;
+}
+
+static int dispatch_train_stats(const LayerStatsArgs& a, int T, int V) {
+#define CALL(T_, V_) return launch_train_stats<T_, V_>(a)
+  COSKAD_DISPATCH_TV(T, V, CALL);
+#undef CALL
 }
 
 }  // namespace coskad
@@ -391,28 +392,8 @@ extern "C" {
 size_t coskad_train_stats_ws_bytes(int Ci) { return train_stats_ws_bytes(Ci); }
 int coskad_stat_floats(int Ci, int Co) { return stat_floats(Ci, Co); }
 
-int coskad_layer_train_stats_f32(const float* in, const float* A, const float* Tm, const float* in_slope,
-                                 const float* Wt, const float* bt, const float* gamma_t,
-                                 const float* beta_t, float* rmean_t, float* rvar_t, long long* nbt_t,
-                                 const float* Wr, const float* br, const float* gamma_r,
-                                 const float* beta_r, float* rmean_r, float* rvar_r, long long* nbt_r,
-                                 float momentum, float* wfold, float* bias, float* stat, void* ws,
-                                 size_t ws_bytes, int B, int Ci, int Co, int T, int V,
-                                 hipStream_t stream) {
-  if (!in || !A || !Tm || !Wt || !gamma_t || !beta_t || !wfold || !bias || !stat || !ws)
-    return fail(COSKAD_ERR_ARG, "layer_train_stats: null pointer");
-  if (Wr && (!gamma_r || !beta_r)) return fail(COSKAD_ERR_ARG, "layer_train_stats: residual BN missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_train_stats: identity residual needs Ci == Co");
-  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_train_stats: B=%d Ci=%d Co=%d", B, Ci, Co);
-#define CALL(T_, V_)                                                                                   \
-  return launch_train_stats<T_, V_>(in, A, Tm, in_slope, Wt, bt, gamma_t, beta_t, rmean_t, rvar_t, nbt_t, \
-                                    Wr, br, gamma_r, beta_r, rmean_r, rvar_r, nbt_r, momentum, wfold, \
-                                    bias, stat, ws, ws_bytes, B, Ci, Co, stream)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
-}
-
-/* The same, additionally storing Z = gcn(PReLU(in)) [B,Ci,T,V] for coskad_layer_apply_z_f32 and the *_z backward. */
+/* One layer's statistics pass and fold, additionally storing Z = gcn(PReLU(in)) [B,Ci,T,V] (NULL: not stored) for
+ * coskad_layer_apply_z_f32 and the *_z backward. */
 int coskad_layer_train_stats_z_f32(const float* in, const float* A, const float* Tm, const float* in_slope,
                                  const float* Wt, const float* bt, const float* gamma_t,
                                  const float* beta_t, float* rmean_t, float* rvar_t, long long* nbt_t,
@@ -421,17 +402,29 @@ int coskad_layer_train_stats_z_f32(const float* in, const float* A, const float*
                                  float momentum, float* wfold, float* bias, float* stat, void* ws,
                                  size_t ws_bytes, int B, int Ci, int Co, int T, int V,
                                  hipStream_t stream, float* Z) {
-  if (!in || !A || !Tm || !Wt || !gamma_t || !beta_t || !wfold || !bias || !stat || !ws)
-    return fail(COSKAD_ERR_ARG, "layer_train_stats: null pointer");
-  if (Wr && (!gamma_r || !beta_r)) return fail(COSKAD_ERR_ARG, "layer_train_stats: residual BN missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_train_stats: identity residual needs Ci == Co");
+  const LayerStatsArgs a{
+      .in = in, .A = A, .Tm = Tm, .in_slope = in_slope,
+      .p = {.Wt = Wt, .bt = bt, .gt = gamma_t, .bet = beta_t, .rm_t = rmean_t, .rv_t = rvar_t, .nbt_t = nbt_t, .Wr = Wr, .br = br,
+            .gr = gamma_r, .ber = beta_r, .rm_r = rmean_r, .rv_r = rvar_r, .nbt_r = nbt_r, .momentum = momentum},
+      .out = {.wfold = wfold, .bias = bias, .stat = stat},
+      .Zout = Z, .ws = ws, .ws_bytes = ws_bytes, .B = B, .Ci = Ci, .Co = Co, .stream = stream};
+  if (int rc = check_layer_stats("layer_train_stats", a, kNeedInput | kNeedFold | kNeedWs)) return rc;
   if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_train_stats: B=%d Ci=%d Co=%d", B, Ci, Co);
-#define CALL(T_, V_)                                                                                   \
-  return launch_train_stats<T_, V_>(in, A, Tm, in_slope, Wt, bt, gamma_t, beta_t, rmean_t, rvar_t, nbt_t, \
-                                    Wr, br, gamma_r, beta_r, rmean_r, rvar_r, nbt_r, momentum, wfold, \
-                                    bias, stat, ws, ws_bytes, B, Ci, Co, stream, Z)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
+  return dispatch_train_stats(a, T, V);
+}
+
+/* The same, Z not stored. */
+int coskad_layer_train_stats_f32(const float* in, const float* A, const float* Tm, const float* in_slope,
+                                 const float* Wt, const float* bt, const float* gamma_t,
+                                 const float* beta_t, float* rmean_t, float* rvar_t, long long* nbt_t,
+                                 const float* Wr, const float* br, const float* gamma_r,
+                                 const float* beta_r, float* rmean_r, float* rvar_r, long long* nbt_r,
+                                 float momentum, float* wfold, float* bias, float* stat, void* ws,
+                                 size_t ws_bytes, int B, int Ci, int Co, int T, int V,
+                                 hipStream_t stream) {
+  return coskad_layer_train_stats_z_f32(in, A, Tm, in_slope, Wt, bt, gamma_t, beta_t, rmean_t, rvar_t, nbt_t, Wr, br, gamma_r, beta_r,
+                                        rmean_r, rvar_r, nbt_r, momentum, wfold, bias, stat, ws, ws_bytes, B, Ci, Co, T, V, stream,
+                                        nullptr);
 }
 
 /* Statistics of a layer whose moment partials were produced by the PREVIOUS layer's coskad_layer_apply_next_f32:
@@ -443,16 +436,17 @@ int coskad_layer_train_fold_f32(const float* partials, int rows, const float* Wt
                                 const float* beta_r, float* rmean_r, float* rvar_r, long long* nbt_r,
                                 float momentum, float* wfold, float* bias, float* stat, void* ws,
                                 size_t ws_bytes, int B, int Ci, int Co, int T, int V, hipStream_t stream) {
-  if (!partials || !Wt || !gamma_t || !beta_t || !wfold || !bias || !stat || !ws)
-    return fail(COSKAD_ERR_ARG, "layer_train_fold: null pointer");
-  if (Wr && (!gamma_r || !beta_r)) return fail(COSKAD_ERR_ARG, "layer_train_fold: residual BN missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_train_fold: identity residual needs Ci == Co");
+  const LayerStatsArgs a{
+      .partials = partials, .rows = rows,
+      .p = {.Wt = Wt, .bt = bt, .gt = gamma_t, .bet = beta_t, .rm_t = rmean_t, .rv_t = rvar_t, .nbt_t = nbt_t, .Wr = Wr, .br = br,
+            .gr = gamma_r, .ber = beta_r, .rm_r = rmean_r, .rv_r = rvar_r, .nbt_r = nbt_r, .momentum = momentum},
+      .out = {.wfold = wfold, .bias = bias, .stat = stat},
+      .ws = ws, .ws_bytes = ws_bytes, .B = B, .Ci = Ci, .Co = Co, .stream = stream};
+  if (int rc = check_layer_stats("layer_train_fold", a, kNeedPartials | kNeedFold | kNeedWs)) return rc;
   if (B <= 0 || Ci <= 0 || Co <= 0 || Ci > 64 || rows <= 0) return fail(COSKAD_ERR_ARG, "layer_train_fold: B=%d Ci=%d Co=%d rows=%d", B, Ci, Co, rows);
   const size_t E = 2 * ((size_t)Ci * Ci + Ci);
   if (ws_bytes < round_up((int)(E * sizeof(double)), 256)) return fail(COSKAD_ERR_WORKSPACE, "layer_train_fold: workspace %zu too small", ws_bytes);
-  return launch_reduce_fold(partials, rows, reinterpret_cast<double*>(ws), (double)B * T * V, Wt, bt, gamma_t, beta_t, rmean_t,
-                            rvar_t, nbt_t, Wr, br, gamma_r, beta_r, rmean_r, rvar_r, nbt_r, momentum, wfold, bias, stat, Ci, Co,
-                            stream);
+  return launch_reduce_fold(partials, rows, reinterpret_cast<double*>(ws), (double)B * T * V, a.p, a.out, Ci, Co, stream);
 }
 
 /* ---- SyncBN (optional; the reference trains with per-rank statistics, train_COSKAD.py:75-78): the three steps of
@@ -463,23 +457,19 @@ int coskad_layer_train_fold_f32(const float* partials, int rows, const float* Wt
  * sums [sum xx^T Ci^2][sum x Ci][sum zz^T Ci^2][sum z Ci] -> sums.  ws: coskad_train_stats_ws_bytes(Ci). */
 int coskad_layer_train_moments_f32(const float* in, const float* A, const float* Tm, const float* in_slope, float* Z, double* sums,
                                    void* ws, size_t ws_bytes, int B, int Ci, int T, int V, hipStream_t stream) {
-  if (!in || !A || !Tm || !sums || !ws) return fail(COSKAD_ERR_ARG, "layer_train_moments: null pointer");
+  const LayerStatsArgs a{.in = in, .A = A, .Tm = Tm, .in_slope = in_slope, .Zout = Z, .sums = sums, .ws = ws, .ws_bytes = ws_bytes,
+                         .B = B, .Ci = Ci, .Co = Ci, .stream = stream};
+  if (int rc = check_layer_stats("layer_train_moments", a, kNeedInput | kNeedSums | kNeedWs)) return rc;
   if (B <= 0 || Ci <= 0) return fail(COSKAD_ERR_ARG, "layer_train_moments: B=%d Ci=%d", B, Ci);
   if ((size_t)sums & 7) return fail(COSKAD_ERR_ARG, "layer_train_moments: sums must be 8-byte aligned");
-#define CALL(T_, V_)                                                                                                       \
-  return launch_train_stats<T_, V_>(in, A, Tm, in_slope, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, \
-                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, ws,     \
-                                    ws_bytes, B, Ci, Ci, stream, Z, sums, 1)
-  COSKAD_DISPATCH_TV(T, V, CALL);
-#undef CALL
+  return dispatch_train_stats(a, T, V);
 }
 
 /* step 1 (moment partials written by the previous layer's coskad_layer_apply_next_f32): partials [rows][2 (Ci^2 + Ci)] -> sums */
 int coskad_layer_moment_sums_f32(const float* partials, int rows, int Ci, double* sums, hipStream_t stream) {
   if (!partials || !sums || rows <= 0 || Ci <= 0 || Ci > 64) return fail(COSKAD_ERR_ARG, "layer_moment_sums: bad argument");
   if ((size_t)sums & 7) return fail(COSKAD_ERR_ARG, "layer_moment_sums: sums must be 8-byte aligned");
-  return launch_reduce_fold(partials, rows, sums, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, Ci, Ci, stream);
+  return launch_reduce_fold(partials, rows, sums, 0.0, BnConvParams{}, FoldOut{}, Ci, Ci, stream);
 }
 
 /* step 2: the fold (statistics, folded weights, running-statistics update) from moment sums over `count` positions
@@ -489,12 +479,15 @@ int coskad_layer_train_fold_sums_f32(const double* sums, double count, const flo
                                      const float* Wr, const float* br, const float* gamma_r,
                                      const float* beta_r, float* rmean_r, float* rvar_r, long long* nbt_r,
                                      float momentum, float* wfold, float* bias, float* stat, int Ci, int Co, hipStream_t stream) {
-  if (!sums || !Wt || !gamma_t || !beta_t || !wfold || !bias || !stat) return fail(COSKAD_ERR_ARG, "layer_train_fold_sums: null pointer");
-  if (Wr && (!gamma_r || !beta_r)) return fail(COSKAD_ERR_ARG, "layer_train_fold_sums: residual BN missing");
-  if (!Wr && Ci != Co) return fail(COSKAD_ERR_ARG, "layer_train_fold_sums: identity residual needs Ci == Co");
+  const LayerStatsArgs a{
+      .p = {.Wt = Wt, .bt = bt, .gt = gamma_t, .bet = beta_t, .rm_t = rmean_t, .rv_t = rvar_t, .nbt_t = nbt_t, .Wr = Wr, .br = br,
+            .gr = gamma_r, .ber = beta_r, .rm_r = rmean_r, .rv_r = rvar_r, .nbt_r = nbt_r, .momentum = momentum},
+      .out = {.wfold = wfold, .bias = bias, .stat = stat},
+      .sums = const_cast<double*>(sums),   // (read only: the fold starts from them)
+      .Ci = Ci, .Co = Co, .stream = stream};
+  if (int rc = check_layer_stats("layer_train_fold_sums", a, kNeedSums | kNeedFold)) return rc;
   if (count <= 0.0 || Ci <= 0 || Co <= 0 || Ci > 64) return fail(COSKAD_ERR_ARG, "layer_train_fold_sums: count=%g Ci=%d Co=%d", count, Ci, Co);
-  return launch_reduce_fold(nullptr, 0, const_cast<double*>(sums), count, Wt, bt, gamma_t, beta_t, rmean_t, rvar_t, nbt_t, Wr, br,
-                            gamma_r, beta_r, rmean_r, rvar_r, nbt_r, momentum, wfold, bias, stat, Ci, Co, stream);
+  return launch_reduce_fold(nullptr, 0, a.sums, count, a.p, a.out, Ci, Co, stream);
 }
 
 #ifdef COSKAD_FOLD_TIMING
