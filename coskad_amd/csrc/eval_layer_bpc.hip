@@ -359,7 +359,9 @@ int launch_eval_layer_bpc(const float* in, float* out, const float* Aw, const fl
 extern "C" {
 
 /* 1: coskad_layer_first_pair_apply_f32 takes the first layer (Ci = 2 -> Cm) with the layer behind it (Cm -> Co) on this layout */
-int coskad_layer_first_pair_ok(int T, int V, int Ci, int Cm, int Co) { return eval_first_pair_ok(T, V, Ci, Cm, Co) ? 1 : 0; }
+int coskad_layer_first_pair_ok(int T, int V, int Ci, int Cm, int Co) {
+  return (eval_first_pair_ok(T, V, Ci, Cm, Co) || eval_first_pair_window_ok(T, V, Ci, Cm, Co)) ? 1 : 0;
+}
 
 /* The first two ST_GCNN layers of the encoder with folded BatchNorm (models/common/components.py:94-105 -> models/graph_layers/
  * stsgcn.py:94-116 twice, eval mode) in ONE pass: out [B, Co, T, V] = layer2(PReLU_mid(layer1(x))), x [B, 2, T, V] the network input; the
@@ -370,8 +372,10 @@ int coskad_layer_first_pair_apply_f32(const float* x, float* out, const float* A
                                       const float* out_slope, int B, int Cm, int Co, int T, int V, hipStream_t stream) {
   if (!x || !out || !A1 || !T1 || !wfold1 || !bias1 || !A2 || !T2 || !wfold2 || !bias2 || !mid_slope)
     return fail(COSKAD_ERR_ARG, "layer_first_pair_apply: null pointer");
+  if (B > 0 && eval_first_pair_window_ok(T, V, 2, Cm, Co))
+    return launch_eval_first_pair_window(x, out, A1, T1, wfold1, bias1, A2, T2, wfold2, bias2, mid_slope, out_slope, B, Co, T, V, stream);
   if (B <= 0 || !eval_first_pair_ok(T, V, 2, Cm, Co))
-    return fail(COSKAD_ERR_SHAPE, "layer_first_pair_apply: built for 12 x 17 / 25, 2 -> 32 -> 16 / 32 / 64 channels");
+    return fail(COSKAD_ERR_SHAPE, "layer_first_pair_apply: built for 8 / 12 / 16 / 24 x 17 / 25, 2 -> 32 -> 16 / 32 / 64 channels");
   const ev::FirstLayer fl{A1, T1, wfold1, bias1};
   if (V == 17) return launch_eval_first_pair_v<17>(x, out, fl, A2, T2, wfold2, bias2, mid_slope, out_slope, B, Co, stream);
   return launch_eval_first_pair_v<25>(x, out, fl, A2, T2, wfold2, bias2, mid_slope, out_slope, B, Co, stream);

@@ -317,6 +317,8 @@ int coskad_layer_apply_f32(const float* in, float* out, const float* A, const fl
                            hipStream_t stream) {
   if (!in || !out || !A || !Tm || !wfold || !bias) return fail(COSKAD_ERR_ARG, "layer_apply: null pointer");
   if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_apply: B=%d Ci=%d Co=%d", B, Ci, Co);
+  if (eval_layer_window_ok(T, V, Ci, Co))
+    return launch_eval_layer_window(in, out, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V, stream);
 #define CALL(T_, V_) return launch_layer_apply<T_, V_>(in, out, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, stream)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL

@@ -120,6 +120,10 @@ class ChainCtx:
 
 # eval-mode forwards run the first two layers in one kernel where it is built (csrc/eval_layer_bpc.hip, FIRST form); tests flip it
 EVAL_FIRST_PAIR = True
+# eval-mode, no-grad forwards of window lengths 8 / 16 / 24 run their layers on the folded one-clip kernels where they are built
+# (csrc/eval_layer_window.hip; models/graph_layers/stsgcn.py: plan_stack); tests and tools/bench_eval_window.py flip it to get the
+# composed route
+EVAL_WINDOW = True
 
 
 def chain_forward(x: Tensor, layers: List[LayerTensors], training: bool, ws: Workspace,

@@ -370,23 +370,72 @@ class ST_GCNN_layer(nn.Module):
         return _PReLUFn.apply(u, slope)
 
 
+def _window_eval_layer(m: "ST_GCNN_layer") -> bool:
+    """an eval-mode layer that is `is_wide` ONLY because of its window length, with BatchNorms that have running statistics to fold
+    (track_running_stats=False normalises with batch statistics in eval mode too: composed path)"""
+    if m.training or max(m.in_channels, m.out_channels) > WIDE_CHANNELS or not ops.window_ok(m.time_dim, m.joints_dim):
+        return False
+    bns = [m.tcn[1]] + ([] if isinstance(m.residual, nn.Identity) else [m.residual[1]])
+    return all(bn.track_running_stats and bn.running_mean is not None for bn in bns)
+
+
+def plan_stack(layer_modules: List["ST_GCNN_layer"], need_grad: bool) -> List[Tuple[str, int, int]]:
+    """The route of a stack, as segments (kind, i, j) over layer_modules[i:j] (no device involved):
+      'chain'       -- consecutive layers on the LDS-resident tile kernels (run_chain: one autograd node);
+      'wide'        -- ONE layer on the composed path (forward_wide);
+      'window_eval' -- consecutive layers of a window length other than 12 in eval mode with nobody asking for a gradient, each one
+                       launch on the folded one-clip kernels (ops.layer_apply_window_ok), or the 2-channel head of a first pair
+                       (ops.layer_first_pair_ok) at the front of such a segment with its partner behind it."""
+    n = len(layer_modules)
+    take = [False] * n
+    if engine.EVAL_WINDOW and not need_grad:
+        ev = [_window_eval_layer(m) for m in layer_modules]
+        take = [ev[k] and ops.layer_apply_window_ok(m.time_dim, m.joints_dim, m.in_channels, m.out_channels)
+                for k, m in enumerate(layer_modules)]
+        for k in range(n - 1):
+            m, nx = layer_modules[k], layer_modules[k + 1]
+            if (engine.EVAL_FIRST_PAIR and ev[k] and not take[k] and take[k + 1] and (k == 0 or not take[k - 1])
+                    and not isinstance(m.residual, nn.Identity) and nx.in_channels == m.out_channels
+                    and ops.layer_first_pair_ok(m.in_channels, m.out_channels, nx.out_channels, m.time_dim, m.joints_dim)):
+                take[k] = True
+    segs: List[Tuple[str, int, int]] = []
+    i = 0
+    while i < n:
+        if take[i]:
+            j = i
+            while j < n and take[j]:
+                j += 1
+            segs.append(("window_eval", i, j))
+        elif layer_modules[i].is_wide:
+            j = i + 1
+            segs.append(("wide", i, j))
+        else:
+            j = i
+            while j < n and not take[j] and not layer_modules[j].is_wide:
+                j += 1
+            segs.append(("chain", i, j))
+        i = j
+    return segs
+
+
 def run_stack(x: Tensor, layer_modules: List["ST_GCNN_layer"], ws: engine.Workspace,
               in_slope: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
     """A stack that may mix fused (<= 64 channels) and wide layers.  x: activated input, or (in_slope given) a pre-activation
     whose PReLU weight is in_slope (no gradient flows to it: eval-mode hand-over of coskad_amd/lowrank.py).  -> (h, slope): apply
-    PReLU(slope) to h to get the stack's output (slope None: h is already activated)."""
+    PReLU(slope) to h to get the stack's output (slope None: h is already activated).  The route is plan_stack's."""
     h, slope = x, in_slope
-    i, n = 0, len(layer_modules)
-    while i < n:
-        if layer_modules[i].is_wide:
+    for kind, i, j in plan_stack(layer_modules, torch.is_grad_enabled()):
+        if kind == "wide":
             if slope is not None:
                 h, slope = _PReLUFn.apply(h, slope), None
             h = layer_modules[i].forward_wide(h)
-            i += 1
+        elif kind == "window_eval":
+            layers = [layer_tensors(m) for m in layer_modules[i:j]]
+            if slope is not None and not ops.layer_apply_window_ok(layer_modules[i].time_dim, layer_modules[i].joints_dim,
+                                                                   layers[0].Ci, layers[0].Co):
+                h, slope = _PReLUFn.apply(h, slope), None      # (the head of a first pair takes the network input as it is)
+            h, _ = engine.chain_forward(h.contiguous(), layers, False, ws, in_slope=slope)
+            slope = layers[-1].slope
         else:
-            j = i
-            while j < n and not layer_modules[j].is_wide:
-                j += 1
             h, slope = run_chain(h, layer_modules[i:j], ws, in_slope=slope)
-            i = j
     return h, slope
