@@ -22,209 +22,10 @@
 #include "common.h"
 #include "mfma_ops.h"
 #include "layer_launch.h"
+#include "window_ops.h"
 
 namespace coskad {
 namespace {
-
-constexpr int kWinBlock = 512;            // eight waves
-constexpr int kWinWaves = kWinBlock / 64;
-constexpr int kLdsFloats = kMaxLdsBytes / 4;
-
-template <int T, int V>
-struct WinGeo {
-  static_assert(T % 4 == 0, "the window length is the K side of the temporal mix: whole k-steps");
-  static constexpr int TV = T * V;
-  static constexpr int LD = TV + 1;              // (TV is even) odd row stride: rows <-> lanes and positions <-> lanes without bank conflicts
-  static constexpr int IMG = 16 * LD;            // floats of one 16-row tile image
-  static constexpr int NA = T * V * V, NT = V * T * T, E = NA + NT;
-  static constexpr int KST = T / 4, NTT = (T + 15) / 16;          // temporal mix: k-steps, 16-column tiles
-  static constexpr int KSV = (V + 3) / 4, NTV = (V + 15) / 16;    // spatial mix
-  static constexpr int FPW = (T + kWinWaves - 1) / kWinWaves, JPW = (V + kWinWaves - 1) / kWinWaves;   // frames / joints per wave of the mixing kernel
-  // mixing kernel: the B operands of a wave's frames and joints stay in its registers (<= 90 at (24, 25)), the LDS holds the row
-  // image alone: up to four row tiles per workgroup pass, within half the LDS so that two workgroups share a CU
-  static constexpr int MixRT = (kLdsFloats / 2) / IMG < 4 ? (kLdsFloats / 2) / IMG : 4;
-  static_assert(MixRT >= 1, "mixing kernel: one row tile exceeds half the LDS");
-  static constexpr int MixLds = MixRT * IMG;
-  static constexpr int MixUB = JPW * NTT * KST + FPW * NTV * KSV > 64 ? 2 : 4;   // float4 loads in flight: what the operands leave room for
-  // parameter kernel: images of X, dZ (-> dY -> dX) and Y of ParRT row tiles; the tables join them in LDS where they fit beside one
-  // tile of each ((24, 25): 28 848 + 29 400 floats do not -- its B operands come from global memory, i.e. from L2).  Where two
-  // workgroups share a CU they are eight waves each; where one workgroup takes more than half the LDS it is sixteen waves, so that
-  // the CU still runs four waves per SIMD and a wave holds half the accumulator tiles.
-  static constexpr bool ParTL = 3 * IMG + E <= kLdsFloats;
-  static constexpr int ParTab = ParTL ? E : 0;
-  static constexpr bool ParOne = 3 * IMG + ParTab > kLdsFloats / 2;
-  static constexpr int ParBlock = ParOne ? 1024 : 512;
-  static constexpr int ParRTmax = ((ParOne ? kLdsFloats : kLdsFloats / 2) - ParTab) / (3 * IMG);
-  static constexpr int ParRT = ParRTmax < 4 ? ParRTmax : 4;
-  static_assert(ParRT >= 1, "parameter kernel: three images exceed the LDS");
-  static constexpr int ParLds = 3 * ParRT * IMG + ParTab;
-  // persistent grid of the parameter kernel = partial rows of its workspace
-  static constexpr int ParGrid = ParOne ? 256 : 512;
-};
-
-// B operand of the temporal mix of joint v for this lane: tb = T[v][T][T]; columns >= T are zeros.
-//   forward: B[k = t][j = q] = T[v][t][q];  adjoint: B[k = q][j = t] = T[v][t][q]
-template <int T, int V, bool ADJ>
-__device__ __forceinline__ void win_temporal_b(const float* tb, int lane, float (&b)[WinGeo<T, V>::NTT][WinGeo<T, V>::KST]) {
-  const int i = lane & 15, k = lane >> 4;
-#pragma unroll
-  for (int nt = 0; nt < WinGeo<T, V>::NTT; ++nt) {
-    const int col = 16 * nt + i;
-    const int cc = col < T ? col : 0;
-#pragma unroll
-    for (int s = 0; s < WinGeo<T, V>::KST; ++s) {
-      const int kk = 4 * s + k;
-      const float tv = ADJ ? tb[cc * T + kk] : tb[kk * T + cc];
-      b[nt][s] = col < T ? tv : 0.f;
-    }
-  }
-}
-
-// 16 rows x (frames of joint v) . B  ->  dst (may be src: every operand is in registers before the first store, and a
-// wave's LDS accesses complete in order).
-template <int T, int V>
-__device__ __forceinline__ void win_temporal_mix(const float* src, float* dst, int v, int lane,
-                                                 const float (&b)[WinGeo<T, V>::NTT][WinGeo<T, V>::KST]) {
-  constexpr int LD = WinGeo<T, V>::LD, KS = WinGeo<T, V>::KST, NT = WinGeo<T, V>::NTT;
-  const int i = lane & 15, k = lane >> 4;
-  float a[KS];
-#pragma unroll
-  for (int s = 0; s < KS; ++s) a[s] = src[i * LD + (4 * s + k) * V + v];
-  f32x4 acc[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) acc[nt] = mfma4(a[s], b[nt][s], acc[nt]);
-  }
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = 16 * nt + i;
-    if (col < T) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dst[(4 * k + r) * LD + col * V + v] = acc[nt][r];
-    }
-  }
-}
-
-template <int T, int V, bool ADJ>
-__device__ __forceinline__ void win_temporal(const float* src, float* dst, const float* tb, int v, int lane) {
-  float b[WinGeo<T, V>::NTT][WinGeo<T, V>::KST];
-  win_temporal_b<T, V, ADJ>(tb, lane, b);
-  win_temporal_mix<T, V>(src, dst, v, lane, b);
-}
-
-// B operand of the spatial mix of frame t for this lane: ab = A[t][V][V].  K = V is padded to whole k-steps with zeros on BOTH
-// operands: neither the image next to the frame nor the table next to A[t] is read.
-//   forward: B[k = v][j = w] = A[t][v][w];  adjoint: B[k = w][j = v] = A[t][v][w]
-template <int T, int V, bool ADJ>
-__device__ __forceinline__ void win_spatial_b(const float* ab, int lane, float (&b)[WinGeo<T, V>::NTV][WinGeo<T, V>::KSV]) {
-  const int i = lane & 15, k = lane >> 4;
-#pragma unroll
-  for (int nt = 0; nt < WinGeo<T, V>::NTV; ++nt) {
-    const int col = 16 * nt + i;
-    const int cc = col < V ? col : 0;
-#pragma unroll
-    for (int s = 0; s < WinGeo<T, V>::KSV; ++s) {
-      const int kk = 4 * s + k;
-      const int kc = kk < V ? kk : 0;
-      const float av = ADJ ? ab[cc * V + kc] : ab[kc * V + cc];
-      b[nt][s] = (col < V && kk < V) ? av : 0.f;
-    }
-  }
-}
-
-// 16 rows x (joints of frame t) . B  ->  dst (may be src)
-template <int T, int V>
-__device__ __forceinline__ void win_spatial_mix(const float* src, float* dst, int t, int lane,
-                                                const float (&b)[WinGeo<T, V>::NTV][WinGeo<T, V>::KSV]) {
-  constexpr int LD = WinGeo<T, V>::LD, KS = WinGeo<T, V>::KSV, NT = WinGeo<T, V>::NTV;
-  const int i = lane & 15, k = lane >> 4;
-  float a[KS];
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const int kk = 4 * s + k;
-    const float xv = src[i * LD + t * V + (kk < V ? kk : 0)];
-    a[s] = kk < V ? xv : 0.f;
-  }
-  f32x4 acc[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) acc[nt] = mfma4(a[s], b[nt][s], acc[nt]);
-  }
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int col = 16 * nt + i;
-    if (col < V) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dst[(4 * k + r) * LD + t * V + col] = acc[nt][r];
-    }
-  }
-}
-
-// LDS image of NR rows starting at global row r0; rows beyond the nv valid ones are zeros.  vec: the tile is 16-byte aligned
-// (T*V is a multiple of 4, so the tensor's base decides) -> float4 loads, UB in flight per thread.
-template <int TV, int LD, int NR, int BLOCK, int UB>
-__device__ __forceinline__ void win_load(float* img, const float* __restrict__ g, size_t r0, int nv, bool vec) {
-  static_assert(TV % 4 == 0, "a float4 stays inside one row");
-  const float* base = g + r0 * TV;
-  if (vec) {
-    const float4* g4 = reinterpret_cast<const float4*>(base);
-    constexpr int N4 = NR * TV / 4;
-    const int n4 = nv * (TV / 4);
-    for (int i0 = threadIdx.x; i0 < N4; i0 += UB * BLOCK) {
-      float4 v[UB];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int i = i0 + u * BLOCK;
-        v[u] = i < n4 ? g4[i] : float4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int i = i0 + u * BLOCK;
-        if (i < N4) {
-          const int e = 4 * i, r = e / TV, p = e - r * TV;
-          float* d = img + r * LD + p;
-          d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
-        }
-      }
-    }
-  } else {
-    for (int e = threadIdx.x; e < NR * TV; e += BLOCK) {
-      const int r = e / TV, p = e - r * TV;
-      img[r * LD + p] = r < nv ? base[e] : 0.f;
-    }
-  }
-}
-
-// the nv valid rows of the LDS image (+ add) -> global rows r0..
-template <int TV, int LD, int NR, int BLOCK>
-__device__ __forceinline__ void win_store(const float* img, float* __restrict__ g, const float* __restrict__ add, size_t r0, int nv,
-                                          bool vec) {
-  float* ob = g + r0 * TV;
-  const float* ab = add ? add + r0 * TV : nullptr;
-  if (vec) {
-    float4* o4 = reinterpret_cast<float4*>(ob);
-    const float4* a4 = reinterpret_cast<const float4*>(ab);
-    const int n4 = nv * (TV / 4);
-    for (int i = threadIdx.x; i < n4; i += BLOCK) {
-      const int e = 4 * i, r = e / TV, p = e - r * TV;
-      const float* s = img + r * LD + p;
-      float4 o = float4{s[0], s[1], s[2], s[3]};
-      if (a4) { const float4 q = a4[i]; o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w; }
-      o4[i] = o;
-    }
-  } else {
-    for (int e = threadIdx.x; e < nv * TV; e += BLOCK) {
-      const int r = e / TV, p = e - r * TV;
-      ob[e] = ab ? img[r * LD + p] + ab[e] : img[r * LD + p];
-    }
-  }
-}
-
-__host__ inline bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
 // Y = gcn(X) or its adjoint on a persistent grid: up to MixRT 16-row tiles per workgroup pass, mixed in place in LDS.  Every wave
 // owns the joints v = wave, wave + 8, .. and the frames t = wave, wave + 8, ..; their B operands are loaded once, into registers.
@@ -287,11 +88,16 @@ __global__ __launch_bounds__(kWinBlock, 4) void k_win_gcn(const float* __restric
 //   1. X, dZ -> LDS                      2. per joint: Y_v = X_v . T[v] into a third image
 //   3. per frame t of this wave: dA[t] += Y_t^T dZ_t, then dY_t = dZ_t . A[t]^T in place
 //   4. per joint v of this wave: dT[v] += X_v^T dY_v, then (DX) dX_v = dY_v . T[v]^T in place      5. (DX) image -> dX
-template <int T, int V, bool DX>
+// ACT (the stored-Z layer backward of a training layer, float4 rows only): `x` is the PRE-activation of the layer's input with PReLU
+// weight in_slope[0].  It is activated on the way into LDS, dX leaves multiplied by PReLU'(x), and the workgroup's share of the slope
+// gradient, sum (dX + add) x over x < 0, goes to dap[blockIdx.x].  Without ACT the kernel is what it was.
+template <int T, int V, bool DX, bool ACT = false>
 __global__ __launch_bounds__((WinGeo<T, V>::ParBlock)) void k_win_params(const float* __restrict__ x, const float* __restrict__ dZ,
                                                                         const float* __restrict__ Aw, const float* __restrict__ Tw,
                                                                         float* __restrict__ partials, float* __restrict__ dX,
-                                                                        const float* __restrict__ add, int rows, int vec) {
+                                                                        const float* __restrict__ add, int rows, int vec,
+                                                                        const float* __restrict__ in_slope = nullptr,
+                                                                        float* __restrict__ dap = nullptr) {
   using G = WinGeo<T, V>;
   constexpr int TV = G::TV, LD = G::LD, RT = G::ParRT, NR = 16 * RT, BLOCK = G::ParBlock, NW = BLOCK / 64;
   constexpr bool TL = G::ParTL;
@@ -312,6 +118,8 @@ __global__ __launch_bounds__((WinGeo<T, V>::ParBlock)) void k_win_params(const f
     Tt = TwL;
   }
   const int wave = uniform(threadIdx.x >> 6);
+  float a_in = 0.f, da = 0.f;
+  if constexpr (ACT) a_in = in_slope[0];
   f32x4 accA[FPW][NTV][NTV], accT[JPW][NTT][NTT];
 #pragma unroll
   for (int f = 0; f < FPW; ++f)
@@ -331,7 +139,8 @@ __global__ __launch_bounds__((WinGeo<T, V>::ParBlock)) void k_win_params(const f
     const size_t r0 = (size_t)tile * NR;
     const int left = rows - tile * NR, nv = left < NR ? left : NR;
     const int nrt = (nv + 15) >> 4;          // row tiles with a valid row (the others are skipped, not mixed as zeros)
-    win_load<TV, LD, NR, BLOCK, 2>(imgX, x, r0, nv, vec != 0);
+    if constexpr (ACT) win_load<TV, LD, NR, BLOCK, 2, true>(imgX, x, r0, nv, true, a_in);
+    else win_load<TV, LD, NR, BLOCK, 2>(imgX, x, r0, nv, vec != 0);
     win_load<TV, LD, NR, BLOCK, 2>(imgD, dZ, r0, nv, vec != 0);
     __syncthreads();   // (the first pass: the tables too)
     for (int it = wave; it < nrt * V; it += NW) {
@@ -409,8 +218,20 @@ __global__ __launch_bounds__((WinGeo<T, V>::ParBlock)) void k_win_params(const f
     }
     __syncthreads();
     if constexpr (DX) {
-      win_store<TV, LD, NR, BLOCK>(imgD, dX, add, r0, nv, vec != 0);
+      if constexpr (ACT) da += win_store_act<TV, LD, NR, BLOCK>(imgD, dX, add, x, r0, nv, a_in);
+      else win_store<TV, LD, NR, BLOCK>(imgD, dX, add, r0, nv, vec != 0);
       __syncthreads();   // the images are loaded again
+    }
+  }
+  if constexpr (ACT && DX) {
+    // the slope-gradient share: lanes -> waves -> one float, in a fixed order (the images are dead: every tile ended with a barrier)
+    da = wave_sum(da);
+    if ((threadIdx.x & 63) == 0) imgX[threadIdx.x >> 6] = da;
+    __syncthreads();
+    if (threadIdx.x == 0 && dap) {
+      float t = 0.f;
+      for (int w = 0; w < NW; ++w) t += imgX[w];
+      dap[blockIdx.x] = t;
     }
   }
 
@@ -488,9 +309,12 @@ int launch_win_gcn(const float* in, float* out, const float* Aw, const float* Tw
   return check_launch("gcn (window)");
 }
 
+// in_slope != NULL: the ACT form (16-byte aligned rows; 17 / 25 joints); dap: its slope-gradient partials, one per workgroup;
+// *rows_out: the workgroups launched
 template <int T, int V>
 int launch_win_params(const float* x, const float* dZ, const float* Aw, const float* Tw, float* dA, float* dT, void* ws,
-                      int accumulate, int rows, hipStream_t st, float* dX, const float* add) {
+                      int accumulate, int rows, hipStream_t st, float* dX, const float* add, const float* in_slope, float* dap,
+                      int* rows_out) {
   using G = WinGeo<T, V>;
   const size_t lds = (size_t)G::ParLds * sizeof(float);
   const int ntiles = ceil_div(rows, 16 * G::ParRT);
@@ -498,7 +322,23 @@ int launch_win_params(const float* x, const float* dZ, const float* Aw, const fl
   float* partials = reinterpret_cast<float*>(ws);
   const int vec = aligned16(x) && aligned16(dZ) && aligned16(dX) && aligned16(add);   // (NULL counts as aligned)
   int rc;
-  if (dX) {
+  if (rows_out) *rows_out = grid;
+  if (in_slope) {
+    if constexpr (V == 17 || V == 25) {
+      if (!vec) return fail(COSKAD_ERR_ARG, "gcn_bwd_params (window): the activating form needs 16-byte aligned rows");
+      if (dX) {
+        if ((rc = set_lds(k_win_params<T, V, true, true>, lds))) return rc;
+        hipLaunchKernelGGL((k_win_params<T, V, true, true>), dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, add, rows,
+                           vec, in_slope, dap);
+      } else {
+        if ((rc = set_lds(k_win_params<T, V, false, true>, lds))) return rc;
+        hipLaunchKernelGGL((k_win_params<T, V, false, true>), dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, add, rows,
+                           vec, in_slope, dap);
+      }
+    } else {
+      return fail(COSKAD_ERR_SHAPE, "gcn_bwd_params (window): the activating form is built for 17 / 25 joints");
+    }
+  } else if (dX) {
     if ((rc = set_lds(k_win_params<T, V, true>, lds))) return rc;
     hipLaunchKernelGGL((k_win_params<T, V, true>), dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, add, rows, vec);
   } else {
@@ -546,8 +386,9 @@ int launch_window_gcn(const float* in, float* out, const float* Aw, const float*
 }
 
 int launch_window_params(const float* x, const float* dZ, const float* Aw, const float* Tw, float* dA, float* dT, void* ws,
-                         int accumulate, int rows, int T, int V, hipStream_t st, float* dX, const float* add) {
-#define CALL(T_, V_) return launch_win_params<T_, V_>(x, dZ, Aw, Tw, dA, dT, ws, accumulate, rows, st, dX, add)
+                         int accumulate, int rows, int T, int V, hipStream_t st, float* dX, const float* add, const float* in_slope,
+                         float* dap, int* rows_out) {
+#define CALL(T_, V_) return launch_win_params<T_, V_>(x, dZ, Aw, Tw, dA, dT, ws, accumulate, rows, st, dX, add, in_slope, dap, rows_out)
   COSKAD_DISPATCH_WINDOW(T, V, CALL);
 #undef CALL
 }

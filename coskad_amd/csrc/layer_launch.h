@@ -10,6 +10,7 @@
 #include <type_traits>
 
 extern "C" int coskad_window_ok(int T, int V);   // gcn_window.hip
+extern "C" int coskad_layer_train_window_ok(int T, int V, int Ci, int Co);   // train_window_flat.hip
 
 namespace coskad {
 
@@ -139,12 +140,30 @@ struct LayerStatsArgs {
 void launch_reduce_partials(const float* partials, int rows, int E, double* out, hipStream_t st);
 
 // gcn_window.hip: the mixing kernels of the window lengths 8, 16 and 24 (coskad_window_ok), behind the entry points of
-// stsgcn_fwd.hip / stsgcn_bwd.hip.  dX NULL: parameter gradients only.
+// stsgcn_fwd.hip / stsgcn_bwd.hip.  dX NULL: parameter gradients only.  in_slope (optional; 17 / 25 joints, 16-byte aligned rows):
+// `x` is a pre-activation -- activated on load, dX multiplied by PReLU'(x) on store, the slope-gradient partials of the
+// *rows_out workgroups to dap (summed by the caller).  in_slope NULL: results as without the three arguments, bit for bit.
 int launch_window_gcn(const float* in, float* out, const float* Aw, const float* Tw, int rows, int T, int V, int adjoint,
                       hipStream_t st);
 int launch_window_params(const float* x, const float* dZ, const float* Aw, const float* Tw, float* dA, float* dT, void* ws,
-                         int accumulate, int rows, int T, int V, hipStream_t st, float* dX, const float* add);
+                         int accumulate, int rows, int T, int V, hipStream_t st, float* dX, const float* add,
+                         const float* in_slope = nullptr, float* dap = nullptr, int* rows_out = nullptr);
 size_t window_params_ws_bytes(int T, int V);
+
+// train_window_moments.hip: the statistics pass of a training layer at the window lengths 8, 16 and 24 (17 / 25 joints; 2, 16, 32
+// input channels): Z = gcn(PReLU(in)) -> Zout (NULL: not stored), *rows_out (<= 512) moment partial rows.  `in` / `Zout` 16-byte aligned
+bool window_moments_ok(int T, int V, int Ci);
+int launch_window_moments(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B, int Ci,
+                          int T, int V, int need_x, float* Zout, hipStream_t st, int* rows_out);
+// train_window_flat.hip: the position-wise passes of such a layer over a clip's T V positions (16-byte aligned activations):
+// the stored-Z apply, stage 1 of the backward (<= 1024 partial rows) and its data pass (dXr NULL: dZ alone)
+bool window_flat_ok(int TV, int Ci, int Co);
+int launch_window_apply(const float* Z, const float* in, float* out, const float* wfold, const float* bias, const float* in_slope,
+                        int B, int Ci, int Co, int TV, hipStream_t st);
+int launch_window_stats(const float* in, const float* Zg, const float* dU, const float* in_slope, float* partials, int B, int Ci, int Co,
+                        int TV, int need_q, hipStream_t st, int* rows_out);
+int launch_window_data(const float* in, const float* Z, const float* dU, const float* coef, const float* in_slope, float* dZ, float* dXr,
+                       int B, int Ci, int Co, int TV, hipStream_t st);
 
 // fused_bwd.hip
 int layer_bwd_below_rows(int T_, int V_, int B, int Ci, int Co, int below_Ci);

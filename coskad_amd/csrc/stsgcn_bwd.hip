@@ -1219,6 +1219,7 @@ struct BwdWs {
   float* dap;
   float* btab;
   float* dz;
+  float* dxr;   // window route only: behind dZ
 };
 
 // chain buffer of a layer's stage-1 sums: [rows][E] partial rows, then (8-byte aligned) their E fp64 sums
@@ -1237,7 +1238,9 @@ size_t layer_bwd_ws_bytes(int B, int Ci, int Co, int T, int V) {
   auto al = [](size_t x) { return (x + 255) / 256 * 256; };
   return al(kMaxGridBwd * E * sizeof(float)) + al(E * sizeof(double)) +
          al(coef_floats(Ci, Co) * sizeof(float)) + al((size_t)((B > kMaxGridBwd ? B : kMaxGridBwd) + 1) * sizeof(float)) +
-         al((size_t)kBtabFloats * sizeof(float)) + al((size_t)B * Ci * T * V * sizeof(float));
+         al((size_t)kBtabFloats * sizeof(float)) + al((size_t)B * Ci * T * V * sizeof(float)) +
+         // the window route (launch_layer_bwd_window) keeps dX_res beside dZ
+         (coskad_layer_train_window_ok(T, V, Ci, Co) ? al((size_t)B * Ci * T * V * sizeof(float)) : 0);
 }
 
 static BwdWs carve(void* ws, int B, int Ci, int Co, int T, int V) {
@@ -1250,7 +1253,8 @@ static BwdWs carve(void* ws, int B, int Ci, int Co, int T, int V) {
   w.coef = reinterpret_cast<float*>(p);     p += al(coef_floats(Ci, Co) * sizeof(float));
   w.dap = reinterpret_cast<float*>(p);      p += al((size_t)((B > kMaxGridBwd ? B : kMaxGridBwd) + 1) * sizeof(float));
   w.btab = reinterpret_cast<float*>(p);     p += al((size_t)kBtabFloats * sizeof(float));
-  w.dz = reinterpret_cast<float*>(p);
+  w.dz = reinterpret_cast<float*>(p);       p += al((size_t)B * Ci * T * V * sizeof(float));
+  w.dxr = reinterpret_cast<float*>(p);
   return w;
 }
 
@@ -1580,6 +1584,49 @@ static int launch_layer_bwd(const LayerBwdArgs& a) {
   return launch_layer_gcn_params<T, V>(a, w.dz, w.partials, slope_partials(a, w), grid_d);
 }
 
+// ---- the driver at the window lengths 8, 16 and 24 (coskad_layer_train_window_ok): the same four stages, decomposed -------------
+//   1. P, Q, sdU over flat positions (train_window_flat.hip; two input channels: first_layer.hip as it is) -> sum_stage1_rows
+//   2. stage2_fold, unchanged
+//   3. dZ and dX_res, position-wise, from the coefficient block (train_window_flat.hip); an identity residual's dX_res is dU itself
+//   4. dA, dT and dIn = (gcn^T(dZ) + dX_res) . PReLU'(in) with the slope-gradient partials (gcn_window.hip: launch_window_params)
+static int launch_layer_bwd_window(const char* who, const LayerBwdArgs& a, int T, int V) {
+  const int B = a.B, Ci = a.Ci, Co = a.Co, TV = T * V;
+  hipStream_t st = a.stream;
+  if (!a.Z) return fail(COSKAD_ERR_SHAPE, "%s: window lengths 8, 16 and 24 train on the stored Z (Z must be given)", who);
+  if (a.below.stats) return fail(COSKAD_ERR_SHAPE, "layer_bwd_chain: the layer below's reductions need the fused data kernel");
+  if (a.ws_bytes < layer_bwd_ws_bytes(B, Ci, Co, T, V))
+    return fail(COSKAD_ERR_WORKSPACE, "layer_bwd: workspace %zu < %zu bytes", a.ws_bytes, layer_bwd_ws_bytes(B, Ci, Co, T, V));
+  BwdWs w = carve(a.ws, B, Ci, Co, T, V);
+  if (a.stats_only.out) w.partials = a.stats_only.out;
+  int rc, rows = 0;
+  if (!a.chain.stats) {
+    const int need_q = a.Wr != nullptr;
+    if (Ci <= 4) rc = launch_first_stats(a.in, a.Z, a.dU, a.in_slope, w.partials, B, Ci, Co, TV, need_q, kMaxGridBwd, st, &rows);
+    else rc = launch_window_stats(a.in, a.Z, a.dU, a.in_slope, w.partials, B, Ci, Co, TV, need_q, st, &rows);
+    if (rc) return rc;
+    if ((rc = sum_stage1_rows(a, w, rows))) return rc;
+  }
+  if (a.stats_only.out) return COSKAD_OK;
+  if ((rc = stage2_fold(a, w, TV, false))) return rc;
+  const bool ident = a.Wr == nullptr;                       // dX_res = dU (the fold writes Br = I, Kr = 0, kr = 0)
+  float* dxr = (a.g.dIn && !ident) ? w.dxr : nullptr;
+  if ((rc = launch_window_data(a.in, a.Z, a.dU, w.coef, a.in_slope, w.dz, dxr, B, Ci, Co, TV, st))) return rc;
+  const float* add = a.g.dIn ? (ident ? a.dU : w.dxr) : nullptr;
+  float* dap = a.g.dIn ? slope_partials(a, w) : nullptr;   // (no input gradient: nobody back-propagates through that PReLU)
+  int grid = 0;
+  {
+    ProbeScope probe(KID_GCN_PARAMS, Ci, Co, st);           // (the parameter kernel and the sum of its partial rows)
+    rc = launch_window_params(a.in, w.dz, a.A, a.Tm, a.g.dA, a.g.dT, w.partials, a.accumulate, B * Ci, T, V, st, a.g.dIn, add,
+                              a.in_slope, dap, &grid);
+  }
+  if (rc) return rc;
+  if (dap) {
+    hipLaunchKernelGGL(k_sum_to, dim3(1), dim3(256), 0, st, dap, grid, a.g.dslope_in, a.accumulate);
+    if ((rc = check_launch("bwd_dslope"))) return rc;
+  }
+  return COSKAD_OK;
+}
+
 }  // namespace coskad
 
 namespace coskad {
@@ -1636,7 +1683,16 @@ static int check_layer_bwd(const char* who, const LayerBwdArgs& a, unsigned need
 }
 constexpr unsigned kNeedLayer = kNeedDU | kNeedFold | kNeedCo;   // a whole layer backward
 
-static int dispatch_layer_bwd(const LayerBwdArgs& a, int T, int V) {
+// who: the entry's name in messages
+static int dispatch_layer_bwd(const char* who, const LayerBwdArgs& a, int T, int V) {
+  if (coskad_window_ok(T, V) && !a.dz_ext) {
+    // window geometries: rows are staged as 16-byte vectors
+    if ((size_t)a.in & 15) return fail(COSKAD_ERR_ARG, "%s: `in` must be 16-byte aligned at window lengths 8, 16 and 24", who);
+    if ((size_t)a.Z & 15) return fail(COSKAD_ERR_ARG, "%s: `Z` must be 16-byte aligned at window lengths 8, 16 and 24", who);
+    if ((size_t)a.dU & 15) return fail(COSKAD_ERR_ARG, "%s: `dU` must be 16-byte aligned at window lengths 8, 16 and 24", who);
+    if ((size_t)a.g.dIn & 15) return fail(COSKAD_ERR_ARG, "%s: `dIn` must be 16-byte aligned at window lengths 8, 16 and 24", who);
+    if (coskad_layer_train_window_ok(T, V, a.Ci, a.Co)) return launch_layer_bwd_window(who, a, T, V);
+  }
 #define CALL(T_, V_) return launch_layer_bwd<T_, V_>(a)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL
@@ -1717,7 +1773,7 @@ int coskad_layer_bwd_z_f32(const float* in, const float* dU, const float* A, con
       .ws = ws, .ws_bytes = ws_bytes, .accumulate = accumulate, .B = B, .Ci = Ci, .Co = Co, .stream = stream};
   if (int rc = check_layer_bwd("layer_bwd", a, kNeedLayer | kNeedGcnGrads)) return rc;
   ProbeScope layer_probe(KID_LAYER_BWD, Ci, Co, stream);   // bench.py: the whole layer backward (all its launches)
-  return dispatch_layer_bwd(a, T, V);
+  return dispatch_layer_bwd("layer_bwd", a, T, V);
 }
 
 /* The same, Z recomputed. */
@@ -1783,7 +1839,7 @@ int coskad_layer_bwd_chain_f32(const float* in, const float* dU, const float* A,
     a.below.Ci = below_Ci;
   }
   ProbeScope layer_probe(KID_LAYER_BWD, Ci, Co, stream);
-  return dispatch_layer_bwd(a, T, V);
+  return dispatch_layer_bwd(who, a, T, V);
 }
 
 /* Stage 1 of coskad_layer_bwd_z_f32 ALONE, into a chain buffer (SyncBN: the caller adds the other ranks' fp64 sums in place, then
@@ -1807,7 +1863,7 @@ int coskad_layer_bwd_stats_f32(const float* in, const float* dU, const float* A,
   if ((size_t)stats_out & 7) return fail(COSKAD_ERR_ARG, "layer_bwd_stats: stats_out must be 8-byte aligned");
   if (stats_out_bytes < coskad_layer_bwd_stats_floats(B, Ci, Co, T, V) * sizeof(float))
     return fail(COSKAD_ERR_WORKSPACE, "layer_bwd_stats: stats_out %zu bytes too small", stats_out_bytes);
-  return dispatch_layer_bwd(a, T, V);
+  return dispatch_layer_bwd("layer_bwd_stats", a, T, V);
 }
 
 /* Stages 1-3 of coskad_layer_bwd_f32 with dZ [B,Ci,T,V] written to the caller's buffer; stage 4 is
@@ -1824,7 +1880,7 @@ int coskad_layer_bwd_data_f32(const float* in, const float* dU, const float* A, 
             .dber = dbeta_r, .dslope_in = dslope_in},
       .ws = ws, .ws_bytes = ws_bytes, .accumulate = accumulate, .B = B, .Ci = Ci, .Co = Co, .stream = stream, .dz_ext = dZ};
   if (int rc = check_layer_bwd("layer_bwd_data", a, kNeedLayer | kNeedDz)) return rc;
-  return dispatch_layer_bwd(a, T, V);
+  return dispatch_layer_bwd("layer_bwd_data", a, T, V);
 }
 
 size_t coskad_layer_gcn_params_ws_bytes(int T, int V) { return coskad_gcn_bwd_params_ws_bytes(T, V); }

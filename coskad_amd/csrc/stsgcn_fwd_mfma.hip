@@ -245,6 +245,14 @@ extern "C" int coskad_layer_apply_z_f32(const float* Z, const float* in, float* 
                                         hipStream_t stream) {
   if (!Z || !in || !out || !A || !Tm || !wfold || !bias) return fail(COSKAD_ERR_ARG, "layer_apply_z: null pointer");
   if (B <= 0 || Ci <= 0 || Co <= 0 || Co > 64 || Ci > 64) return fail(COSKAD_ERR_ARG, "layer_apply_z: B=%d Ci=%d Co=%d", B, Ci, Co);
+  if (coskad_window_ok(T, V)) {
+    // window lengths 8, 16 and 24: rows are staged as 16-byte vectors; the flat-position GEMM of train_window_flat.hip
+    if ((size_t)Z & 15) return fail(COSKAD_ERR_ARG, "layer_apply_z: `Z` must be 16-byte aligned at window lengths 8, 16 and 24");
+    if ((size_t)in & 15) return fail(COSKAD_ERR_ARG, "layer_apply_z: `in` must be 16-byte aligned at window lengths 8, 16 and 24");
+    if ((size_t)out & 15) return fail(COSKAD_ERR_ARG, "layer_apply_z: `out` must be 16-byte aligned at window lengths 8, 16 and 24");
+    if (!out_slope && Ci > 4 && coskad_layer_train_window_ok(T, V, Ci, Co))
+      return launch_window_apply(Z, in, out, wfold, bias, in_slope, B, Ci, Co, T * V, stream);
+  }
   // a handful of input channels (the first layer): plain FMAs on full-line stores (first_layer.hip)
   if (!out_slope && Ci <= 4 && (T * V) % 4 == 0) return launch_first_apply(Z, in, out, wfold, bias, in_slope, B, Ci, Co, T * V, stream);
   // default geometry, 16 / 32 input channels, pre-activation output: the wave-per-clip K-ring GEMM (fused_apply.hip)

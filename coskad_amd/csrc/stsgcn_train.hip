@@ -377,7 +377,29 @@ static int check_layer_stats(const char* who, const LayerStatsArgs& a, unsigned 
   return COSKAD_OK;
 }
 
-static int dispatch_train_stats(const LayerStatsArgs& a, int T, int V) {
+// The statistics pass at the window lengths 8, 16 and 24 (train_window_moments.hip), then the same fold
+static int launch_train_stats_window(const LayerStatsArgs& a, int T, int V) {
+  const int B = a.B, Ci = a.Ci, Co = a.Co;
+  if (a.ws_bytes < train_stats_ws_bytes(Ci))
+    return fail(COSKAD_ERR_WORKSPACE, "train_stats: workspace %zu < %zu bytes", a.ws_bytes, train_stats_ws_bytes(Ci));
+  const int E = 2 * (Ci * Ci + Ci);
+  float* partials = reinterpret_cast<float*>(a.ws);
+  double* red = reinterpret_cast<double*>(reinterpret_cast<char*>(a.ws) + round_up((int)(kMaxGrid * (size_t)E * sizeof(float)), 256));
+  const int need_x = a.sums ? 1 : (a.p.Wr != nullptr);
+  int rows = 0;
+  if (int rc = launch_window_moments(a.in, a.A, a.Tm, a.in_slope, partials, B, Ci, T, V, need_x, a.Zout, a.stream, &rows)) return rc;
+  if (a.sums) return launch_reduce_fold(partials, rows, a.sums, 0.0, BnConvParams{}, FoldOut{}, Ci, Co, a.stream);
+  return launch_reduce_fold(partials, rows, red, (double)B * T * V, a.p, a.out, Ci, Co, a.stream);
+}
+
+// who: the entry's name in messages; full: the call folds (a layer Ci -> Co), else it stops behind the moment sums (Ci alone)
+static int dispatch_train_stats(const char* who, const LayerStatsArgs& a, int T, int V, bool full) {
+  if (coskad_window_ok(T, V)) {
+    // window geometries: rows are staged as 16-byte vectors
+    if ((size_t)a.in & 15) return fail(COSKAD_ERR_ARG, "%s: `in` must be 16-byte aligned at window lengths 8, 16 and 24", who);
+    if ((size_t)a.Zout & 15) return fail(COSKAD_ERR_ARG, "%s: `Z` must be 16-byte aligned at window lengths 8, 16 and 24", who);
+    if (full ? coskad_layer_train_window_ok(T, V, a.Ci, a.Co) != 0 : window_moments_ok(T, V, a.Ci)) return launch_train_stats_window(a, T, V);
+  }
 #define CALL(T_, V_) return launch_train_stats<T_, V_>(a)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL
@@ -410,7 +432,7 @@ int coskad_layer_train_stats_z_f32(const float* in, const float* A, const float*
       .Zout = Z, .ws = ws, .ws_bytes = ws_bytes, .B = B, .Ci = Ci, .Co = Co, .stream = stream};
   if (int rc = check_layer_stats("layer_train_stats", a, kNeedInput | kNeedFold | kNeedWs)) return rc;
   if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_train_stats: B=%d Ci=%d Co=%d", B, Ci, Co);
-  return dispatch_train_stats(a, T, V);
+  return dispatch_train_stats("layer_train_stats", a, T, V, true);
 }
 
 /* The same, Z not stored. */
@@ -462,7 +484,7 @@ int coskad_layer_train_moments_f32(const float* in, const float* A, const float*
   if (int rc = check_layer_stats("layer_train_moments", a, kNeedInput | kNeedSums | kNeedWs)) return rc;
   if (B <= 0 || Ci <= 0) return fail(COSKAD_ERR_ARG, "layer_train_moments: B=%d Ci=%d", B, Ci);
   if ((size_t)sums & 7) return fail(COSKAD_ERR_ARG, "layer_train_moments: sums must be 8-byte aligned");
-  return dispatch_train_stats(a, T, V);
+  return dispatch_train_stats("layer_train_moments", a, T, V, false);
 }
 
 /* step 1 (moment partials written by the previous layer's coskad_layer_apply_next_f32): partials [rows][2 (Ci^2 + Ci)] -> sums */

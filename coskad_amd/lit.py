@@ -114,6 +114,9 @@ class LitEncoder(nn.Module):
         # `flat_plain_gcn` (not a key of the reference's yamls either): the Learnable_GCN / Static_GCN encoders train on the flat step
         # with the fused layer kernels unless the yaml says `flat_plain_gcn: false` (then: the autograd step)
         extra["flat_plain_gcn"] = bool(getattr(self.args, "flat_plain_gcn", True))
+        # `fused_window` (not a key of the reference's yamls either): encoders of `dataset_seg_len` 8 / 16 / 24 train on the stored-Z layer
+        # kernels where those are built unless the yaml says `fused_window: false` (then: the composed path)
+        extra["fused_window"] = bool(getattr(self.args, "fused_window", True))
         self._engine = make_train_step(self.model, lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)),
                                      head="poincare" if self.hyperbolic else ("mahalanobis" if maha else "euclidean"), **extra)
         self._epoch = 0

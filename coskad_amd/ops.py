@@ -57,6 +57,21 @@ def window_ok(T: int, V: int) -> bool:
     return T in WINDOW_LENGTHS and V in JOINT_LAYOUTS
 
 
+TRAIN_WINDOW_JOINTS = (17, 25)          # joint layouts, input and output widths of the stored-Z training kernels at those window
+TRAIN_WINDOW_CIN = (2, 16, 32)          # lengths (csrc/train_window_moments.hip, csrc/train_window_flat.hip)
+TRAIN_WINDOW_COUT = (16, 32, 64)
+# geometries measured no faster than the composed path stay switched off here: none
+TRAIN_WINDOW_OFF = frozenset()
+
+
+def layer_train_window_ok(T: int, V: int, Ci: int, Co: int) -> bool:
+    """Host arithmetic of `coskad_layer_train_window_ok`: a (Ci -> Co) layer of window length 8 / 16 / 24 trains on the stored-Z layer
+    kernels (engine.chain_forward / chain_backward run it as they run a 12-frame layer).  False at T = 12.  Restated here so that
+    building a train step needs no native library; tests/test_train_window_host.py holds the two in agreement."""
+    return (T in WINDOW_LENGTHS and V in TRAIN_WINDOW_JOINTS and Ci in TRAIN_WINDOW_CIN and Co in TRAIN_WINDOW_COUT
+            and (T, V) not in TRAIN_WINDOW_OFF)
+
+
 def gcn(x: Tensor, A: Tensor, Tm: Tensor, adjoint: bool = False) -> Tensor:
     """ConvTemporalGraphical.forward (reference stsgcn.py:143-156) or its adjoint."""
     N, C, T, V = x.shape

@@ -153,6 +153,30 @@ class _TileRun(_Segment):
                                      in_slope_grad=in_slope_grad)
 
 
+def _is_window(m) -> bool:
+    """a layer that is `is_wide` ONLY because of its window length (8 / 16 / 24) and that the stored-Z training kernels take at that
+    length: <= 64 channels, no dropout, BatchNorms the shared statistics kernel can serve (layer_tensors checks them)"""
+    from .models.graph_layers.stsgcn import WIDE_CHANNELS, layer_tensors
+    if (max(m.in_channels, m.out_channels) > WIDE_CHANNELS or m.dropout > 0 or not ops.window_ok(m.time_dim, m.joints_dim)
+            or not ops.layer_train_window_ok(m.time_dim, m.joints_dim, m.in_channels, m.out_channels)):
+        return False
+    try:
+        layer_tensors(m)
+    except NotImplementedError:
+        return False
+    return True
+
+
+class _WindowRun(_TileRun):
+    """a run of layers of window length 8 / 16 / 24 on the stored-Z layer kernels (csrc/train_window_*.hip): the same
+    engine.chain_forward / chain_backward calls, whose C-ABI entry points take the geometry; main stream, no SyncBN.  Hands over a
+    pre-activation plus its slope, like a tile run."""
+    kind = 'window'
+
+    def __init__(self, modules, fp: "FlatParams", prefixes) -> None:
+        super().__init__(modules, fp, prefixes, side=None, sync=None)
+
+
 class _WideLayer(_Segment):
     """a layer beyond the tile kernels on its composed path (stsgcn.wide_forward / wide_backward); hands over an activated output"""
     kind = 'wide'
@@ -258,12 +282,14 @@ class _FlatStack:
     HIP path (stsgcn.wide_forward / wide_backward: explicit forward and backward, no autograd), gradients written to the flat
     buffer's views; layers the commuted / narrow-output kernels take run there."""
 
-    def __init__(self, modules, fp: "FlatParams", prefix: str, first: int = 0, plain: bool = False, side=None, sync=None) -> None:
+    def __init__(self, modules, fp: "FlatParams", prefix: str, first: int = 0, plain: bool = False, side=None, sync=None,
+                 window: bool = False) -> None:
         """modules: the layers first, first + 1, .. of the nn.Sequential whose parameters are named `{prefix}{index}.`
         plain: no commuted / narrow-output segments (those layers stay in the tile runs); side, sync: the tile runs' side stream /
-        SyncBN process group"""
+        SyncBN process group; window: layers of window length 8 / 16 / 24 run on the stored-Z layer kernels where those are built
+        (`window` runs) instead of the composed path"""
         dec = prefix.startswith("decoder")
-        kinds = ['wide' if m.is_wide else 'narrow' if not plain and _is_narrow(m) else
+        kinds = [('window' if window and _is_window(m) else 'wide') if m.is_wide else 'narrow' if not plain and _is_narrow(m) else
                  'commute' if not plain and _is_commute(m, dec) else 'tile' for m in modules]
         single = {'wide': _WideLayer, 'narrow': _NarrowLayer, 'commute': _CommuteLayer}
         self.segs = []
@@ -274,6 +300,10 @@ class _FlatStack:
                 while j < n and kinds[j] == 'tile':
                     j += 1
                 self.segs.append(_TileRun(modules[i:j], fp, [f"{prefix}{first + k}." for k in range(i, j)], side=side, sync=sync))
+            elif kinds[i] == 'window':
+                while j < n and kinds[j] == 'window':
+                    j += 1
+                self.segs.append(_WindowRun(modules[i:j], fp, [f"{prefix}{first + k}." for k in range(i, j)]))
             else:
                 self.segs.append(single[kinds[i]](modules[i], fp, f"{prefix}{first + i}."))
             i = j
@@ -540,7 +570,9 @@ class STSETrainStep(_FlatStep, _OneClassHead):
 
     def __init__(self, model, lr: float = 1e-4, alpha: float = 1e-6, head: str = 'euclidean',
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, use_graph: bool = False,
-                 side_stream: bool = False, sync_bn: bool = False) -> None:
+                 side_stream: bool = False, sync_bn: bool = False, fused_window: bool = False) -> None:
+        """fused_window: encoder layers of window length 8 / 16 / 24 train on the stored-Z layer kernels where those are built
+        (`window` runs of the stack; off: the composed path, as before)"""
         from .models.sts.ae import STSE
         from .models.common.components import MLP
         self.mlp = isinstance(model.btlnk, MLP)
@@ -580,7 +612,7 @@ class STSETrainStep(_FlatStep, _OneClassHead):
         else:
             plain = not wide and (use_graph or side_stream or sync_bn or not any(_is_commute(l) for l in model.encoder.model))
             self.stack = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.", plain=plain, side=self.side,
-                                    sync=self.sync_group)
+                                    sync=self.sync_group, window=fused_window)
         # gradient buckets for the data-parallel all-reduce: [encoder | bottleneck]; the bottleneck parameters are the
         # tail of the flat buffer (named_parameters order) and their gradients are final before the encoder backward
         names = self.fp.names
@@ -887,11 +919,13 @@ class AutogradTrainStep(_OneClassHead):
             return self.reg_scale * sum((p.float() ** 2).sum() for p in self.reg_params).reshape(1)
 
 
-def make_train_step(model, flat_plain_gcn: bool = False, **kw):
+def make_train_step(model, flat_plain_gcn: bool = False, fused_window: bool = False, **kw):
     """STSETrainStep (flat buffers, fused Adam, no autograd) for every STS-GCN encoder -- tile kernels and wide layers alike -- with a
     linear or in-width mlp projector, and with `flat_plain_gcn` for the plain-GCN encoders (Learnable_GCN / Static_GCN) behind such
     a projector too (fused layer kernels, csrc/plain_gcn.hip; the wrappers ask for it).  AutogradTrainStep for what is left:
-    projectors / latents beyond the bottleneck kernels, and the plain-GCN encoders without `flat_plain_gcn`."""
+    projectors / latents beyond the bottleneck kernels, and the plain-GCN encoders without `flat_plain_gcn`.
+    `fused_window`: an STS-GCN encoder of window length 8 / 16 / 24 runs its layers on the stored-Z layer kernels where those are built
+    (csrc/train_window_*.hip; the wrappers ask for it) instead of the composed path; still eager, on the main stream."""
     from .models.common.components import MLP, Encoder
     btl = getattr(model, 'btlnk', None)
     enc = getattr(model, 'encoder', None)
@@ -907,7 +941,7 @@ def make_train_step(model, flat_plain_gcn: bool = False, **kw):
             kw.pop('use_graph', None); kw.pop('side_stream', None)
             if kw.get('sync_bn') and not (dist.is_available() and dist.is_initialized() and dist.get_world_size(kw.get('process_group')) > 1):
                 kw.pop('sync_bn')
-        return STSETrainStep(model, **kw)
+        return STSETrainStep(model, fused_window=fused_window, **kw)
     kw.pop('use_graph', None); kw.pop('side_stream', None)
     if kw.pop('sync_bn', False):
         # the optional key `sync_batchnorm` (absent in the reference): with one rank there is nothing to synchronise

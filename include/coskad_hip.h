@@ -109,8 +109,21 @@ int coskad_layer_train_stats_f32(const float* in, const float* A, const float* T
                                  size_t ws_bytes, int B, int Ci, int Co, int T, int V,
                                  hipStream_t stream);
 
+/* 1 when a (Ci -> Co) ST_GCNN layer of window length T (8, 16, 24) trains on the stored-Z layer kernels (statistics pass, apply,
+ * backward); 0 otherwise, T = 12 included (the tile kernels' own geometry).  Host arithmetic.
+ * Holds for T in {8, 16, 24} x V in {17, 25} x Ci in {2, 16, 32} x Co in {16, 32, 64} (csrc/train_window_moments.hip,
+ * csrc/train_window_flat.hip, csrc/gcn_window.hip).  Where it holds, coskad_layer_train_stats_z_f32, coskad_layer_train_stats_f32,
+ * coskad_layer_apply_z_f32, coskad_layer_bwd_z_f32, coskad_layer_bwd_chain_f32, coskad_layer_bwd_stats_f32 and
+ * coskad_layer_bwd_ws_bytes serve the layer with the contracts stated for T = 12 (the backward needs the stored Z; `below_*` is
+ * refused; coskad_layer_bwd_below_rows is 0); coskad_layer_train_moments_f32 serves every such (T, V, Ci).
+ * Alignment at EVERY window geometry of coskad_window_ok: the activation pointers of these entry points (`in`, `Z`, `dU`, `dIn`, `out`)
+ * must be 16-byte aligned -- rows are staged as 16-byte vectors -- else COSKAD_ERR_ARG naming the pointer, before anything is launched
+ * and before the shape is judged.  Parameters, gradients and tables need 4-byte alignment only. */
+int coskad_layer_train_window_ok(int T, int V, int Ci, int Co);
+
 /* Stored-Z variant of the training forward: the statistics pass also writes Z = gcn(PReLU(in)) [B,Ci,T,V]; the layer
- * is then a streaming GEMM over Z and `in` (no staging, no mixing recompute), and the backward reads Z as well. */
+ * is then a streaming GEMM over Z and `in` (no staging, no mixing recompute), and the backward reads Z as well.
+ * (T, V): T = 12, or a window geometry where coskad_layer_train_window_ok holds (see there for the alignment rule). */
 int coskad_layer_train_stats_z_f32(const float* in, const float* A, const float* Tm, const float* in_slope,
                                    const float* Wt, const float* bt, const float* gamma_t,
                                    const float* beta_t, float* rmean_t, float* rvar_t, long long* nbt_t,
@@ -119,6 +132,9 @@ int coskad_layer_train_stats_z_f32(const float* in, const float* A, const float*
                                    float momentum, float* wfold, float* bias, float* stat, void* ws,
                                    size_t ws_bytes, int B, int Ci, int Co, int T, int V,
                                    hipStream_t stream, float* Z);
+/* U = Wz Z + Wx PReLU_in(in) + b from the stored Z.  (T, V): T = 12, or a window geometry of coskad_layer_train_window_ok -- see its comment for the set and the 16-byte alignment of the activation pointers: at EVERY window length 8 / 16 / 24
+ * (coskad_window_ok), the few-channel first-layer route and geometries no kernel serves included, a misaligned `Z`, `in` or `out` is
+ * COSKAD_ERR_ARG naming the pointer (those routes load 16-byte vectors too), before the shape is judged. */
 int coskad_layer_apply_z_f32(const float* Z, const float* in, float* out, const float* A, const float* Tm,
                              const float* wfold, const float* bias, const float* in_slope, const float* out_slope,
                              int B, int Ci, int Co, int T, int V, hipStream_t stream);
@@ -262,6 +278,7 @@ int coskad_mlp_head_bwd_f32(const float* y1, const float* stat, const float* gam
 
 /* ---- backward of one ST_GCNN_layer (autograd of stsgcn.py:94-116 in training mode) ------ */
 
+/* (window geometries of coskad_layer_train_window_ok: what that route needs -- one more [B, Ci, T, V] buffer than at T = 12) */
 size_t coskad_layer_bwd_ws_bytes(int B, int Ci, int Co, int T, int V);
 
 /* 1 when one clip of a (Ci -> Co) ST_GCNN layer fits the LDS-resident tile kernels (forward, statistics, backward);
@@ -283,6 +300,7 @@ int coskad_layer_fits(int Ci, int Co, int T, int V);
  * a 2-channel layer, 16 -> 32 above a 32-channel layer, 32 -> 64 above a 16-channel layer: the default stack). */
 int coskad_layer_bwd_below_rows(int B, int Ci, int Co, int below_Ci, int T, int V);
 size_t coskad_layer_bwd_below_floats(int B, int Ci, int Co, int below_Ci, int T, int V);
+/* (T, V): T = 12, or a window geometry of coskad_layer_train_window_ok -- see its comment for the set and the 16-byte alignment of the activation pointers (`in`, `Z`, `dU`, `dIn`); there `below_*` is refused. */
 int coskad_layer_bwd_chain_f32(const float* in, const float* dU, const float* A, const float* Tm,
                                const float* in_slope, const float* stat, const float* Wt, const float* gamma_t,
                                const float* Wr, const float* gamma_r, float* dIn, float* dA, float* dT, float* dWt,
@@ -301,6 +319,9 @@ int coskad_layer_bwd_chain_f32(const float* in, const float* dU, const float* A,
  * Backward: coskad_layer_bwd_stats_f32 (stage 1 alone, into a chain buffer: rows, then sums at coskad_layer_bwd_sums_offset floats)
  * or the chain buffer the layer above filled -> all-reduce the sums in place -> coskad_layer_bwd_chain_f32 with stats_in and
  * stats_count = global clips x T x V (0: this batch). */
+/* coskad_layer_train_moments_f32, coskad_layer_bwd_stats_f32 -- (T, V): T = 12, or the window lengths 8 / 16 / 24 at 17 / 25 joints with
+ * Ci in {2, 16, 32} (and, for the backward's stage 1, coskad_layer_train_window_ok(T, V, Ci, Co)); activation pointers (`in`, `Z`, `dU`)
+ * 16-byte aligned there, as coskad_layer_train_window_ok's comment states. */
 int coskad_layer_train_moments_f32(const float* in, const float* A, const float* Tm, const float* in_slope, float* Z, double* sums,
                                    void* ws, size_t ws_bytes, int B, int Ci, int T, int V, hipStream_t stream);
 int coskad_layer_moment_sums_f32(const float* partials, int rows, int Ci, double* sums, hipStream_t stream);
@@ -332,6 +353,8 @@ int coskad_layer_bwd_f32(const float* in, const float* dU, const float* A, const
 
 /* coskad_layer_bwd_f32 reading the stored Z = gcn(PReLU(in)) of coskad_layer_train_stats_z_f32 instead of recomputing
  * the mixing in its reduction and data kernels (Z == NULL: identical to coskad_layer_bwd_f32). */
+/* (T, V): T = 12, or a window geometry of coskad_layer_train_window_ok -- see its comment for the set and the 16-byte alignment of the activation pointers (`in`, `Z`, `dU`, `dIn`);
+ * there Z must be given. */
 int coskad_layer_bwd_z_f32(const float* in, const float* dU, const float* A, const float* Tm,
                            const float* in_slope, const float* stat, const float* Wt, const float* gamma_t,
                            const float* Wr, const float* gamma_r, float* dIn, float* dA, float* dT, float* dWt,
