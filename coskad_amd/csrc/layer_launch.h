@@ -11,6 +11,7 @@
 
 extern "C" int coskad_window_ok(int T, int V);   // gcn_window.hip
 extern "C" int coskad_layer_train_window_ok(int T, int V, int Ci, int Co);   // train_window_flat.hip
+extern "C" int coskad_layer_train_window_narrow_ok(int T, int V, int Ci, int Co);
 
 namespace coskad {
 

@@ -1240,7 +1240,7 @@ size_t layer_bwd_ws_bytes(int B, int Ci, int Co, int T, int V) {
          al(coef_floats(Ci, Co) * sizeof(float)) + al((size_t)((B > kMaxGridBwd ? B : kMaxGridBwd) + 1) * sizeof(float)) +
          al((size_t)kBtabFloats * sizeof(float)) + al((size_t)B * Ci * T * V * sizeof(float)) +
          // the window route (launch_layer_bwd_window) keeps dX_res beside dZ
-         (coskad_layer_train_window_ok(T, V, Ci, Co) ? al((size_t)B * Ci * T * V * sizeof(float)) : 0);
+         ((coskad_layer_train_window_ok(T, V, Ci, Co) || coskad_layer_train_window_narrow_ok(T, V, Ci, Co)) ? al((size_t)B * Ci * T * V * sizeof(float)) : 0);
 }
 
 static BwdWs carve(void* ws, int B, int Ci, int Co, int T, int V) {
@@ -1584,8 +1584,9 @@ static int launch_layer_bwd(const LayerBwdArgs& a) {
   return launch_layer_gcn_params<T, V>(a, w.dz, w.partials, slope_partials(a, w), grid_d);
 }
 
-// ---- the driver at the window lengths 8, 16 and 24 (coskad_layer_train_window_ok): the same four stages, decomposed -------------
-//   1. P, Q, sdU over flat positions (train_window_flat.hip; two input channels: first_layer.hip as it is) -> sum_stage1_rows
+// ---- the driver at the window lengths 8, 16 and 24 (coskad_layer_train_window_ok, or coskad_layer_train_window_narrow_ok for the
+// few-channel (4 -> 2) layer): the same four stages, decomposed
+//   1. P, Q, sdU over flat positions (train_window_flat.hip; two or four input channels: first_layer.hip as it is) -> sum_stage1_rows
 //   2. stage2_fold, unchanged
 //   3. dZ and dX_res, position-wise, from the coefficient block (train_window_flat.hip); an identity residual's dX_res is dU itself
 //   4. dA, dT and dIn = (gcn^T(dZ) + dX_res) . PReLU'(in) with the slope-gradient partials (gcn_window.hip: launch_window_params)
@@ -1691,7 +1692,8 @@ static int dispatch_layer_bwd(const char* who, const LayerBwdArgs& a, int T, int
     if ((size_t)a.Z & 15) return fail(COSKAD_ERR_ARG, "%s: `Z` must be 16-byte aligned at window lengths 8, 16 and 24", who);
     if ((size_t)a.dU & 15) return fail(COSKAD_ERR_ARG, "%s: `dU` must be 16-byte aligned at window lengths 8, 16 and 24", who);
     if ((size_t)a.g.dIn & 15) return fail(COSKAD_ERR_ARG, "%s: `dIn` must be 16-byte aligned at window lengths 8, 16 and 24", who);
-    if (coskad_layer_train_window_ok(T, V, a.Ci, a.Co)) return launch_layer_bwd_window(who, a, T, V);
+    if (coskad_layer_train_window_ok(T, V, a.Ci, a.Co) || coskad_layer_train_window_narrow_ok(T, V, a.Ci, a.Co))
+      return launch_layer_bwd_window(who, a, T, V);
   }
 #define CALL(T_, V_) return launch_layer_bwd<T_, V_>(a)
   COSKAD_DISPATCH_TV(T, V, CALL);

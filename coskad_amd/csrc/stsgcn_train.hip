@@ -398,7 +398,9 @@ static int dispatch_train_stats(const char* who, const LayerStatsArgs& a, int T,
     // window geometries: rows are staged as 16-byte vectors
     if ((size_t)a.in & 15) return fail(COSKAD_ERR_ARG, "%s: `in` must be 16-byte aligned at window lengths 8, 16 and 24", who);
     if ((size_t)a.Zout & 15) return fail(COSKAD_ERR_ARG, "%s: `Z` must be 16-byte aligned at window lengths 8, 16 and 24", who);
-    if (full ? coskad_layer_train_window_ok(T, V, a.Ci, a.Co) != 0 : window_moments_ok(T, V, a.Ci)) return launch_train_stats_window(a, T, V);
+    if (full ? (coskad_layer_train_window_ok(T, V, a.Ci, a.Co) || coskad_layer_train_window_narrow_ok(T, V, a.Ci, a.Co))
+             : window_moments_ok(T, V, a.Ci))
+      return launch_train_stats_window(a, T, V);
   }
 #define CALL(T_, V_) return launch_train_stats<T_, V_>(a)
   COSKAD_DISPATCH_TV(T, V, CALL);

@@ -319,10 +319,12 @@ int launch_window_apply(const float* Z, const float* in, float* out, const float
 }
 
 // dZ = Bt dU + Kt Z + kt (always) and dX_res = Br dU + Kr PReLU(in) + kr (dXr != NULL) from the coefficient block of k_bwd_fold:
-// [wDZ (Co + Ci) x CiP][kt CiP][wDX (Co + Ci) x CiP][kr CiP], CiP = round_up(Ci, 16).  Ci: 2 (the first layer), 16, 32
+// [wDZ (Co + Ci) x CiP][kt CiP][wDX (Co + Ci) x CiP][kr CiP], CiP = round_up(Ci, 16).  Ci: 2 (the first layer), 16, 32; or the
+// few-channel (4 -> 2) layer of coskad_layer_train_window_narrow_ok: M = 4 output rows, K = 6 table rows padded with zero rows
 int launch_window_data(const float* in, const float* Z, const float* dU, const float* coef, const float* in_slope, float* dZ, float* dXr,
                        int B, int Ci, int Co, int TV, hipStream_t st) {
-  if (TV % 4 || !(Ci == 2 || Ci == 16 || Ci == 32) || !(Co == 16 || Co == 32 || Co == 64))
+  const bool wide = (Ci == 2 || Ci == 16 || Ci == 32) && (Co == 16 || Co == 32 || Co == 64), narrow = Ci == 4 && Co == 2;
+  if (TV % 4 || !(wide || narrow))
     return fail(COSKAD_ERR_SHAPE, "layer_bwd (window): unsupported (%d positions, %d -> %d)", TV, Ci, Co);
   const int CiP = round_up(Ci, 16);
   FlatGemm g{};
@@ -368,6 +370,13 @@ extern "C" {
 int coskad_layer_train_window_ok(int T, int V, int Ci, int Co) {
   return (T == 8 || T == 16 || T == 24) && (V == 17 || V == 25) && (Ci == 2 || Ci == 16 || Ci == 32) &&
          (Co == 16 || Co == 32 || Co == 64);
+}
+
+/* 1 when a FEW-CHANNEL (Ci -> Co) layer of window length T (8, 16, 24) trains on the stored-Z layer kernels: the virtual (4 -> 2)
+ * layer a stack's last (C -> 2) layer runs as by commutation.  A set of its own beside coskad_layer_train_window_ok.  Host
+ * arithmetic. */
+int coskad_layer_train_window_narrow_ok(int T, int V, int Ci, int Co) {
+  return (T == 8 || T == 16 || T == 24) && (V == 17 || V == 25) && Ci == 4 && Co == 2;
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// The statistics pass of a TRAINING layer at the window lengths 8, 16 and 24 (17 / 25 joints; 2, 16 or 32 input channels):
+// The statistics pass of a TRAINING layer at the window lengths 8, 16 and 24 (17 / 25 joints; 2, 4, 16 or 32 input channels):
 //     X = PReLU_in(in),  Z = gcn(X) -> Zout,  one partial row [sum x x^T | sum x | sum z z^T | sum z] per workgroup
 // (reference: models/graph_layers/stsgcn.py:56-80 and the batch statistics of both BatchNorms, 94-110; the moment form is the one of
 // stsgcn_train.hip, whose launch_reduce_fold finishes the pass unchanged).
@@ -7,8 +7,9 @@
 // waves, a wave's B operands of both mixes in its registers for the whole launch, K = V zero-padded to whole k-steps on both operands
 // (window_ops.h).  A workgroup pass takes RT row tiles = whole clips (RT even, so that a 32-channel clip's two tiles travel together).
 // The Gram sums run over FLAT positions of the same image, before (X) and after (Z) the mixing: K = positions, four per k-step, the
-// k-steps dealt to the waves; the A and the B operand of a diagonal tile are the same register.  With two input channels a row tile
-// holds eight clips: the 16 x 16 tile Gram is accumulated as it is and its eight 2 x 2 diagonal blocks are added at the end.
+// k-steps dealt to the waves; the A and the B operand of a diagonal tile are the same register.  With two (four) input channels a row
+// tile holds eight (four) clips: the 16 x 16 tile Gram is accumulated as it is and its eight 2 x 2 (four 4 x 4) diagonal blocks are
+// added at the end.
 //
 // Determinism: no atomics.  The waves add their accumulators into one LDS row one after another, the row leaves as the workgroup's
 // partial row, launch_reduce_partials sums the rows in fp64 in a fixed order.  Rows beyond the batch are zeros in LDS.
@@ -38,11 +39,11 @@ __global__ __launch_bounds__(kWinBlock, (MomGeo<T, V>::Ops > 64 ? 2 : 4)) void k
     float* __restrict__ partials, float* __restrict__ Zout, int rows, int need_x) {
   using G = WinGeo<T, V>;
   constexpr int TV = G::TV, LD = G::LD, RT = MomGeo<T, V>::RT, NR = 16 * RT;
-  constexpr int ROWS = CI == 32 ? 32 : 16;        // rows of one Gram image: a clip of 16 / 32 channels, or eight clips of two
+  constexpr int ROWS = CI == 32 ? 32 : 16;        // rows of one Gram image: a clip of 16 / 32 channels, or 16 / CI clips of two / four
   constexpr int NACC = CI == 32 ? 3 : 1;          // tiles 00, 01, 11 (symmetric) or the one tile
   constexpr int NS = CI == 32 ? 2 : 1;
   constexpr int GF = ROWS * ROWS + ROWS;          // floats of one Gram + row sums in the final LDS row
-  static_assert(CI == 2 || CI == 16 || CI == 32, "built for 2, 16 and 32 input channels");
+  static_assert(CI == 2 || CI == 4 || CI == 16 || CI == 32, "built for 2, 4, 16 and 32 input channels");
   static_assert(2 * GF <= RT * G::IMG, "the final row is aliased onto the image");
   extern __shared__ float win_smem[];
   float* img = win_smem;
@@ -169,12 +170,13 @@ __global__ __launch_bounds__(kWinBlock, (MomGeo<T, V>::Ops > 64 ? 2 : 4)) void k
   // partial row: [MX CI^2][sumX CI][MZ CI^2][sumZ CI]
   constexpr int EH = CI * CI + CI;
   float* dst = partials + (size_t)blockIdx.x * (2 * EH);
-  if constexpr (CI == 2) {
+  if constexpr (CI < 16) {                         // the tile's 16 / CI clips: their diagonal blocks, one after another (fixed order)
     if (threadIdx.x < 2 * EH) {
       const int which = threadIdx.x / EH, e = threadIdx.x - which * EH;
       const float* base = row + which * GF;
       float t = 0.f;
-      for (int b = 0; b < 8; ++b) t += e < 4 ? base[(2 * b + (e >> 1)) * ROWS + 2 * b + (e & 1)] : base[ROWS * ROWS + 2 * b + (e - 4)];
+      for (int b = 0; b < 16 / CI; ++b)
+        t += e < CI * CI ? base[(CI * b + e / CI) * ROWS + CI * b + e % CI] : base[ROWS * ROWS + CI * b + (e - CI * CI)];
       dst[threadIdx.x] = t;
     }
   } else {
@@ -202,6 +204,7 @@ int launch_win_moments(const float* in, const float* Aw, const float* Tw, const 
   {
     ProbeScope probe(KID_FWD_MOMENTS, Ci, Ci, st);
     if (Ci == 2) LAUNCH_MOM(2);
+    else if (Ci == 4) LAUNCH_MOM(4);
     else if (Ci == 16) LAUNCH_MOM(16);
     else LAUNCH_MOM(32);
   }
@@ -222,7 +225,7 @@ int launch_win_moments(const float* in, const float* Aw, const float* Tw, const 
 }  // namespace
 
 bool window_moments_ok(int T, int V, int Ci) {
-  return (T == 8 || T == 16 || T == 24) && (V == 17 || V == 25) && (Ci == 2 || Ci == 16 || Ci == 32);
+  return (T == 8 || T == 16 || T == 24) && (V == 17 || V == 25) && (Ci == 2 || Ci == 4 || Ci == 16 || Ci == 32);
 }
 
 int launch_window_moments(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B, int Ci,

@@ -72,6 +72,20 @@ def layer_train_window_ok(T: int, V: int, Ci: int, Co: int) -> bool:
             and (T, V) not in TRAIN_WINDOW_OFF)
 
 
+# the few-channel set beside it: the virtual (4 -> 2) layer a stack's last (C -> 2) layer runs as by commutation.
+# Geometries measured no faster than the autograd route of the decoder models stay switched off in a table of their own: none
+TRAIN_WINDOW_NARROW = ((4, 2),)
+TRAIN_WINDOW_NARROW_OFF = frozenset()
+
+
+def layer_train_window_narrow_ok(T: int, V: int, Ci: int, Co: int) -> bool:
+    """Host arithmetic of `coskad_layer_train_window_narrow_ok`: the few-channel (4 -> 2) layer of window length 8 / 16 / 24 trains on
+    the stored-Z layer kernels.  A set of its own: `layer_train_window_ok` stays False there.  tests/test_ae_window_host.py holds the
+    library and this restatement in agreement."""
+    return (T in WINDOW_LENGTHS and V in TRAIN_WINDOW_JOINTS and (Ci, Co) in TRAIN_WINDOW_NARROW
+            and (T, V) not in TRAIN_WINDOW_NARROW_OFF)
+
+
 def gcn(x: Tensor, A: Tensor, Tm: Tensor, adjoint: bool = False) -> Tensor:
     """ConvTemporalGraphical.forward (reference stsgcn.py:143-156) or its adjoint."""
     N, C, T, V = x.shape

@@ -167,6 +167,24 @@ def _is_window(m) -> bool:
     return True
 
 
+def _is_narrow_window(m) -> bool:
+    """a (C -> 2) layer of window length 8 / 16 / 24 that runs by commutation like its 12-frame sibling (_is_narrow): the convolutions
+    first (csrc/last_layer.hip), then the virtual (4 -> 2) layer on the few-channel stored-Z kernels of that window length
+    (ops.layer_train_window_narrow_ok)"""
+    from .models.graph_layers.stsgcn import WIDE_CHANNELS, layer_tensors
+    T, V = m.time_dim, m.joints_dim
+    if (not NARROW_OUT or m.out_channels > 2 or isinstance(m.residual, torch.nn.Identity) or m.dropout > 0
+            or max(m.in_channels, m.out_channels) > WIDE_CHANNELS or not ops.window_ok(T, V)
+            or not ops.narrow_conv_ok(m.in_channels, 2 * m.out_channels, T * V)
+            or not ops.layer_train_window_narrow_ok(T, V, 2 * m.out_channels, m.out_channels)):
+        return False
+    try:
+        layer_tensors(m)
+    except NotImplementedError:
+        return False
+    return True
+
+
 class _WindowRun(_TileRun):
     """a run of layers of window length 8 / 16 / 24 on the stored-Z layer kernels (csrc/train_window_*.hip): the same
     engine.chain_forward / chain_backward calls, whose C-ABI entry points take the geometry; main stream, no SyncBN.  Hands over a
@@ -288,9 +306,7 @@ class _FlatStack:
         plain: no commuted / narrow-output segments (those layers stay in the tile runs); side, sync: the tile runs' side stream /
         SyncBN process group; window: layers of window length 8 / 16 / 24 run on the stored-Z layer kernels where those are built
         (`window` runs) instead of the composed path"""
-        dec = prefix.startswith("decoder")
-        kinds = [('window' if window and _is_window(m) else 'wide') if m.is_wide else 'narrow' if not plain and _is_narrow(m) else
-                 'commute' if not plain and _is_commute(m, dec) else 'tile' for m in modules]
+        kinds = self.kinds(modules, prefix, plain=plain, window=window)
         single = {'wide': _WideLayer, 'narrow': _NarrowLayer, 'commute': _CommuteLayer}
         self.segs = []
         i, n = 0, len(modules)
@@ -308,6 +324,19 @@ class _FlatStack:
                 self.segs.append(single[kinds[i]](modules[i], fp, f"{prefix}{first + i}."))
             i = j
         self.last_slope_grad = self.segs[-1].out_slope_grad
+
+    @staticmethod
+    def kinds(modules, prefix: str, plain: bool = False, window: bool = False) -> List[str]:
+        """the segment kind of every layer, as the constructor cuts the stack (needs no parameters' buffers and no device)"""
+        dec = prefix.startswith("decoder")
+
+        def beyond(m) -> str:          # an `is_wide` layer: at a window length the stored-Z kernels where asked for and built
+            if window and _is_window(m):
+                return 'window'
+            return 'narrow' if window and not plain and _is_narrow_window(m) else 'wide'
+
+        return [beyond(m) if m.is_wide else 'narrow' if not plain and _is_narrow(m) else
+                'commute' if not plain and _is_commute(m, dec) else 'tile' for m in modules]
 
     def _stats_rider(self, k: int) -> Optional[engine.LayerTensors]:
         """the first layer of a tile run behind commuted segment k when its statistics pass rides on that segment's last kernel"""
@@ -701,7 +730,10 @@ class STSAETrainStep(_FlatStep):
     through the same kernels.  Gradients land in the flat buffer; data-parallel all-reduce and Adam as in STSETrainStep."""
 
     def __init__(self, model, mode: str = 'ae', lr: float = 1e-4, alpha: float = 0.0, lambda_: float = 0.01, phi: float = 1.0,
-                 beta: float = 1.0, gamma: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None) -> None:
+                 beta: float = 1.0, gamma: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None,
+                 fused_window: bool = False) -> None:
+        """fused_window: layers of window length 8 / 16 / 24 train on the stored-Z layer kernels where those are built (`window` runs
+        of both stacks, the last decoder layer as a `narrow` segment; off: the composed path, as before).  Eager, main stream."""
         from .models.sts.ae import STSAE
         from .models.sts.vae import STSVAE
         from .models.common.components import Encoder
@@ -715,18 +747,17 @@ class STSAETrainStep(_FlatStep):
         super().__init__(model, lr, alpha, betas, eps, process_group)
         self.mode = mode
         self.lambda_, self.phi, self.beta, self.gamma = float(lambda_), float(phi), float(beta), float(gamma)
-        self.enc = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.")
+        self.enc = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.", window=fused_window)
         # the decoder's first layer sees a rank-(latent + 1) input (rev_btlnk of the latent): folded into one streaming pass where that
         # layer would otherwise take the composed wide path (coskad_amd/lowrank.py)
         from . import lowrank
         dec_layers = list(model.decoder.model)
         self.lowrank = None
-        if (len(dec_layers) > 1 and lowrank.LowRankFirstLayer.supports(model.rev_btlnk, dec_layers[0])
-                and (lowrank.MODE == 'always' or (lowrank.MODE == 'wide' and dec_layers[0].is_wide))):
+        if self._folds_first(model):
             self.lowrank = lowrank.LowRankFirstLayer(model.rev_btlnk, dec_layers[0], self.fp.gviews)
-            self.dec = _FlatStack(dec_layers[1:], self.fp, "decoder.model.", first=1)
+            self.dec = _FlatStack(dec_layers[1:], self.fp, "decoder.model.", first=1, window=fused_window)
         else:
-            self.dec = _FlatStack(dec_layers, self.fp, "decoder.model.")
+            self.dec = _FlatStack(dec_layers, self.fp, "decoder.model.", window=fused_window)
         self.center_acc = torch.zeros(ops.head_slots(model.latent_dim), device=self.fp.flat.device, dtype=torch.float32)
         self.last = {}
 
@@ -739,6 +770,23 @@ class STSAETrainStep(_FlatStep):
                 return model.btlnk.hip_ok and model.btlnk.hidden_layers[0] <= 16 and model.latent_dim <= 16
             return isinstance(model.btlnk, torch.nn.Identity) and model.latent_dim + model.fc_var.out_features <= 16
         return isinstance(model.btlnk, torch.nn.Linear) and model.latent_dim <= 16
+
+    @staticmethod
+    def _folds_first(model) -> bool:
+        """the decoder's first layer is folded into rev_btlnk's streaming pass (coskad_amd/lowrank.py)"""
+        from . import lowrank
+        dec_layers = list(model.decoder.model)
+        return (len(dec_layers) > 1 and lowrank.LowRankFirstLayer.supports(model.rev_btlnk, dec_layers[0])
+                and (lowrank.MODE == 'always' or (lowrank.MODE == 'wide' and dec_layers[0].is_wide)))
+
+    @staticmethod
+    def segment_kinds(model, fused_window: bool = False):
+        """-> (encoder kinds, decoder kinds behind a folded first layer), one per layer, as the constructor would cut the two stacks; the wrappers ask
+        before they build a step (a stack with `wide` segments at a window length stays with them on the autograd route)"""
+        dec_layers = list(model.decoder.model)
+        first = 1 if STSAETrainStep._folds_first(model) else 0
+        return (_FlatStack.kinds(list(model.encoder.model), "encoder.model.", window=fused_window),
+                _FlatStack.kinds(dec_layers[first:], "decoder.model.", window=fused_window))
 
     def step(self, x: Tensor) -> Dict[str, Tensor]:
         """-> {'rec': F.mse_loss(x_rec, x), 'head': MSE(z, c) | KL, ('exp': mean(1 / kappa)), 'z': the latents}"""

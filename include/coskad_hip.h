@@ -121,6 +121,12 @@ int coskad_layer_train_stats_f32(const float* in, const float* A, const float* T
  * and before the shape is judged.  Parameters, gradients and tables need 4-byte alignment only. */
 int coskad_layer_train_window_ok(int T, int V, int Ci, int Co);
 
+/* 1 when a FEW-CHANNEL (Ci -> Co) layer of window length T trains on the same entry points: exactly T in {8, 16, 24} x V in {17, 25} x
+ * (Ci, Co) = (4, 2), the virtual layer a stack's last (C -> 2) layer runs as by commutation; 0 for everything else (T = 12, V = 14 / 18,
+ * (6, 3), ...).  A set of its own: coskad_layer_train_window_ok is unchanged and stays 0 there.  Where either predicate holds the entry
+ * points listed above serve the layer, with the same alignment rule; coskad_layer_train_moments_f32 serves Ci = 4 as well. */
+int coskad_layer_train_window_narrow_ok(int T, int V, int Ci, int Co);
+
 /* Stored-Z variant of the training forward: the statistics pass also writes Z = gcn(PReLU(in)) [B,Ci,T,V]; the layer
  * is then a streaming GEMM over Z and `in` (no staging, no mixing recompute), and the backward reads Z as well.
  * (T, V): T = 12, or a window geometry where coskad_layer_train_window_ok holds (see there for the alignment rule). */
@@ -320,7 +326,7 @@ int coskad_layer_bwd_chain_f32(const float* in, const float* dU, const float* A,
  * or the chain buffer the layer above filled -> all-reduce the sums in place -> coskad_layer_bwd_chain_f32 with stats_in and
  * stats_count = global clips x T x V (0: this batch). */
 /* coskad_layer_train_moments_f32, coskad_layer_bwd_stats_f32 -- (T, V): T = 12, or the window lengths 8 / 16 / 24 at 17 / 25 joints with
- * Ci in {2, 16, 32} (and, for the backward's stage 1, coskad_layer_train_window_ok(T, V, Ci, Co)); activation pointers (`in`, `Z`, `dU`)
+ * Ci in {2, 4, 16, 32} (and, for the backward's stage 1, coskad_layer_train_window_ok or _narrow_ok(T, V, Ci, Co)); activation pointers (`in`, `Z`, `dU`)
  * 16-byte aligned there, as coskad_layer_train_window_ok's comment states. */
 int coskad_layer_train_moments_f32(const float* in, const float* A, const float* Tm, const float* in_slope, float* Z, double* sums,
                                    void* ws, size_t ws_bytes, int B, int Ci, int T, int V, hipStream_t stream);
