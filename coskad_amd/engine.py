@@ -124,6 +124,21 @@ EVAL_FIRST_PAIR = True
 # (csrc/eval_layer_window.hip; models/graph_layers/stsgcn.py: plan_stack); tests and tools/bench_eval_window.py flip it to get the
 # composed route
 EVAL_WINDOW = True
+# eval-mode, no-grad decoders run their last (C -> 2) layer on the one-clip tail kernel where it is built (csrc/eval_tail_window.hip:
+# STSAE.reconstruction_scores at every window length, STSAE.decode at 8 / 16 / 24 frames); tests and tools/bench_score_tail.py flip it
+# to get the route without it
+EVAL_TAIL = True
+
+
+def eval_fold(L: LayerTensors):
+    """-> (wfold, bias) of a layer with running statistics (ops.bn_fold), kept in the layer's cache until a tensor it reads changes"""
+    key = L.fold_key() if L.cache is not None else None
+    if key is not None and L.cache.get("key") == key:
+        return L.cache["fold"]                         # weights unchanged since the last eval forward
+    wb = ops.bn_fold(L.w2(L.Wt), L.bt, L.gt, L.bet, L.rm_t, L.rv_t, L.w2(L.Wr), L.br, L.gr, L.ber, L.rm_r, L.rv_r)
+    if key is not None:
+        L.cache["key"], L.cache["fold"] = key, wb
+    return wb
 
 
 def chain_forward(x: Tensor, layers: List[LayerTensors], training: bool, ws: Workspace,
@@ -167,15 +182,6 @@ def chain_forward(x: Tensor, layers: List[LayerTensors], training: bool, ws: Wor
         for i in range(n - 1):
             fuse_flat[i] = (not fuse[i] and layers[i + 1].Ci == layers[i].Co and layers[i].Wr is not None
                             and ops.layer_apply_next_flat_ok(layers[i].Ci, layers[i].Co, T, V))
-    def eval_fold(L):
-        key = L.fold_key() if L.cache is not None else None
-        if key is not None and L.cache.get("key") == key:
-            return L.cache["fold"]                         # weights unchanged since the last eval forward
-        wb = ops.bn_fold(L.w2(L.Wt), L.bt, L.gt, L.bet, L.rm_t, L.rv_t, L.w2(L.Wr), L.br, L.gr, L.ber, L.rm_r, L.rv_r)
-        if key is not None:
-            L.cache["key"], L.cache["fold"] = key, wb
-        return wb
-
     skip = -1
     pending = pending0          # (Z, partials, rows) of THIS layer, written by the previous layer's apply (or by x's producer)
     if pending0 is not None and not (batch_stats[0] and STORE_Z and sync is None):

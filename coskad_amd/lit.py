@@ -375,8 +375,11 @@ class LitAutoEncoder(_AutogradLit):
     rec_loss_weight = 0.2
 
     def window_scores_from_batch(self, x: torch.Tensor) -> torch.Tensor:
-        z, x_rec = self.model(x)
-        return eval_utils.rec_and_hy_window_scores(x, x_rec, z, self.model.c, self.rec_loss_weight, self.score_type)
+        if self.score_type == 'hyp':           # the latent alone: no decoder
+            z, rec = self.model.encode(x), None
+        else:                                   # the last decoder layer and the error in one launch where the kernel is built
+            z, rec = self.model.reconstruction_scores(x)
+        return eval_utils.rec_and_hy_from_rec(rec, z, self.model.c, self.rec_loss_weight, self.score_type)
 
 
 class LitVAE(_AutogradLit):
@@ -453,7 +456,7 @@ class LitVAE(_AutogradLit):
     training_epoch_end = on_train_epoch_end
 
     def window_scores_from_batch(self, x: torch.Tensor) -> torch.Tensor:
-        z, _, _ = self.model(x)
+        z = self.model.sample(x)[0]            # forward's latent (its draws, in its order) without the decoder behind it
         return 1 - F.cosine_similarity(self.model.mean_vector.expand_as(z), z)
 
 

@@ -208,6 +208,11 @@ class STSAE(STSE):
 
     def decode(self, Z: Tensor, input_shape: Tuple[int]) -> Tensor:
         B, C, T, V, M = input_shape
+        if ops.window_ok(T, V) and self._tail_layer(Z) is not None:
+            # 8 / 16 / 24 frames, eval mode, nobody asks for a gradient: the last layer (a composed `wide` segment of plan_stack) as ONE
+            # launch of the one-clip tail kernel; 12 frames keep their tile-kernel chain
+            h, slope = self._decode_head(Z, B * M, C, T, V)
+            return self._run_tail(h, slope, None)[0]
         folded = self._decode_folded(Z, B * M, T, V)
         if folded is not None:
             return folded
@@ -218,13 +223,68 @@ class STSAE(STSE):
         H = H.view(B * M, C, T, V)
         return self.decoder(H)
 
-    def _decode_folded(self, Z: Tensor, N: int, T: int, V: int) -> Optional[Tensor]:
+    def _tail_layer(self, t: Tensor):
+        """the decoder's last layer where ops.layer_tail takes it: eval mode, nobody asks for a gradient, fp32 on the device, running
+        statistics to fold, no dropout, a convolution residual, a shape of `ops.layer_tail_ok`, engine.EVAL_TAIL on.  None otherwise."""
+        if (not engine.EVAL_TAIL or self.training or torch.is_grad_enabled() or not t.is_cuda or t.dtype != torch.float32
+                or not isinstance(self.decoder, Decoder)):
+            return None
+        mods = list(self.decoder.model)
+        last = mods[-1]
+        if len(mods) < 2 or last.training or last.dropout > 0 or isinstance(last.residual, nn.Identity):
+            return None
+        if not all(bn.track_running_stats and bn.running_mean is not None for bn in (last.tcn[1], last.residual[1])):
+            return None
+        return last if ops.layer_tail_ok(last.time_dim, last.joints_dim, last.in_channels, last.out_channels) else None
+
+    def _decode_head(self, Z: Tensor, N: int, C: int, T: int, V: int):
+        """decode's route (no gradient) up to but not including the decoder's last layer -> (h, slope): apply PReLU(slope) to h to get
+        that layer's input (slope None: h is activated)"""
+        from ..graph_layers.stsgcn import run_stack
+        mods = list(self.decoder.model)[:-1]
+        head = self._decode_folded(Z, N, T, V, mods=mods)
+        if head is not None:
+            return head
+        if ops.rev_btlnk_ok(self.rev_btlnk.out_features, self.latent_dim):
+            H = ops.rev_btlnk_fwd(Z.contiguous(), self.rev_btlnk.weight.contiguous(), self.rev_btlnk.bias)
+        else:
+            H = self.rev_btlnk(Z)
+        return run_stack(H.view(N, C, T, V), mods, self.decoder._ws)
+
+    def _run_tail(self, h: Tensor, slope: Optional[Tensor], X: Optional[Tensor]):
+        """the last layer on ops.layer_tail -> (x_rec, None) without a target, (None, scores [B]) against the target X"""
+        from ..graph_layers.stsgcn import layer_tensors
+        last = self.decoder.model[-1]
+        L = layer_tensors(last)
+        wfold, bias = engine.eval_fold(L)          # the cache and key of engine.chain_forward's eval-mode layers
+        return ops.layer_tail(h.contiguous(), L.A, L.T, wfold, bias, L.Co, in_slope=slope, out_slope=L.slope,
+                              x=None if X is None else X.contiguous(), want_out=X is None, want_score=X is not None)
+
+    def reconstruction_scores(self, X: Tensor) -> Tuple[Tensor, Tensor]:
+        """-> (Z, rec [B]): the latent and the per-window mean squared reconstruction error ((x_rec - X)^2 over (C, T, V)).  In eval
+        mode without gradients, where `_tail_layer` holds, the last decoder layer and the error are ONE launch that writes no
+        reconstruction (csrc/eval_tail_window.hip); everywhere else the formula on forward's output."""
+        if len(X.shape) == 4 and self._tail_layer(X) is not None:
+            Z, (B, C, T, V, M) = self._latent(X)
+            h, slope = self._decode_head(Z, B * M, C, T, V)
+            return Z, self._run_tail(h, slope, X)[1]
+        out = self(X)
+        Z, x_rec = out[0], out[1]
+        return Z, ((x_rec - X) ** 2).reshape(X.shape[0], -1).mean(-1)
+
+    def _latent(self, X: Tensor):
+        """-> (Z, input_shape): the latent forward hands to decode"""
+        return self.encode(X, return_shape=True)
+
+    def _decode_folded(self, Z: Tensor, N: int, T: int, V: int, mods=None):
         """Eval-mode fast path (no gradient): rev_btlnk + the decoder's first layer as ONE streaming pass where that layer would
         take the composed wide path (coskad_amd/lowrank.py: the latent makes its input rank latent + 1), the remaining layers
-        as usual.  None: not applicable."""
+        as usual.  None: not applicable.  `mods`: a prefix of the decoder's layers to stop behind -> (h, slope) as run_stack's."""
         from ... import lowrank
         from ..graph_layers.stsgcn import run_stack
-        mods = list(self.decoder.model) if isinstance(self.decoder, Decoder) else []
+        head = mods is not None
+        if mods is None:
+            mods = list(self.decoder.model) if isinstance(self.decoder, Decoder) else []
         if (self.training or torch.is_grad_enabled() or not Z.is_cuda or Z.dtype != torch.float32 or len(mods) < 2
                 or not lowrank.eval_supported(self.rev_btlnk, mods[0])):
             return None
@@ -243,6 +303,8 @@ class STSAE(STSE):
         Mw, Mb = cached[1]
         U1 = ops.rev_btlnk_fwd(Z.contiguous(), Mw, Mb).view(N, mods[0].out_channels, T, V)
         u, slope = run_stack(U1, mods[1:], self.decoder._ws, in_slope=mods[0].prelu.weight)
+        if head:
+            return u, slope
         return u if slope is None else _PReLUFn.apply(u, slope)
 
     def forward(self, X: Tensor) -> Tuple[Tensor]:

@@ -167,7 +167,8 @@ class STSVAE(STSAE):
             p_Z = HypersphericalUniform(self.latent_dim - 1, device=Z_mean.device)
         return q_Z, p_Z
 
-    def forward(self, X: Tensor):
+    def sample(self, X: Tensor):
+        """-> (Z, input_shape, (q_Z, p_Z, Z_var)): forward up to the sampled latent -- every random draw of a forward, in its order"""
         if (not self.training and not torch.is_grad_enabled() and X.is_cuda and self.distribution == 'ps' and 2 <= self.latent_dim <= 16):
             # scoring forward (spherical_vae.py:76-78): normalise, softplus + 1 and the PowerSpherical sample on csrc/vae_head.hip
             # (two launches around torch's Beta draw and Gaussian direction: the module path's noise streams) instead of ~40
@@ -178,9 +179,15 @@ class STSVAE(STSAE):
             Z, _, _, saved = ops.ps_head_forward(m_raw, v_raw)
             Z_var = saved[3].unsqueeze(-1)
             q_Z, p_Z = self.reparameterize(saved[2], Z_var)
-            return Z, self.decode(Z, input_shape=input_shape), (q_Z, p_Z, Z_var)
+            return Z, input_shape, (q_Z, p_Z, Z_var)
         Z_mean, Z_var, input_shape = self.encode(X, return_shape=True)
         q_Z, p_Z = self.reparameterize(Z_mean, Z_var)
-        Z = q_Z.rsample()
-        X_rec = self.decode(Z, input_shape=input_shape)
-        return Z, X_rec, (q_Z, p_Z, Z_var)
+        return q_Z.rsample(), input_shape, (q_Z, p_Z, Z_var)
+
+    def _latent(self, X: Tensor):
+        Z, input_shape, _ = self.sample(X)
+        return Z, input_shape
+
+    def forward(self, X: Tensor):
+        Z, input_shape, dists = self.sample(X)
+        return Z, self.decode(Z, input_shape=input_shape), dists

@@ -130,6 +130,46 @@ def layer_apply_window_ok(T: int, V: int, Ci: int, Co: int) -> bool:
     return bool(_lib.lib().coskad_layer_apply_window_ok(T, V, Ci, Co))
 
 
+# (T, V) where the decoder-tail kernel measured no faster than the route without it stay switched off here
+LAYER_TAIL_OFF = frozenset()
+
+
+def layer_tail_ok(T: int, V: int, Ci: int, Co: int) -> bool:
+    """layer_tail takes the (Ci -> Co) layer: 8 / 12 / 16 / 24 frames x 17 / 25 joints, 16 / 32 -> 2 channels (csrc/eval_tail_window.hip:
+    `coskad_layer_tail_ok`) and the geometry is not switched off in LAYER_TAIL_OFF.  A set of its own: the other predicates stay False
+    for two output channels."""
+    return bool(_lib.lib().coskad_layer_tail_ok(T, V, Ci, Co)) and (T, V) not in LAYER_TAIL_OFF
+
+
+def layer_tail(x_in: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, bias: Tensor, Co: int, in_slope: Optional[Tensor] = None,
+               out_slope: Optional[Tensor] = None, x: Optional[Tensor] = None, want_out: bool = True, want_score: bool = False,
+               out: Optional[Tensor] = None, score: Optional[Tensor] = None):
+    """The last layer of an eval-mode decoder with folded BatchNorm (layer_apply's contract, two output channels) as one launch with
+    one clip per workgroup, and -- `want_score`, against the target `x` [B, Co, T, V] -- the clip's mean squared reconstruction error
+    from the same launch.  -> (out [B, Co, T, V] or None, score [B] or None); a clip's results do not depend on the batch."""
+    B, Ci, T, V = x_in.shape
+    _chk(x_in, "x_in"); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T))
+    _chk(wfold, "wfold", (2 * Ci, cop(Co))); _chk(bias, "bias", (cop(Co),))
+    _chk(in_slope, "in_slope", (1,), optional=True); _chk(out_slope, "out_slope", (1,), optional=True)
+    if not (want_out or want_score):
+        raise ValueError("layer_tail: neither the reconstruction nor the score asked for")
+    if want_score:
+        _chk(x, "x", (B, Co, T, V))
+        if score is None:
+            score = torch.empty(B, device=x_in.device, dtype=torch.float32)
+        else:
+            _chk(score, "score", (B,))
+    if want_out:
+        if out is None:
+            out = torch.empty(B, Co, T, V, device=x_in.device, dtype=torch.float32)
+        else:
+            _chk(out, "out", (B, Co, T, V))
+    out, score = (out if want_out else None), (score if want_score else None)
+    call("coskad_layer_tail_f32", x_in, x if want_score else None, out, score, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V,
+         _stream(), tag=(Ci, Co))
+    return out, score
+
+
 def layer_first_pair_ok(Ci: int, Cm: int, Co: int, T: int, V: int) -> bool:
     """the first layer (2 -> Cm) and the layer behind it (Cm -> Co), folded, in one pass (csrc/eval_layer_bpc.hip, FIRST form; window
     lengths 8 / 16 / 24: csrc/eval_layer_window.hip)"""

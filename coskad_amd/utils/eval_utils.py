@@ -153,6 +153,13 @@ def rec_and_hy_window_scores(x: torch.Tensor, x_rec: torch.Tensor, z: torch.Tens
     The 'hyp' part runs on the HIP head kernel when the latents live on the GPU."""
     B = x.shape[0]
     rec = ((x_rec - x) ** 2).reshape(B, -1).mean(-1)
+    return rec_and_hy_from_rec(rec, z, c, rec_loss_weight, loss_type)
+
+
+def rec_and_hy_from_rec(rec: torch.Tensor, z: torch.Tensor, c: torch.Tensor, rec_loss_weight: float = 0.2,
+                        loss_type: str = 'rec') -> torch.Tensor:
+    """rec_and_hy_window_scores from the per-window reconstruction error `rec` [B] itself (STSAE.reconstruction_scores forms it
+    without a reconstruction in memory); `rec` may be None for 'hyp', which does not read it."""
     if loss_type == 'rec':
         return rec
     from .. import ops

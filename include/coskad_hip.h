@@ -65,6 +65,22 @@ int coskad_layer_apply_f32(const float* in, float* out, const float* A, const fl
                            const float* out_slope, int B, int Ci, int Co, int T, int V,
                            hipStream_t stream);
 
+/* The TAIL of a decoder in eval mode (csrc/eval_tail_window.hip): the same layer with TWO output channels, one clip per workgroup
+ * on a persistent grid, and -- in the same launch, without atomics -- the clip's reconstruction error against the target x [B, Co, T, V]:
+ *   out [B, Co, T, V] = PReLU_out( Wz . gcn(PReLU_in in) + Wx . PReLU_in in + b )      (optional)
+ *   score [B]         = mean over (c, t, v) of (out - x)^2                             (optional; needs x)
+ * coskad_layer_tail_ok: 1 for T in {8, 12, 16, 24} x V in {17, 25} x Ci in {16, 32} x Co = 2, 0 otherwise (a set of its own: the other
+ * `*_ok` predicates keep their answers).  coskad_layer_tail_max_grid: the persistent grid's cap (workgroups), 0 where not ok.
+ * wfold [2*Ci][16], bias [16]: as coskad_bn_fold_f32 writes them for Co = 2.  At least one of out / score; `in`, `x`, `out` 16-byte
+ * aligned (COSKAD_ERR_ARG naming the pointer), `score` 4-byte aligned; other shapes fail with COSKAD_ERR_SHAPE ("unsupported ...").
+ * Every check runs before the device is touched.  A clip's results do not depend on B or on the workgroup that forms them. */
+int coskad_layer_tail_ok(int T, int V, int Ci, int Co);
+int coskad_layer_tail_max_grid(int T, int V, int Ci);
+int coskad_layer_tail_f32(const float* in, const float* x, float* out, float* score,
+                          const float* A, const float* Tm, const float* wfold, const float* bias,
+                          const float* in_slope, const float* out_slope,
+                          int B, int Ci, int Co, int T, int V, hipStream_t stream);
+
 /* nn.PReLU() with one shared weight (stsgcn.py:82,110), elementwise, for API paths that must
  * materialise the post-activation tensor.  bwd: du = dout * PReLU'(u); dslope (+)= sum dout*u [u<0];
  * ws >= 1024 floats. */
