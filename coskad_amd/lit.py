@@ -263,22 +263,12 @@ class _AutogradLit(LitEncoder):
     def _make_optimiser(self, mode: str, **weights) -> None:
         """The flat-buffer step with the fused Adam (trainer.STSAETrainStep: no autograd around the encoder / decoder chains)
         where the model is within its kernels; torch autograd + torch.optim.Adam over the module surface otherwise."""
-        from .trainer import STSAETrainStep
-        from .models.common.components import Encoder
+        from .trainer import make_decoder_step
         self._flat = None
-        on_gpu = next(self.model.parameters()).is_cuda
-        ok = on_gpu and isinstance(self.model.encoder, Encoder) and STSAETrainStep.supports(self.model)
-        # `fused_window` (not a key of the reference's yamls): at `dataset_seg_len` 8 / 16 / 24 the flat step takes the model when
-        # the stored-Z layer kernels serve EVERY layer of both stacks (no `wide` segment: such a stack -- 8-channel layers, a
-        # joint layout without window kernels -- stays on the autograd route, as does every model with `fused_window: false`)
-        window = ok and ops.window_ok(self.model.n_frames, self.model.n_joints) and bool(getattr(self.args, "fused_window", True))
-        if window:
-            enc_kinds, dec_kinds = STSAETrainStep.segment_kinds(self.model, fused_window=True)
-            window = 'wide' not in enc_kinds and 'wide' not in dec_kinds
-        if window or (ok and not self.model.encoder.model[-1].is_wide and not self.model.decoder.model[-1].is_wide):
-            self._flat = STSAETrainStep(self.model, mode=mode, lr=self.learning_rate,
-                                        alpha=float(getattr(self.args, "alpha", 0.0)), fused_window=window, **weights)
-        else:
+        if next(self.model.parameters()).is_cuda:
+            self._flat = make_decoder_step(self.model, mode, fused_window=bool(getattr(self.args, "fused_window", True)),
+                                           lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)), **weights)
+        if self._flat is None:
             self._opt = torch.optim.Adam(self.model.parameters(), lr=self.learning_rate)
 
     def _reg_loss(self) -> torch.Tensor:

@@ -153,36 +153,33 @@ class _TileRun(_Segment):
                                      in_slope_grad=in_slope_grad)
 
 
-def _is_window(m) -> bool:
-    """a layer that is `is_wide` ONLY because of its window length (8 / 16 / 24) and that the stored-Z training kernels take at that
-    length: <= 64 channels, no dropout, BatchNorms the shared statistics kernel can serve (layer_tensors checks them)"""
-    from .models.graph_layers.stsgcn import WIDE_CHANNELS, layer_tensors
-    if (max(m.in_channels, m.out_channels) > WIDE_CHANNELS or m.dropout > 0 or not ops.window_ok(m.time_dim, m.joints_dim)
-            or not ops.layer_train_window_ok(m.time_dim, m.joints_dim, m.in_channels, m.out_channels)):
+def _window_layer(m) -> bool:
+    """what every layer on the stored-Z kernels of window length 8 / 16 / 24 needs: that window length, <= 64 channels, no dropout,
+    BatchNorms the shared statistics kernel can serve (layer_tensors checks them)"""
+    from .models.graph_layers.stsgcn import WIDE_CHANNELS
+    if max(m.in_channels, m.out_channels) > WIDE_CHANNELS or m.dropout > 0 or not ops.window_ok(m.time_dim, m.joints_dim):
         return False
     try:
         layer_tensors(m)
     except NotImplementedError:
         return False
     return True
+
+
+def _is_window(m) -> bool:
+    """a layer that is `is_wide` ONLY because of its window length (8 / 16 / 24) and that the stored-Z training kernels take at that
+    length"""
+    return _window_layer(m) and ops.layer_train_window_ok(m.time_dim, m.joints_dim, m.in_channels, m.out_channels)
 
 
 def _is_narrow_window(m) -> bool:
     """a (C -> 2) layer of window length 8 / 16 / 24 that runs by commutation like its 12-frame sibling (_is_narrow): the convolutions
     first (csrc/last_layer.hip), then the virtual (4 -> 2) layer on the few-channel stored-Z kernels of that window length
     (ops.layer_train_window_narrow_ok)"""
-    from .models.graph_layers.stsgcn import WIDE_CHANNELS, layer_tensors
     T, V = m.time_dim, m.joints_dim
-    if (not NARROW_OUT or m.out_channels > 2 or isinstance(m.residual, torch.nn.Identity) or m.dropout > 0
-            or max(m.in_channels, m.out_channels) > WIDE_CHANNELS or not ops.window_ok(T, V)
-            or not ops.narrow_conv_ok(m.in_channels, 2 * m.out_channels, T * V)
-            or not ops.layer_train_window_narrow_ok(T, V, 2 * m.out_channels, m.out_channels)):
-        return False
-    try:
-        layer_tensors(m)
-    except NotImplementedError:
-        return False
-    return True
+    return (NARROW_OUT and m.out_channels <= 2 and not isinstance(m.residual, torch.nn.Identity) and _window_layer(m)
+            and ops.narrow_conv_ok(m.in_channels, 2 * m.out_channels, T * V)
+            and ops.layer_train_window_narrow_ok(T, V, 2 * m.out_channels, m.out_channels))
 
 
 class _WindowRun(_TileRun):
@@ -526,9 +523,96 @@ class _OneClassHead:
         return self.model.inv_cov_matrix
 
 
+def _stacked_heads(m):
+    """the VAE's fc_mean | fc_var as one Linear -> (W, b), mean rows first"""
+    return torch.cat([m.fc_mean.weight, m.fc_var.weight], 0), torch.cat([m.fc_mean.bias, m.fc_var.bias], 0)
+
+
+def _unstack_head_grads(gv: Dict[str, Tensor], L: int, gW: Tensor, gb: Tensor) -> None:
+    """the stacked Linear's gradients into the four views of fc_mean (rows < L) and fc_var"""
+    gv["fc_mean.weight"].copy_(gW[:L]); gv["fc_var.weight"].copy_(gW[L:])
+    gv["fc_mean.bias"].copy_(gb[:L]); gv["fc_var.bias"].copy_(gb[L:])
+
+
+class _LinearProjector:
+    """The bottleneck projector, `btlnk` an nn.Linear (ae.py:97-101), on the encoder's pre-activation output U (PReLU `slope` on load).
+    Every form: forward(U, slope) -> (y, saved); backward(saved, dy, U, slope, ctx, top_layers, last_slope_grad) -> (dU, top_stats)
+    with (ctx, top_layers) = the encoder's _FlatStack.top and top_stats chain_backward's `stats_in` (engine.btlnk_backward).
+    Parameters and gradients stay in the flat buffers."""
+
+    def __init__(self, lin, fp: "FlatParams", ws: engine.Workspace, wname: str = "btlnk.") -> None:
+        self.lin, self.ws = lin, ws
+        self.gW, self.gb = fp.gviews[wname + "weight"], fp.gviews.get(wname + "bias")
+
+    def forward(self, U: Tensor, slope):
+        W = self.lin.weight
+        return ops.btlnk_fwd(U, W, self.lin.bias, slope, ws=self.ws), W
+
+    def backward(self, W, dy, U, slope, ctx, top_layers, last_slope_grad):
+        return engine.btlnk_backward(ctx, top_layers or [], U, W, dy, slope, self.gW, self.gb, last_slope_grad, self.ws)
+
+
+class _MLPProjector(_LinearProjector):
+    """`mlp` projector (components.py:209-226): the wide first Linear on the bottleneck kernel, then every [BatchNorm1d, ReLU, Linear]
+    block on csrc/mlp_head.hip"""
+
+    def __init__(self, mlp, fp: "FlatParams", ws: engine.Workspace) -> None:
+        super().__init__(mlp.net[0], fp, ws, "btlnk.net.0.")
+        gv = fp.gviews
+        self.blocks = [(bn, lin, {"gamma": gv[f"btlnk.net.{3 * i + 1}.weight"], "beta": gv[f"btlnk.net.{3 * i + 1}.bias"],
+                                  "W2": gv[f"btlnk.net.{3 * i + 3}.weight"], "b2": gv.get(f"btlnk.net.{3 * i + 3}.bias")})
+                       for i, (bn, lin) in enumerate(mlp.blocks())]
+
+    def forward(self, U: Tensor, slope):
+        if U.shape[0] == 1:                # nn.BatchNorm1d's own check in training mode
+            raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d of the mlp projector)")
+        y, W = super().forward(U, slope)
+        saved = []
+        for bn, lin, _ in self.blocks:
+            z, stat = ops.mlp_head_fwd(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                       lin.weight, lin.bias, True, momentum=ops.bn_momentum(bn), eps=bn.eps)
+            saved.append((y, stat))
+            y = z
+        return y, (W, saved)
+
+    def backward(self, saved, dy, *top):
+        W, block_saved = saved
+        for (bn, lin, g), (y_in, stat) in zip(reversed(self.blocks), reversed(block_saved)):
+            dy = ops.mlp_head_bwd(y_in, stat, bn.weight, bn.bias, lin.weight, dy, g, True)
+        return super().backward(W, dy, *top)
+
+
+class _StackedHeads:
+    """the VAE's mean | concentration heads on the encoder's output (`btlnk` is Identity): their weights stacked, one pass over U"""
+
+    def __init__(self, model, fp: "FlatParams", ws: engine.Workspace) -> None:
+        self.model, self.ws, self.gv = model, ws, fp.gviews
+
+    def forward(self, U: Tensor, slope):
+        W, b = _stacked_heads(self.model)
+        return ops.btlnk_fwd(U, W, b, slope, ws=self.ws), (W, b)
+
+    def backward(self, saved, dy, U, slope, ctx, top_layers, last_slope_grad):
+        W, b = saved
+        gW, gb = torch.empty_like(W), torch.empty_like(b)
+        res = engine.btlnk_backward(ctx, top_layers or [], U, W, dy, slope, gW, gb, last_slope_grad, self.ws)
+        _unstack_head_grads(self.gv, self.model.latent_dim, gW, gb)
+        return res
+
+
+def _projector(model, fp: "FlatParams", ws: engine.Workspace):
+    """the projector form of a model the step classes admitted"""
+    from .models.common.components import MLP
+    if isinstance(model.btlnk, MLP):
+        return _MLPProjector(model.btlnk, fp, ws)
+    if isinstance(model.btlnk, torch.nn.Linear):
+        return _LinearProjector(model.btlnk, fp, ws)
+    return _StackedHeads(model, fp, ws)
+
+
 class _FlatStep:
-    """What the autograd-free steps share: the model's parameters re-homed in flat buffers, Adam's moments and the fused update, the
-    regulariser, the data-parallel world, the `mlp` projector's blocks."""
+    """What the autograd-free steps share: the model's parameters re-homed in flat buffers, the bottleneck projector, Adam's moments and
+    the fused update, the regulariser, the data-parallel world."""
 
     use_graph = False
 
@@ -540,6 +624,7 @@ class _FlatStep:
         self.fp = FlatParams(model)
         self.m, self.v = torch.zeros_like(self.fp.flat), torch.zeros_like(self.fp.flat)
         self.ws = engine.Workspace()
+        self.projector = _projector(model, self.fp, self.ws)
         self.reg_scale = 0.5 / self.fp.n_reg_tensors          # calc_reg_loss value = reg_scale * sum p^2
         self.reg_coef = self.alpha * 2.0 * self.reg_scale      # its gradient coefficient, times alpha
         self.steps = 0
@@ -565,29 +650,6 @@ class _FlatStep:
             ops.adam_pow(self.fp.flat, self.fp.grad, self.m, self.v, self.fp.reg_mask, self.lr, self.beta1, self.beta2, self.eps,
                          float(self._bpow[0]), float(self._bpow[1]), gscale=1.0 / self.world, reg_coef=self.reg_coef)
 
-    def _mlp_forward(self, U: Tensor, slope: Tensor):
-        """`mlp` projector (components.py:209-226) on the chain's pre-activation output: the wide first Linear on the bottleneck kernel
-        (PReLU on load), then every [BatchNorm1d, ReLU, Linear] block on csrc/mlp_head.hip; parameters and gradients stay in the flat
-        buffers -> (y, saved)"""
-        if U.shape[0] == 1:                # nn.BatchNorm1d's own check in training mode
-            raise ValueError("Expected more than 1 value per channel when training (BatchNorm1d of the mlp projector)")
-        btl = self.model.btlnk
-        y = ops.btlnk_fwd(U, btl.net[0].weight, btl.net[0].bias, slope, ws=self.ws)
-        saved = []
-        for i, (bn, lin) in enumerate(btl.blocks()):
-            z, stat = ops.mlp_head_fwd(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                       lin.weight, lin.bias, True, momentum=ops.bn_momentum(bn), eps=bn.eps)
-            saved.append((y, stat, bn, lin, f"btlnk.net.{3 * i + 1}.", f"btlnk.net.{3 * i + 3}."))
-            y = z
-        return y, saved
-
-    def _mlp_backward(self, saved, d: Tensor) -> Tensor:
-        """back through the blocks of _mlp_forward -> the gradient of the first Linear's output"""
-        gv = self.fp.gviews
-        for y_in, stat, bn, lin, bname, lname in reversed(saved):
-            g = {"gamma": gv[bname + "weight"], "beta": gv[bname + "bias"], "W2": gv[lname + "weight"], "b2": gv.get(lname + "bias")}
-            d = ops.mlp_head_bwd(y_in, stat, bn.weight, bn.bias, lin.weight, d, g, True)
-        return d
 
 
 class STSETrainStep(_FlatStep, _OneClassHead):
@@ -604,8 +666,8 @@ class STSETrainStep(_FlatStep, _OneClassHead):
         (`window` runs of the stack; off: the composed path, as before)"""
         from .models.sts.ae import STSE
         from .models.common.components import MLP
-        self.mlp = isinstance(model.btlnk, MLP)
-        if not isinstance(model, STSE) or not (isinstance(model.btlnk, torch.nn.Linear) or (self.mlp and model.btlnk.hip_ok)):
+        mlp = isinstance(model.btlnk, MLP)
+        if not isinstance(model, STSE) or not (isinstance(model.btlnk, torch.nn.Linear) or (mlp and model.btlnk.hip_ok)):
             raise TypeError("STSETrainStep drives an STSE with projector='linear' or an 'mlp' within the kernels' widths")
         super().__init__(model, lr, alpha, betas, eps, process_group)
         self.head = head
@@ -629,7 +691,7 @@ class STSETrainStep(_FlatStep, _OneClassHead):
         # BatchNorm boundary of the forward and the backward adds the other ranks' fp64 sums (engine.chain_forward / _backward)
         self.sync_group = None
         if sync_bn and self.world > 1:
-            if self.mlp or side_stream or use_graph or wide:
+            if mlp or side_stream or use_graph or wide:
                 raise ValueError("sync_bn: encoder BatchNorm only (STS-GCN encoder within the tile kernels, linear projector), on the "
                                  "main stream, outside hipGraph capture")
             self.sync_group = process_group if process_group is not None else dist.group.WORLD
@@ -666,21 +728,13 @@ class STSETrainStep(_FlatStep, _OneClassHead):
 
     # -- the step ---------------------------------------------------------------------------
     def _body(self, x: Tensor) -> Tensor:
-        m, gv = self.model, self.fp.gviews
         U, slope, saved_stack = self.stack.forward(x, self.ws)          # slope None: the stack ended in a wide layer (activated output)
         ctx, top_layers = self.stack.top(saved_stack)
-        if self.mlp:
-            wname, W = "btlnk.net.0.", m.btlnk.net[0].weight
-            z, saved = self._mlp_forward(U, slope)
-        else:
-            wname, W = "btlnk.", m.btlnk.weight
-            z = ops.btlnk_fwd(U, W, m.btlnk.bias, slope, ws=self.ws)
+        z, saved = self.projector.forward(U, slope)
         stats, dz = self._head(z)
-        if self.mlp:
-            dz = self._mlp_backward(saved, dz)
         # (the side-stream backward runs its own batch reductions: no ChainCtx, so the bottleneck's backward forms none)
-        dU, top_stats = engine.btlnk_backward(ctx if self.side is None else None, top_layers or [], U, W, dz, slope, gv[wname + "weight"],
-                                              gv.get(wname + "bias"), self.stack.last_slope_grad, self.ws)
+        dU, top_stats = self.projector.backward(saved, dz, U, slope, ctx if self.side is None else None, top_layers,
+                                                self.stack.last_slope_grad)
         work = None
         if self.world > 1 and self.tail_off is not None:
             # bucket 1 (87 % of the bytes: the bottleneck weight) is complete now: its all-reduce runs on the collective
@@ -717,6 +771,105 @@ class STSETrainStep(_FlatStep, _OneClassHead):
         return self._stats_static
 
 
+class _LatentHead:
+    """The latent head of the decoder step, between the projector's output y and the decoder entry's input z_dec.
+    forward(y) -> (z_dec, dz0, losses, saved): dz0 the head's own gradient w.r.t. z_dec (None: all of it comes back through the
+    decoder), losses the 'head' (and 'exp') entries of the step's result; backward(saved, dz) -> dy."""
+
+    def __init__(self, step: "STSAETrainStep", heads: bool = False) -> None:
+        """heads: the VAE's two small head Linears act on y here (`mlp` projector; else the projector stacked them)"""
+        self.model, self.acc, self.gv, self.heads = step.model, step.center_acc, step.fp.gviews, heads
+        self.beta, self.gamma = step.beta, step.gamma
+
+
+class _CentreLatent(_LatentHead):
+    """the autoencoder's: MSE(z, c) against the centre and its gradient, which the decoder's backward adds to"""
+
+    def forward(self, y: Tensor):
+        stats, dz, _ = ops.mse_head(y, self.model.c, acc=self.acc)
+        return y, dz, {'head': stats[0:1]}, None
+
+    def backward(self, saved, dz: Tensor) -> Tensor:
+        return dz
+
+
+class _PowerSphericalLatent(_LatentHead):
+    """The PowerSpherical head on csrc/vae_head.hip (normalise, softplus + 1, Householder sample, KL, 1 / kappa: three launches +
+    torch's Beta draw instead of ~80 element-wise launches under autograd); the two small Linears of the `mlp` projector's heads ride
+    on the strided GEMM with the weights stacked"""
+
+    def forward(self, y: Tensor):
+        m, L = self.model, self.model.latent_dim
+        Wc, H2 = None, y
+        if self.heads:
+            Wc, bc = _stacked_heads(m)                                        # [L + 1, L]
+            H2 = ops.gemm(y, Wc.t(), bias=bc, bias_mode=2)
+        zs, kl_rows, ik_rows, ps_saved = ops.ps_head_forward(H2[:, :L], H2[:, L:L + 1])
+        return zs, None, {'head': kl_rows.mean().reshape(1), 'exp': ik_rows.mean().reshape(1)}, (y, H2, Wc, ps_saved)
+
+    def backward(self, saved, dz: Tensor) -> Tensor:
+        y, H2, Wc, ps_saved = saved
+        L, B = self.model.latent_dim, dz.shape[0]
+        dH2 = torch.empty_like(H2)
+        ops.ps_head_backward(ps_saved, dz, self.beta / B, self.gamma / B, dH2[:, :L], dH2[:, L:L + 1])
+        if Wc is None:
+            return dH2
+        # the two heads' Linears (weights stacked): dWc = dH2^T y, db = column sums, dy = dH2 Wc
+        dWc = ops.gemm_rows_outer(dH2, y.contiguous(), torch.empty(L + 1, L, device=dH2.device, dtype=torch.float32))
+        _unstack_head_grads(self.gv, L, dWc, dH2.sum(0))
+        return ops.gemm(dH2, Wc)
+
+
+class _AutogradLatent(_LatentHead):
+    """every other distribution of the VAE: torch ops on [B, latent] tensors under a local autograd graph (vae.py:79-91,104-118)"""
+
+    def __init__(self, step: "STSAETrainStep", heads: bool = False) -> None:
+        super().__init__(step, heads)
+        names = ("fc_mean.weight", "fc_mean.bias", "fc_var.weight", "fc_var.bias") if heads else ()
+        self.head_params, self.head_grads = [step.model.get_parameter(n) for n in names], [self.gv[n] for n in names]
+
+    def forward(self, y: Tensor):
+        m, L = self.model, self.model.latent_dim
+        y.requires_grad_(True)
+        with torch.enable_grad():
+            if self.heads:
+                Z_mean, Z_var = m._finish_heads(m.fc_mean(y), m.fc_var(y), None, False)
+            else:
+                Z_mean, Z_var = m._finish_heads(y[:, :L], y[:, L:], None, False)
+            q, p = m.reparameterize(Z_mean, Z_var)
+            zs = q.rsample()
+            loss_kl = torch.distributions.kl.kl_divergence(q, p).sum(-1).mean()
+            loss_exp = (1 / Z_var).mean()
+            small = self.beta * loss_kl + self.gamma * loss_exp
+        losses = {'head': loss_kl.detach().reshape(1), 'exp': loss_exp.detach().reshape(1)}
+        return zs.detach().contiguous(), None, losses, (y, zs, small)
+
+    def backward(self, saved, dz: Tensor) -> Tensor:
+        y, zs, small = saved
+        res = torch.autograd.grad([zs, small], [y] + self.head_params, [dz, torch.ones_like(small)])
+        for into, g in zip(self.head_grads, res[1:]):
+            into.copy_(g)
+        return res[0].contiguous()
+
+
+class _PlainEntry:
+    """The decoder entry where the decoder's first layer is not folded into it (else: lowrank.LowRankFirstLayer, the same two calls):
+    rev_btlnk (ae.py:223-227), H = z Wr^T + br on the strided MFMA GEMM, straight into the decoder's [B, hid, T, V] view; backward
+    dWr = dH^T z, dbr = sum dH, dz (+)= dH Wr on streaming kernels over dH (csrc/rev_btlnk.hip)"""
+
+    def __init__(self, model, gviews) -> None:
+        self.rev, self.shape = model.rev_btlnk, (model.hidden_dimension, model.n_frames, model.n_joints)
+        self.gW, self.gb, self._z = gviews["rev_btlnk.weight"], gviews["rev_btlnk.bias"], None
+
+    def forward(self, z: Tensor) -> Tensor:
+        self._z = z
+        return ops.rev_btlnk_fwd(z, self.rev.weight, self.rev.bias).view(z.shape[0], *self.shape)
+
+    def backward(self, dH: Tensor, dz: Optional[Tensor] = None) -> Tensor:
+        z, self._z = self._z, None
+        return ops.rev_btlnk_bwd(dH.reshape(z.shape[0], -1), z, self.rev.weight, self.gW, self.gb, dz=dz)
+
+
 class STSAETrainStep(_FlatStep):
     """One optimisation step of the decoder models on flat parameter / gradient buffers with the fused Adam -- the
     reference's training_step + optimizer step of
@@ -724,10 +877,11 @@ class STSAETrainStep(_FlatStep):
       mode 'ae'  (models/euclidean_autoencoder.py:106-118): lambda_ * MSE(x_rec, x) + MSE(z, c) + alpha * reg
       mode 'vae' (models/spherical_vae.py:81-107):          phi * MSE(x_rec, x) + alpha * reg + beta * KL(q || p) + gamma * mean(1 / kappa)
 
-    encoder -> bottleneck (one kernel pass; the VAE's mean | concentration heads stacked) -> [VAE: normalise, softplus + 1,
-    PowerSpherical rsample, KL: torch ops on [B, latent] tensors under a local autograd graph] -> rev_btlnk (MFMA GEMM) ->
-    decoder -> reconstruction head (PReLU of the last layer + MSE + its gradient in one kernel) -> everything backwards
-    through the same kernels.  Gradients land in the flat buffer; data-parallel all-reduce and Adam as in STSETrainStep."""
+    encoder stack -> `projector` (the bottleneck, one kernel pass; the VAE's mean | concentration heads stacked) -> `latent` (MSE to
+    the centre | the PowerSpherical head | another distribution under a local autograd graph) -> `entry` (rev_btlnk, with the first
+    decoder layer folded in where lowrank.py takes it) -> decoder stack -> reconstruction head -> the same stages backwards.  The
+    constructor picks every stage's form and refuses what they do not take; gradients land in the flat buffer; data-parallel
+    all-reduce and Adam as in STSETrainStep."""
 
     def __init__(self, model, mode: str = 'ae', lr: float = 1e-4, alpha: float = 0.0, lambda_: float = 0.01, phi: float = 1.0,
                  beta: float = 1.0, gamma: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None,
@@ -744,21 +898,31 @@ class STSAETrainStep(_FlatStep):
         if not self.supports(model):
             raise TypeError("STSAETrainStep: projector / latent size outside the bottleneck kernels (latent rows <= 16, "
                             "'linear' projector)")
+        # a stack ending `wide` hands over an activated output (no slope, no `last_slope_grad`), which neither the bottleneck kernels
+        # nor the reconstruction head take: refused before anything touches the model (its parameters are not re-homed yet)
+        for kinds, which in zip(self.segment_kinds(model, fused_window), ("an encoder", "a decoder")):
+            if kinds[-1] == 'wide':
+                raise NotImplementedError(f"STSAETrainStep: {which} ending in a wide layer")
         super().__init__(model, lr, alpha, betas, eps, process_group)
         self.mode = mode
         self.lambda_, self.phi, self.beta, self.gamma = float(lambda_), float(phi), float(beta), float(gamma)
+        self.w_rec = self.lambda_ if mode == 'ae' else self.phi
         self.enc = _FlatStack(list(model.encoder.model), self.fp, "encoder.model.", window=fused_window)
         # the decoder's first layer sees a rank-(latent + 1) input (rev_btlnk of the latent): folded into one streaming pass where that
-        # layer would otherwise take the composed wide path (coskad_amd/lowrank.py)
+        # layer would otherwise take the composed wide path (coskad_amd/lowrank.py); it then hands over a pre-activation and its slope
         from . import lowrank
-        dec_layers = list(model.decoder.model)
-        self.lowrank = None
+        dec_layers, gv = list(model.decoder.model), self.fp.gviews
+        self.lowrank = self.entry_slope = self.entry_slope_grad = None
         if self._folds_first(model):
-            self.lowrank = lowrank.LowRankFirstLayer(model.rev_btlnk, dec_layers[0], self.fp.gviews)
-            self.dec = _FlatStack(dec_layers[1:], self.fp, "decoder.model.", first=1, window=fused_window)
+            self.lowrank = self.entry = lowrank.LowRankFirstLayer(model.rev_btlnk, dec_layers[0], gv)
+            self.entry_slope, self.entry_slope_grad = dec_layers[0].prelu.weight, gv["decoder.model.0.prelu.weight"]
         else:
-            self.dec = _FlatStack(dec_layers, self.fp, "decoder.model.", window=fused_window)
+            self.entry = _PlainEntry(model, gv)
+        first = 0 if self.lowrank is None else 1
+        self.dec = _FlatStack(dec_layers[first:], self.fp, "decoder.model.", first=first, window=fused_window)
         self.center_acc = torch.zeros(ops.head_slots(model.latent_dim), device=self.fp.flat.device, dtype=torch.float32)
+        latent = _CentreLatent if mode == 'ae' else _PowerSphericalLatent if model.distribution == 'ps' else _AutogradLatent
+        self.latent = latent(self, heads=isinstance(self.projector, _MLPProjector))
         self.last = {}
 
     @staticmethod
@@ -791,126 +955,19 @@ class STSAETrainStep(_FlatStep):
     def step(self, x: Tensor) -> Dict[str, Tensor]:
         """-> {'rec': F.mse_loss(x_rec, x), 'head': MSE(z, c) | KL, ('exp': mean(1 / kappa)), 'z': the latents}"""
         self.steps += 1
-        m, gv = self.model, self.fp.gviews
         x = x.contiguous()
-        B = x.shape[0]
-        T, V, hid = m.n_frames, m.n_joints, m.hidden_dimension
         U, slope, enc_saved = self.enc.forward(x, self.ws)
-        if slope is None:              # the encoder ended in a wide layer: already activated
-            raise NotImplementedError("STSAETrainStep: an encoder ending in a wide layer")
-        out: Dict[str, Tensor] = {}
-        if self.mode == 'ae':
-            W, b, wname = m.btlnk.weight, m.btlnk.bias, "btlnk."
-            z = ops.btlnk_fwd(U, W, b, slope, ws=self.ws)
-            stats, dz, _ = ops.mse_head(z, m.c, acc=self.center_acc)              # MSE(z, c) and its gradient
-            out['head'] = stats[0:1]
-            z_dec, graph = z, None
-        else:
-            from .models.sts.vae import kl_ps_uniform
-            from .models.common.components import MLP
-            L = m.latent_dim
-            mlp = isinstance(m.btlnk, MLP)
-            mlp_saved, head_params = None, []
-            if mlp:
-                # `mlp` projector (vae.py:141-146): wide Linear on the bottleneck kernel, [BatchNorm1d, ReLU, Linear] blocks on
-                # csrc/mlp_head.hip; the two small heads act on its [B, latent] output inside the local autograd graph
-                W = m.btlnk.net[0].weight
-                Hd, mlp_saved = self._mlp_forward(U, slope)
-                head_params = [m.fc_mean.weight, m.fc_mean.bias, m.fc_var.weight, m.fc_var.bias]
-            else:
-                W = torch.cat([m.fc_mean.weight, m.fc_var.weight], 0)             # heads stacked: one pass over U
-                b = torch.cat([m.fc_mean.bias, m.fc_var.bias], 0)
-                Hd = ops.btlnk_fwd(U, W, b, slope, ws=self.ws)
-            if m.distribution == 'ps':
-                # the PowerSpherical head on csrc/vae_head.hip (normalise, softplus + 1, Householder sample, KL, 1 / kappa: three
-                # launches + torch's Beta draw instead of ~80 element-wise launches under autograd); the two small Linears of the
-                # `mlp` projector's heads ride on the strided GEMM with the weights stacked
-                if mlp:
-                    Wc = torch.cat([m.fc_mean.weight, m.fc_var.weight], 0)            # [L + 1, L]
-                    bc = torch.cat([m.fc_mean.bias, m.fc_var.bias], 0)
-                    H2 = ops.gemm(Hd, Wc.t(), bias=bc, bias_mode=2)
-                else:
-                    Wc, H2 = None, Hd
-                zs, kl_rows, ik_rows, ps_saved = ops.ps_head_forward(H2[:, :L], H2[:, L:L + 1])
-                out['head'], out['exp'] = kl_rows.mean().reshape(1), ik_rows.mean().reshape(1)
-                z_dec, graph = zs, ('ps', Hd, H2, Wc, ps_saved, mlp_saved)
-            else:
-                Hd.requires_grad_(True)
-                with torch.enable_grad():                                         # [B, latent] tensors: vae.py:79-91,104-118
-                    if mlp:
-                        Z_mean, Z_var = m._finish_heads(m.fc_mean(Hd), m.fc_var(Hd), None, False)
-                    else:
-                        Z_mean, Z_var = m._finish_heads(Hd[:, :L], Hd[:, L:], None, False)
-                    q, p = m.reparameterize(Z_mean, Z_var)
-                    zs = q.rsample()
-                    loss_kl = torch.distributions.kl.kl_divergence(q, p).sum(-1).mean()
-                    loss_exp = (1 / Z_var).mean()
-                    small = self.beta * loss_kl + self.gamma * loss_exp
-                out['head'], out['exp'] = loss_kl.detach().reshape(1), loss_exp.detach().reshape(1)
-                z_dec, graph = zs.detach().contiguous(), ('autograd', Hd, zs, small, head_params, mlp_saved)
-            dz = None
-        out['z'] = z_dec
-        # rev_btlnk (ae.py:223-227): H = z Wr^T + br on the strided MFMA GEMM, straight into the decoder's [B, hid, T, V] view
-        Wr, br = m.rev_btlnk.weight, m.rev_btlnk.bias
-        if self.lowrank is not None:
-            l0 = m.decoder.model[0]
-            Ud, dslope_d, dec_saved = self.dec.forward(self.lowrank.forward(z_dec), self.ws, in_slope=l0.prelu.weight)
-        else:
-            H = ops.rev_btlnk_fwd(z_dec, Wr, br)
-            Ud, dslope_d, dec_saved = self.dec.forward(H.view(B, hid, T, V), self.ws)
-        w_rec = self.lambda_ if self.mode == 'ae' else self.phi
-        if dslope_d is None:
-            raise NotImplementedError("STSAETrainStep: a decoder ending in a wide layer")
-        loss_rec, dUd, _ = ops.rec_head(Ud, x, dslope_d, dslope=self.dec.last_slope_grad, upstream=w_rec)
-        out['rec'] = loss_rec
+        y, proj_saved = self.projector.forward(U, slope)
+        z, dz, losses, latent_saved = self.latent.forward(y)
+        Ud, slope_d, dec_saved = self.dec.forward(self.entry.forward(z), self.ws, in_slope=self.entry_slope)
+        # reconstruction head: PReLU of the last layer + MSE + its gradient in one kernel
+        loss_rec, dUd, _ = ops.rec_head(Ud, x, slope_d, dslope=self.dec.last_slope_grad, upstream=self.w_rec)
+        out = dict(losses, z=z, rec=loss_rec)
         # ---- backward ----------------------------------------------------------------------------------------------------
-        if self.lowrank is not None:
-            dU1 = self.dec.backward(dec_saved, dUd, self.ws, need_dx=True, in_slope_grad=gv["decoder.model.0.prelu.weight"])
-            rev_bwd = lambda dz_: self.lowrank.backward(dU1, dz=dz_)
-        else:
-            dH = self.dec.backward(dec_saved, dUd, self.ws, need_dx=True).reshape(B, -1)
-            # rev_btlnk: dWr = dH^T z, dbr = sum dH, dz (+)= dH Wr: streaming kernels over dH (csrc/rev_btlnk.hip)
-            rev_bwd = lambda dz_: ops.rev_btlnk_bwd(dH, z_dec, Wr, gv["rev_btlnk.weight"], gv["rev_btlnk.bias"], dz=dz_)
-        if self.mode == 'ae':
-            dHd = rev_bwd(dz)                                                     # dz = d MSE(z, c) + dH Wr
-        else:
-            dz_dec = rev_bwd(None)
-            L = m.latent_dim
-            if graph[0] == 'ps':
-                _, Hd, H2, Wc, ps_saved, mlp_saved = graph
-                dH2 = torch.empty_like(H2)
-                ops.ps_head_backward(ps_saved, dz_dec, self.beta / B, self.gamma / B, dH2[:, :L], dH2[:, L:L + 1])
-                if mlp_saved is not None:
-                    # the two heads' Linears (weights stacked): dWc = dH2^T Hd, db = column sums, dHd = dH2 Wc
-                    dWc = ops.gemm_rows_outer(dH2, Hd.contiguous(), torch.empty(L + 1, L, device=dH2.device, dtype=torch.float32))
-                    dbc = dH2.sum(0)
-                    gv["fc_mean.weight"].copy_(dWc[:L]); gv["fc_var.weight"].copy_(dWc[L:])
-                    gv["fc_mean.bias"].copy_(dbc[:L]); gv["fc_var.bias"].copy_(dbc[L:])
-                    dHd = ops.gemm(dH2, Wc)
-                else:
-                    dHd = dH2
-            else:
-                _, Hd, zs, small, head_params, mlp_saved = graph
-                res = torch.autograd.grad([zs, small], [Hd] + head_params, [dz_dec, torch.ones_like(small)])
-                dHd = res[0].contiguous()
-                if mlp_saved is not None:
-                    for n, g_ in zip(("fc_mean.weight", "fc_mean.bias", "fc_var.weight", "fc_var.bias"), res[1:]):
-                        gv[n].copy_(g_)
-            if mlp_saved is not None:
-                dHd = self._mlp_backward(mlp_saved, dHd)
-        tctx, tlayers = self.enc.top(enc_saved)
-        bb = lambda gW_, gb_: engine.btlnk_backward(tctx, tlayers, U, W, dHd, slope, gW_, gb_, self.enc.last_slope_grad, self.ws)
-        if self.mode == 'ae':
-            dU, top_stats = bb(gv["btlnk.weight"], gv.get("btlnk.bias"))
-        elif mlp_saved is not None:          # mlp projector: the wide first Linear of the MLP
-            dU, top_stats = bb(gv["btlnk.net.0.weight"], gv.get("btlnk.net.0.bias"))
-        else:
-            gW = torch.empty_like(W)
-            gb = torch.empty_like(b)
-            dU, top_stats = bb(gW, gb)
-            L = m.latent_dim
-            gv["fc_mean.weight"].copy_(gW[:L]); gv["fc_var.weight"].copy_(gW[L:])
-            gv["fc_mean.bias"].copy_(gb[:L]); gv["fc_var.bias"].copy_(gb[L:])
+        d = self.dec.backward(dec_saved, dUd, self.ws, need_dx=True, in_slope_grad=self.entry_slope_grad)
+        dy = self.latent.backward(latent_saved, self.entry.backward(d, dz=dz))
+        ctx, top_layers = self.enc.top(enc_saved)
+        dU, top_stats = self.projector.backward(proj_saved, dy, U, slope, ctx, top_layers, self.enc.last_slope_grad)
         self.enc.backward(enc_saved, dU, self.ws, need_dx=False, top_stats=top_stats)
         if self.world > 1:
             dist.all_reduce(self.fp.grad, group=self.pg)                          # SUM; the 1 / W is folded into Adam
@@ -975,25 +1032,34 @@ def make_train_step(model, flat_plain_gcn: bool = False, fused_window: bool = Fa
     `fused_window`: an STS-GCN encoder of window length 8 / 16 / 24 runs its layers on the stored-Z layer kernels where those are built
     (csrc/train_window_*.hip; the wrappers ask for it) instead of the composed path; still eager, on the main stream."""
     from .models.common.components import MLP, Encoder
-    btl = getattr(model, 'btlnk', None)
-    enc = getattr(model, 'encoder', None)
+    btl, enc = getattr(model, 'btlnk', None), getattr(model, 'encoder', None)
     proj_ok = isinstance(btl, torch.nn.Linear) or (isinstance(btl, MLP) and btl.hip_ok)
-    if flat_plain_gcn and proj_ok and _is_plain_gcn(enc) and model.latent_dim <= ops.BTLNK_LMAX:
-        kw.pop('use_graph', None); kw.pop('side_stream', None)      # main stream, eager launches, as for wide layers
+    flat = (proj_ok and model.latent_dim <= ops.BTLNK_LMAX
+            and (isinstance(enc, Encoder) or (flat_plain_gcn and _is_plain_gcn(enc))))
+    if not flat or _is_plain_gcn(enc) or any(l.is_wide for l in enc.model):
+        # plain-GCN and wide layers, and the autograd step: main stream, eager launches; the optional key `sync_batchnorm` (absent in
+        # the reference): with one rank there is nothing to synchronise
+        kw.pop('use_graph', None); kw.pop('side_stream', None)
         if kw.get('sync_bn') and not (dist.is_available() and dist.is_initialized() and dist.get_world_size(kw.get('process_group')) > 1):
             kw.pop('sync_bn')
-        return STSETrainStep(model, **kw)
-    fast = proj_ok and isinstance(enc, Encoder) and model.latent_dim <= ops.BTLNK_LMAX
-    if fast:
-        if any(l.is_wide for l in model.encoder.model):     # wide layers: main stream, eager launches
-            kw.pop('use_graph', None); kw.pop('side_stream', None)
-            if kw.get('sync_bn') and not (dist.is_available() and dist.is_initialized() and dist.get_world_size(kw.get('process_group')) > 1):
-                kw.pop('sync_bn')
+    if flat:
         return STSETrainStep(model, fused_window=fused_window, **kw)
-    kw.pop('use_graph', None); kw.pop('side_stream', None)
     if kw.pop('sync_bn', False):
-        # the optional key `sync_batchnorm` (absent in the reference): with one rank there is nothing to synchronise
-        world = dist.get_world_size(kw.get('process_group')) if (dist.is_available() and dist.is_initialized()) else 1
-        if world > 1:
-            raise ValueError("sync_bn: encoder BatchNorm only (STS-GCN encoder within the tile kernels, linear projector)")
+        raise ValueError("sync_bn: encoder BatchNorm only (STS-GCN encoder within the tile kernels, linear projector)")
     return AutogradTrainStep(model, **kw)
+
+
+def make_decoder_step(model, mode: str, fused_window: bool = True, **kw) -> Optional[STSAETrainStep]:
+    """STSAETrainStep for an autoencoder / VAE within its kernels, None for what stays on torch autograd + torch.optim.Adam: another
+    encoder, a projector / latent outside `supports`, a stack ending in a `wide` segment.  `fused_window` (not a key of the reference's
+    yamls): at window length 8 / 16 / 24 the flat step takes the model when the stored-Z layer kernels serve EVERY layer of both stacks
+    (no `wide` segment: such a stack -- 8-channel layers, a joint layout without window kernels -- stays on the autograd route, as
+    does every model with `fused_window` off)."""
+    from .models.common.components import Encoder
+    if not isinstance(getattr(model, 'encoder', None), Encoder) or not STSAETrainStep.supports(model):
+        return None
+    window = (fused_window and ops.window_ok(model.n_frames, model.n_joints)
+              and not any('wide' in kinds for kinds in STSAETrainStep.segment_kinds(model, fused_window=True)))
+    if any(kinds[-1] == 'wide' for kinds in STSAETrainStep.segment_kinds(model, fused_window=window)):
+        return None
+    return STSAETrainStep(model, mode=mode, fused_window=window, **kw)

@@ -72,10 +72,11 @@ def test_default_widths_cut_into_window_runs_and_a_narrow_layer(T, V):
     assert eng.dec.last_slope_grad is gv["decoder.model.3.prelu.weight"]
     assert eng.enc.last_slope_grad is gv["encoder.model.3.prelu.weight"]
     assert trainer.STSAETrainStep.segment_kinds(_ae(T, V), fused_window=True) == (['window'] * 4, ['window', 'window', 'narrow'])
-    # off unless asked for
+    # off unless asked for: both stacks composed, ending in activated outputs -- a cut the step refuses before it touches the model
     for kw in ({}, dict(fused_window=False)):
-        eng = trainer.STSAETrainStep(_ae(T, V), **kw)
-        assert _kinds(eng.enc) == ['wide'] * 4 and _kinds(eng.dec) == ['wide'] * 3
+        assert trainer.STSAETrainStep.segment_kinds(_ae(T, V), **kw) == (['wide'] * 4, ['wide'] * 3)
+        with pytest.raises(NotImplementedError, match="STSAETrainStep: an encoder ending in a wide layer"):
+            trainer.STSAETrainStep(_ae(T, V), **kw)
 
 
 def test_vae_cuts_the_same_way():
@@ -100,12 +101,16 @@ def test_mixed_stacks_keep_wide_segments():
     assert 'wide' in _kinds(eng.enc) and 'wide' in _kinds(eng.dec)
     enc_k, dec_k = trainer.STSAETrainStep.segment_kinds(_ae(8, 17, channels=(16, 8, 16), hid=16), fused_window=True)
     assert enc_k == ['window', 'wide', 'wide', 'window'] == _kinds(eng.enc) and 'wide' in dec_k       # (per layer)
-    eng = trainer.STSAETrainStep(_ae(16, 18), fused_window=True)
-    assert set(_kinds(eng.enc) + _kinds(eng.dec)) == {'wide'}
-    # a last layer with dropout stays composed
+    enc_k, dec_k = trainer.STSAETrainStep.segment_kinds(_ae(16, 18), fused_window=True)
+    assert set(enc_k + dec_k) == {'wide'}
+    with pytest.raises(NotImplementedError, match="STSAETrainStep: an encoder ending in a wide layer"):
+        trainer.STSAETrainStep(_ae(16, 18), fused_window=True)
+    # a last layer with dropout stays composed: a decoder ending in an activated output, which the step refuses
     m = _ae(8, 17)
     m.decoder.model[-1].dropout = 0.1
-    assert _kinds(trainer.STSAETrainStep(m, fused_window=True).dec) == ['window', 'wide']
+    assert trainer.STSAETrainStep.segment_kinds(m, fused_window=True)[1] == ['window', 'window', 'wide']
+    with pytest.raises(NotImplementedError, match="STSAETrainStep: a decoder ending in a wide layer"):
+        trainer.STSAETrainStep(m, fused_window=True)
 
 
 def _aligned(n_floats):
