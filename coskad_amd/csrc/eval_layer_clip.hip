@@ -1,10 +1,16 @@
-// One ST_GCNN layer with BatchNorm folded (eval_layer_bpc.hip's contract: U = Wz . gcn(X) + Wx . X + b, X = PReLU(in), optional PReLU
-// on the way out) at the window lengths 8, 16 and 24 frames, 17 or 25 joints, ONE CLIP PER WORKGROUP OF FOUR WAVES, nothing but the
-// layer's input and output in HBM; and its FIRST form (the network input [B, 2, T, V] -> layer 1 on the VALU -> PReLU -> this layer).
-// The phases are those of k_eval_layer_bpc: residual product from the staged rows into registers, temporal and spatial mix in place,
-// main product added, flush through the image in full lines.  What differs with the window length:
+// One ST_GCNN layer with BatchNorm folded (eval mode, or any caller that hands over folded weights; reference
+// models/graph_layers/stsgcn.py:56-80 the mixing, 94-116 the layer):
+//     U = Wz . gcn(X) + Wx . X + b          X = PReLU(in) (in_slope), optional PReLU on the way out (out_slope)
+// at 8, 12, 16 or 24 frames, 17 or 25 joints, ONE CLIP PER WORKGROUP OF FOUR WAVES, nothing but the layer's input and output in HBM;
+// and its FIRST form (the network input [B, 2, T, V] -> layer 1 on the VALU -> PReLU -> this layer: the first layer's kernel, its
+// 32-row write and this kernel's 32-row read gone).
+// The mixes are dealt by joint and by frame, as in fwd_moments_bpc.hip, so that a wave's operands of both are the same for every clip.
+// ONE image: the residual convolution Wx . X runs first, straight from the staged rows (B operands read from the image, the folded
+// weights as A operands held in registers for the launch; a wave owns output tiles x position tiles), its sums wait in registers while
+// the image is mixed in place into Z, then Wz . Z is added; the sums leave through the image in full lines.  (Measurements at 12
+// frames against the LDS-table kernel k_layer_apply_m and against two layers in one kernel: DESIGN 5.10.)  With the frame count:
 //   * the temporal mix has T / 4 k-steps and, at T = 24, two output column tiles (frames 0..15, 16..23): a wave reads every A operand
-//     of a (row tile, joint), forms both tiles and only then stores either (at T = 8 the B operand's columns 8..15 are zero and
+//     of a (row tile, joint), forms both tiles and only then stores either (at T = 8 / 12 the B operand's columns T..15 are zero and
 //     never stored);
 //   * the spatial mix pads K = V to a multiple of 4 with zeros on BOTH operands, so no neighbouring frame leaks in;
 //   * a wave's share of the position tiles can be EMPTY (16 output channels at 8 x 17: 9 tiles, 3 per wave): it still walks every
@@ -12,7 +18,8 @@
 //   * Geo<> decides per instantiation what stays in registers for the launch -- the mixing operands (HOLD; else read per clip
 //     through L2: up to 120 / 168 registers at T = 24) and the next clip's rows (PF; else this clip's rows go straight into the
 //     image) -- and whether 64 output channels leave through 64 rows at once or through the 32 input rows in two rounds (TWO), so
-//     that a CU holds two workgroups wherever anything allows it (PER_CU: launch bounds and the persistent grid);
+//     that a CU holds two workgroups wherever anything allows it (PER_CU: launch bounds and the persistent grid); at T = 12
+//     everything fits and is kept, and PER_CU is what was measured there;
 //   * FIRST keeps x, Y0, Z0 behind the 32 input rows of the image (rows 32..37), so 2 -> 32 -> 64 at 24 x 25 stays inside 160 KB.
 // No atomics; a clip's output does not depend on the workgroup or loop round that forms it.
 #include "fused_ops.h"
@@ -20,14 +27,15 @@
 #include <cstdint>
 
 namespace coskad {
-namespace evw {
+namespace evc {
 
 using ff::f32x4;
 using ff::Lane;
 using ff::mfma;
 using ff::prelu;
 
-// the first layer (2 -> 32, folded) of the FIRST form: mixing parameters, folded weights [4][32] (rows Z0 Z1 X0 X1), bias [32]
+// the first layer (2 -> 32, folded) of the FIRST form: mixing parameters, folded weights [4][32] (rows Z0 Z1 X0 X1), bias [32]; the
+// PReLU between the layers is the main kernel's `in_slope`
 struct FirstLayer {
   const float* A;
   const float* T;
@@ -39,7 +47,7 @@ constexpr int imin(int a, int b) { return a < b ? a : b; }
 
 template <int T, int V, int CT, int OT, bool FIRST>
 struct Geo {
-  static_assert(T % 4 == 0 && T <= 32, "window lengths 8 / 16 / 24");
+  static_assert(T % 4 == 0 && T <= 32, "8 / 12 / 16 / 24 frames");
   static_assert(!FIRST || CT == 2, "the first layer has 32 output channels");
   static constexpr int TV = T * V, LD = TV + 2, R4 = TV / 4, Ci = 16 * CT, Co = 16 * OT;
   static_assert(TV % 4 == 0, "rows are staged as float4");
@@ -66,22 +74,51 @@ struct Geo {
   static constexpr int IN_ROWS = FIRST ? 38 : 32;                             // (FIRST: x, Y0, Z0 in rows 32..37)
   static constexpr int per_cu_in(bool hold, bool pf) { return imin(3, imin(by_lds(IN_ROWS), by_reg(hold, pf))); }
   static constexpr int TARGET = imin(2, per_cu_in(false, false));
-  static constexpr bool PF = FIRST || (XL <= 13 && per_cu_in(false, true) >= TARGET);
-  static constexpr bool HOLD = regs(true, PF) <= 256 && per_cu_in(true, PF) >= TARGET;
+  // T = 12 was measured on its own, before this rule: rows prefetched, operands held (63 registers), 64 output channels
+  // through 64 rows, and three workgroups per CU asked for except at 64 output channels and at 32 -> 32 (the estimate regs() would
+  // ask for 3 / 3 / 2 / 2 at 17 x 32 -> 32, 17 x 2 -> 32 -> 32, 25 x 16 -> 32, 25 x 32 -> 16 and drop the held operands at 25 x 32 -> 64)
+  static constexpr bool T12 = T == 12;
+  static constexpr bool PF = T12 || FIRST || (XL <= 13 && per_cu_in(false, true) >= TARGET);
+  static constexpr bool HOLD = T12 || (regs(true, PF) <= 256 && per_cu_in(true, PF) >= TARGET);
   // 64 output channels leave through 64 rows at once, or -- where those rows would cost a workgroup per CU -- through the 32 input
   // rows in two rounds (waves 0, 1 then waves 2, 3)
-  static constexpr bool TWO = OT == 4 && imin(3, by_lds(64)) < per_cu_in(HOLD, PF);
+  static constexpr bool TWO = !T12 && OT == 4 && imin(3, by_lds(64)) < per_cu_in(HOLD, PF);
   static constexpr int ROWS = (OT == 4 && !TWO) ? 64 : IN_ROWS;
   static constexpr int FR = TWO ? 32 : Co, NR = Co / FR;                      // rows per flush round, rounds
   static constexpr int LDS_BYTES = ROWS * LD * 4;
   static_assert(LDS_BYTES + STATIC_BYTES <= kMaxLdsBytes, "160 KB of LDS");
   static constexpr int BY_LDS = by_lds(ROWS);
   static constexpr int BY_REG = by_reg(HOLD, PF);
-  static constexpr int PER_CU = imin(3, imin(BY_LDS, BY_REG));                // workgroups (= waves per SIMD) a CU is asked to hold
+  // workgroups (= waves per SIMD) a CU is asked to hold
+  static constexpr int PER_CU = T12 ? ((OT == 4 || (CT == 2 && OT == 2)) ? 2 : 3) : imin(3, imin(BY_LDS, BY_REG));
 };
 
+// the 12-frame choices, for both V and all nine (CT, OT, FIRST): grid, block and dynamic LDS follow from them
+template <int V, int CT, int OT, bool FIRST>
+constexpr bool geo12_pinned() {
+  using G = Geo<12, V, CT, OT, FIRST>;
+  return G::PER_CU == ((OT == 4 || (CT == 2 && OT == 2)) ? 2 : 3) && G::HOLD && G::PF && !G::TWO &&
+         G::ROWS == (OT == 4 ? 64 : (FIRST ? 38 : 32));
+}
+template <int V>
+constexpr bool geo12_pinned_v() {
+  return geo12_pinned<V, 1, 1, false>() && geo12_pinned<V, 1, 2, false>() && geo12_pinned<V, 1, 4, false>() &&
+         geo12_pinned<V, 2, 1, false>() && geo12_pinned<V, 2, 2, false>() && geo12_pinned<V, 2, 4, false>() &&
+         geo12_pinned<V, 2, 1, true>() && geo12_pinned<V, 2, 2, true>() && geo12_pinned<V, 2, 4, true>();
+}
+static_assert(geo12_pinned_v<17>() && geo12_pinned_v<25>(), "Geo<12, ..>: the measured 12-frame choices");
+
+// four positions (e: float4 index into the clip's rows) of one input row into the image
+template <int R4, int LD>
+__device__ __forceinline__ void stage_row(float* imz, bool pre, float a_in, int e, float4 v) {
+  const int row = e / R4, col = 4 * (e - row * R4);
+  if (pre) { v.x = prelu(v.x, a_in); v.y = prelu(v.y, a_in); v.z = prelu(v.z, a_in); v.w = prelu(v.w, a_in); }
+  *reinterpret_cast<float2*>(imz + row * LD + col) = float2{v.x, v.y};
+  *reinterpret_cast<float2*>(imz + row * LD + col + 2) = float2{v.z, v.w};
+}
+
 template <int T, int V, int CT, int OT, bool FIRST>
-__global__ __launch_bounds__(256, (Geo<T, V, CT, OT, FIRST>::PER_CU)) void k_eval_layer_window(
+__global__ __launch_bounds__(256, (Geo<T, V, CT, OT, FIRST>::PER_CU)) void k_eval_layer_clip(
     const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ Aw, const float* __restrict__ Tw,
     const float* __restrict__ wfold, const float* __restrict__ bias, const float* __restrict__ in_slope,
     const float* __restrict__ out_slope, int B, FirstLayer fl) {
@@ -162,12 +199,9 @@ __global__ __launch_bounds__(256, (Geo<T, V, CT, OT, FIRST>::PER_CU)) void k_eva
       }
     }
   };
-  auto stage = [&](int e, float4 v) {                    // four positions of one input row into the image
-    const int row = e / R4, col = 4 * (e - row * R4);
-    if (pre) { v.x = prelu(v.x, a_in); v.y = prelu(v.y, a_in); v.z = prelu(v.z, a_in); v.w = prelu(v.w, a_in); }
-    *reinterpret_cast<float2*>(imz + row * LD + col) = float2{v.x, v.y};
-    *reinterpret_cast<float2*>(imz + row * LD + col + 2) = float2{v.z, v.w};
-  };
+  // (the window lengths stage through a by-reference lambda, T = 12 calls stage_row itself: each as it was measured.  The lambda costs
+  // the mixes of a 12-frame clip 26 .. 41 VALU instructions of LDS address arithmetic, 0.5 - 1.4 % of a launch: DESIGN 5.10)
+  auto stage = [&](int e, float4 v) { stage_row<R4, LD>(imz, pre, a_in, e, v); };
   const float* Ap = Aw;
   const float* Tp = Tw;
   int clip = blockIdx.x;
@@ -242,7 +276,10 @@ __global__ __launch_bounds__(256, (Geo<T, V, CT, OT, FIRST>::PER_CU)) void k_eva
 #pragma unroll
       for (int i = 0; i < XL; ++i) {
         const int e = tid + 256 * i;
-        if (e < N4) stage(e, px[i]);
+        if (e < N4) {
+          if constexpr (T == 12) stage_row<R4, LD>(imz, pre, a_in, e, px[i]);
+          else stage(e, px[i]);
+        }
       }
     } else {
       // (the big clips: no registers for the next clip's rows across the phases -- this clip's rows, straight into the image)
@@ -401,7 +438,7 @@ struct Args {
 template <int T, int V, int CT, int OT, bool FIRST>
 static void launch_one(const Args& a) {
   using G = Geo<T, V, CT, OT, FIRST>;
-  auto k = k_eval_layer_window<T, V, CT, OT, FIRST>;
+  auto k = k_eval_layer_clip<T, V, CT, OT, FIRST>;
   if (G::LDS_BYTES > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
   const int cap = 256 * G::PER_CU;                       // the persistent grid: PER_CU workgroups on each of 256 CUs
   const int grid = a.B < cap ? a.B : cap;
@@ -430,10 +467,12 @@ static void launch_tv(const Args& a, int Ci, int Co, bool first) {
 static void launch_any(const Args& a, int T, int V, int Ci, int Co, bool first) {
   if (V == 17) {
     if (T == 8) launch_tv<8, 17>(a, Ci, Co, first);
+    else if (T == 12) launch_tv<12, 17>(a, Ci, Co, first);
     else if (T == 16) launch_tv<16, 17>(a, Ci, Co, first);
     else launch_tv<24, 17>(a, Ci, Co, first);
   } else {
     if (T == 8) launch_tv<8, 25>(a, Ci, Co, first);
+    else if (T == 12) launch_tv<12, 25>(a, Ci, Co, first);
     else if (T == 16) launch_tv<16, 25>(a, Ci, Co, first);
     else launch_tv<24, 25>(a, Ci, Co, first);
   }
@@ -441,47 +480,69 @@ static void launch_any(const Args& a, int T, int V, int Ci, int Co, bool first) 
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace evw
+}  // namespace evc
 
-// every (T, V) of 8 / 16 / 24 x 17 / 25 builds without scratch inside 160 KB for every channel pair: none is declined
-static bool window_geometry(int T_, int V_) { return (T_ == 8 || T_ == 16 || T_ == 24) && (V_ == 17 || V_ == 25); }
+// every (T, V) of 8 / 12 / 16 / 24 x 17 / 25 builds without scratch inside 160 KB for every channel pair: none is declined
+static bool clip_geometry(int T_, int V_) { return (T_ == 8 || T_ == 12 || T_ == 16 || T_ == 24) && (V_ == 17 || V_ == 25); }
 
-bool eval_layer_window_ok(int T_, int V_, int Ci, int Co) {
-  return window_geometry(T_, V_) && (Ci == 16 || Ci == 32) && (Co == 16 || Co == 32 || Co == 64);
+bool eval_layer_clip_ok(int T_, int V_, int Ci, int Co) {
+  return clip_geometry(T_, V_) && (Ci == 16 || Ci == 32) && (Co == 16 || Co == 32 || Co == 64);
 }
 
-bool eval_first_pair_window_ok(int T_, int V_, int Ci, int Cm, int Co) {
-  return window_geometry(T_, V_) && Ci == 2 && Cm == 32 && (Co == 16 || Co == 32 || Co == 64);
+bool eval_first_pair_clip_ok(int T_, int V_, int Ci, int Cm, int Co) {
+  return clip_geometry(T_, V_) && Ci == 2 && Cm == 32 && (Co == 16 || Co == 32 || Co == 64);
 }
 
-int launch_eval_layer_window(const float* in, float* out, const float* Aw, const float* Tw, const float* wfold, const float* bias,
-                             const float* in_slope, const float* out_slope, int B, int Ci, int Co, int T_, int V_, hipStream_t st) {
-  if (!eval_layer_window_ok(T_, V_, Ci, Co))
-    return fail(COSKAD_ERR_SHAPE, "eval_layer_window: built for 8 / 16 / 24 x 17 / 25, 16 / 32 -> 16 / 32 / 64 channels");
-  if (!evw::aligned16(in)) return fail(COSKAD_ERR_ARG, "layer_apply: `in` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)in);
-  if (!evw::aligned16(out)) return fail(COSKAD_ERR_ARG, "layer_apply: `out` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)out);
-  evw::launch_any(evw::Args{in, out, Aw, Tw, wfold, bias, in_slope, out_slope, B, evw::FirstLayer{}, st}, T_, V_, Ci, Co, false);
-  return check_launch("eval_layer_window");
+// (16-byte alignment of the clip tensors is asked for at the window lengths 8 / 16 / 24 only: the 12-frame callers never had to)
+int launch_eval_layer_clip(const float* in, float* out, const float* Aw, const float* Tw, const float* wfold, const float* bias,
+                           const float* in_slope, const float* out_slope, int B, int Ci, int Co, int T_, int V_, hipStream_t st) {
+  if (!eval_layer_clip_ok(T_, V_, Ci, Co))
+    return fail(COSKAD_ERR_SHAPE, "eval_layer_clip: built for 8 / 12 / 16 / 24 x 17 / 25, 16 / 32 -> 16 / 32 / 64 channels");
+  if (T_ != 12) {
+    if (!evc::aligned16(in)) return fail(COSKAD_ERR_ARG, "layer_apply: `in` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)in);
+    if (!evc::aligned16(out)) return fail(COSKAD_ERR_ARG, "layer_apply: `out` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)out);
+  }
+  evc::launch_any(evc::Args{in, out, Aw, Tw, wfold, bias, in_slope, out_slope, B, evc::FirstLayer{}, st}, T_, V_, Ci, Co, false);
+  return check_launch("eval_layer_clip");
 }
 
-int launch_eval_first_pair_window(const float* x, float* out, const float* A1, const float* T1, const float* wfold1,
-                                  const float* bias1, const float* A2, const float* T2, const float* wfold2, const float* bias2,
-                                  const float* mid_slope, const float* out_slope, int B, int Co, int T_, int V_, hipStream_t st) {
-  if (!eval_first_pair_window_ok(T_, V_, 2, 32, Co))
-    return fail(COSKAD_ERR_SHAPE, "eval_first_pair_window: built for 8 / 16 / 24 x 17 / 25, 2 -> 32 -> 16 / 32 / 64 channels");
-  if (!evw::aligned16(x)) return fail(COSKAD_ERR_ARG, "layer_first_pair_apply: `x` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)x);
-  if (!evw::aligned16(out))
-    return fail(COSKAD_ERR_ARG, "layer_first_pair_apply: `out` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)out);
-  evw::launch_any(evw::Args{x, out, A2, T2, wfold2, bias2, mid_slope, out_slope, B, evw::FirstLayer{A1, T1, wfold1, bias1}, st}, T_, V_,
+int launch_eval_first_pair_clip(const float* x, float* out, const float* A1, const float* T1, const float* wfold1,
+                                const float* bias1, const float* A2, const float* T2, const float* wfold2, const float* bias2,
+                                const float* mid_slope, const float* out_slope, int B, int Co, int T_, int V_, hipStream_t st) {
+  if (!eval_first_pair_clip_ok(T_, V_, 2, 32, Co))
+    return fail(COSKAD_ERR_SHAPE, "eval_first_pair_clip: built for 8 / 12 / 16 / 24 x 17 / 25, 2 -> 32 -> 16 / 32 / 64 channels");
+  if (T_ != 12) {
+    if (!evc::aligned16(x)) return fail(COSKAD_ERR_ARG, "layer_first_pair_apply: `x` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)x);
+    if (!evc::aligned16(out))
+      return fail(COSKAD_ERR_ARG, "layer_first_pair_apply: `out` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)out);
+  }
+  evc::launch_any(evc::Args{x, out, A2, T2, wfold2, bias2, mid_slope, out_slope, B, evc::FirstLayer{A1, T1, wfold1, bias1}, st}, T_, V_,
                   32, Co, true);
-  return check_launch("eval_first_pair_window");
+  return check_launch("eval_first_pair_clip");
 }
 
 extern "C" {
 
 /* 1: coskad_layer_apply_f32 runs the layer as ONE launch (folded BatchNorm, one clip per workgroup) at this window length other than
- * 12; 0 at T = 12 (whose own kernels coskad_layer_fits describes) and everywhere else */
-int coskad_layer_apply_window_ok(int T, int V, int Ci, int Co) { return eval_layer_window_ok(T, V, Ci, Co) ? 1 : 0; }
+ * 12; 0 at T = 12 (which coskad_layer_fits describes, though the same kernel serves it) and everywhere else */
+int coskad_layer_apply_window_ok(int T, int V, int Ci, int Co) { return (T != 12 && eval_layer_clip_ok(T, V, Ci, Co)) ? 1 : 0; }
+
+/* 1: coskad_layer_first_pair_apply_f32 takes the first layer (Ci = 2 -> Cm) with the layer behind it (Cm -> Co) on this layout */
+int coskad_layer_first_pair_ok(int T, int V, int Ci, int Cm, int Co) { return eval_first_pair_clip_ok(T, V, Ci, Cm, Co) ? 1 : 0; }
+
+/* The first two ST_GCNN layers of the encoder with folded BatchNorm (models/common/components.py:94-105 -> models/graph_layers/
+ * stsgcn.py:94-116 twice, eval mode) in ONE pass: out [B, Co, T, V] = layer2(PReLU_mid(layer1(x))), x [B, 2, T, V] the network input; the
+ * 32-channel activation between them never reaches HBM.  wfold1 [4, 32] / bias1 [32], wfold2 [64, Co] / bias2 from coskad_bn_fold_f32;
+ * out_slope may be NULL (pre-activation output). */
+int coskad_layer_first_pair_apply_f32(const float* x, float* out, const float* A1, const float* T1, const float* wfold1, const float* bias1,
+                                      const float* A2, const float* T2, const float* wfold2, const float* bias2, const float* mid_slope,
+                                      const float* out_slope, int B, int Cm, int Co, int T, int V, hipStream_t stream) {
+  if (!x || !out || !A1 || !T1 || !wfold1 || !bias1 || !A2 || !T2 || !wfold2 || !bias2 || !mid_slope)
+    return fail(COSKAD_ERR_ARG, "layer_first_pair_apply: null pointer");
+  if (B <= 0 || !eval_first_pair_clip_ok(T, V, 2, Cm, Co))
+    return fail(COSKAD_ERR_SHAPE, "layer_first_pair_apply: built for 8 / 12 / 16 / 24 x 17 / 25, 2 -> 32 -> 16 / 32 / 64 channels");
+  return launch_eval_first_pair_clip(x, out, A1, T1, wfold1, bias1, A2, T2, wfold2, bias2, mid_slope, out_slope, B, Co, T, V, stream);
+}
 
 }  // extern "C"
 

@@ -216,19 +216,16 @@ template <int T, int V>
 int launch_layer_apply_m(const float* in, float* out, const float* Aw, const float* Tw, const float* wfold,
                          const float* bias, const float* in_slope, const float* out_slope, int B, int Ci,
                          int Co, hipStream_t st, const float* Zg);
-// eval_layer_bpc.hip: the 25-joint layout, 16 / 32 input channels, one clip per four-wave workgroup
-bool eval_layer_bpc_ok(int T_, int V_, int Ci, int Co);
-int launch_eval_layer_bpc(const float* in, float* out, const float* Aw, const float* Tw, const float* wfold, const float* bias,
-                          const float* in_slope, const float* out_slope, int B, int Ci, int Co, int T_, int V_, hipStream_t st);
-// eval_layer_window.hip: the same layer (and the first pair 2 -> 32 -> Co) at the window lengths 8, 16 and 24, 17 / 25 joints; the
-// launchers check `in` / `out` for 16-byte alignment (COSKAD_ERR_ARG) before anything is launched
-bool eval_layer_window_ok(int T_, int V_, int Ci, int Co);
-int launch_eval_layer_window(const float* in, float* out, const float* Aw, const float* Tw, const float* wfold, const float* bias,
-                             const float* in_slope, const float* out_slope, int B, int Ci, int Co, int T_, int V_, hipStream_t st);
-bool eval_first_pair_window_ok(int T_, int V_, int Ci, int Cm, int Co);
-int launch_eval_first_pair_window(const float* x, float* out, const float* A1, const float* T1, const float* wfold1,
-                                  const float* bias1, const float* A2, const float* T2, const float* wfold2, const float* bias2,
-                                  const float* mid_slope, const float* out_slope, int B, int Co, int T_, int V_, hipStream_t st);
+// eval_layer_clip.hip: the folded layer (16 / 32 input channels) and the first pair 2 -> 32 -> Co, one clip per four-wave workgroup,
+// at 8 / 12 / 16 / 24 frames x 17 / 25 joints; at the window lengths 8 / 16 / 24 the launchers check `in` / `out` for 16-byte
+// alignment (COSKAD_ERR_ARG) before anything is launched
+bool eval_layer_clip_ok(int T_, int V_, int Ci, int Co);
+int launch_eval_layer_clip(const float* in, float* out, const float* Aw, const float* Tw, const float* wfold, const float* bias,
+                           const float* in_slope, const float* out_slope, int B, int Ci, int Co, int T_, int V_, hipStream_t st);
+bool eval_first_pair_clip_ok(int T_, int V_, int Ci, int Cm, int Co);
+int launch_eval_first_pair_clip(const float* x, float* out, const float* A1, const float* T1, const float* wfold1,
+                                const float* bias1, const float* A2, const float* T2, const float* wfold2, const float* bias2,
+                                const float* mid_slope, const float* out_slope, int B, int Co, int T_, int V_, hipStream_t st);
 // fused_apply.hip
 bool layer_apply_ring_ok(int T_, int V_, int Ci, int Co);
 int launch_layer_apply_ring(const float* Z, const float* in, float* out, const float* wfold, const float* bias,

@@ -260,12 +260,9 @@ static int launch_layer_apply(const float* in, float* out, const float* Aw, cons
                               const float* out_slope, int B, int Ci, int Co, hipStream_t st) {
   constexpr int kBlock = Geo<T, V>::Block;   // threads per block of this geometry
   constexpr int LD = Geo<T, V>::LD;
-  // -DCOSKAD_ABLATE builds: COSKAD_EVAL_TILE=1 takes the round-1 LDS-table kernel at these shapes too, COSKAD_VALU_FWD=1 the VALU
-  // kernel for every shape; the product library always takes the MFMA kernel when the tile fits the LDS
-  static const bool tile_only = ablate_env("COSKAD_EVAL_TILE", 0) == 1;
+  // -DCOSKAD_ABLATE builds: COSKAD_VALU_FWD=1 takes the VALU kernel for every shape; the product library always takes the MFMA kernel
+  // when the tile fits the LDS
   static const bool use_mfma = ablate_env("COSKAD_VALU_FWD", 0) != 1;
-  if (!tile_only && eval_layer_bpc_ok(T, V, Ci, Co))
-    return launch_eval_layer_bpc(in, out, Aw, Tw, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V, st);
   if (use_mfma) {
     const int rc = launch_layer_apply_m<T, V>(in, out, Aw, Tw, wfold, bias, in_slope, out_slope, B, Ci, Co, st, nullptr);
     if (rc <= 0) return rc;   // 1 = does not fit in LDS: VALU kernel below
@@ -317,8 +314,11 @@ int coskad_layer_apply_f32(const float* in, float* out, const float* A, const fl
                            hipStream_t stream) {
   if (!in || !out || !A || !Tm || !wfold || !bias) return fail(COSKAD_ERR_ARG, "layer_apply: null pointer");
   if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_apply: B=%d Ci=%d Co=%d", B, Ci, Co);
-  if (eval_layer_window_ok(T, V, Ci, Co))
-    return launch_eval_layer_window(in, out, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V, stream);
+  // the one-clip kernel where it is built (-DCOSKAD_ABLATE builds: COSKAD_EVAL_TILE=1 sends its T = 12 shapes to the round-1 LDS-table
+  // kernel below instead)
+  static const bool tile_only = ablate_env("COSKAD_EVAL_TILE", 0) == 1;
+  if (eval_layer_clip_ok(T, V, Ci, Co) && !(tile_only && T == 12))
+    return launch_eval_layer_clip(in, out, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V, stream);
 #define CALL(T_, V_) return launch_layer_apply<T_, V_>(in, out, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, stream)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL

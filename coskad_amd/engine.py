@@ -118,10 +118,10 @@ class ChainCtx:
     sync_count: float = 0.0                              # ... and the positions of the global batch
 
 
-# eval-mode forwards run the first two layers in one kernel where it is built (csrc/eval_layer_bpc.hip, FIRST form); tests flip it
+# eval-mode forwards run the first two layers in one kernel where it is built (csrc/eval_layer_clip.hip, FIRST form); tests flip it
 EVAL_FIRST_PAIR = True
-# eval-mode, no-grad forwards of window lengths 8 / 16 / 24 run their layers on the folded one-clip kernels where they are built
-# (csrc/eval_layer_window.hip; models/graph_layers/stsgcn.py: plan_stack); tests and tools/bench_eval_window.py flip it to get the
+# eval-mode, no-grad forwards of window lengths 8 / 16 / 24 run their layers on the folded one-clip kernel where it is built
+# (csrc/eval_layer_clip.hip; models/graph_layers/stsgcn.py: plan_stack); tests and tools/bench_eval_window.py flip it to get the
 # composed route
 EVAL_WINDOW = True
 # eval-mode, no-grad decoders run their last (C -> 2) layer on the one-clip tail kernel where it is built (csrc/eval_tail_window.hip:

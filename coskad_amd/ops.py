@@ -125,8 +125,8 @@ def layer_apply(x: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, bias: Tensor, C
 
 
 def layer_apply_window_ok(T: int, V: int, Ci: int, Co: int) -> bool:
-    """layer_apply is ONE launch (folded BatchNorm, one clip per workgroup: csrc/eval_layer_window.hip) at this window length other
-    than 12; False at T = 12, whose layers `layer_fits` describes"""
+    """layer_apply is ONE launch (folded BatchNorm, one clip per workgroup: csrc/eval_layer_clip.hip) at this window length other
+    than 12; False at T = 12, whose layers `layer_fits` describes (the same kernel serves them at 17 / 25 joints)"""
     return bool(_lib.lib().coskad_layer_apply_window_ok(T, V, Ci, Co))
 
 
@@ -171,8 +171,8 @@ def layer_tail(x_in: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, bias: Tensor,
 
 
 def layer_first_pair_ok(Ci: int, Cm: int, Co: int, T: int, V: int) -> bool:
-    """the first layer (2 -> Cm) and the layer behind it (Cm -> Co), folded, in one pass (csrc/eval_layer_bpc.hip, FIRST form; window
-    lengths 8 / 16 / 24: csrc/eval_layer_window.hip)"""
+    """the first layer (2 -> Cm) and the layer behind it (Cm -> Co), folded, in one pass (csrc/eval_layer_clip.hip, FIRST form: 8 / 12 /
+    16 / 24 frames)"""
     return bool(_lib.lib().coskad_layer_first_pair_ok(T, V, Ci, Cm, Co))
 
 

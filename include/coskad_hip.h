@@ -57,8 +57,9 @@ int coskad_bn_fold_f32(const float* Wt, const float* bt, const float* gamma_t, c
  *   out = [PReLU_out]( Wz . gcn([PReLU_in] in) + Wx . [PReLU_in] in + b )
  * in_slope / out_slope: device pointers to the 1-element PReLU weight, or NULL to skip.
  * (T, V): T = 12, or a window length where coskad_layer_apply_window_ok(T, V, Ci, Co) holds: there the layer is one launch with one clip
- * per workgroup (csrc/eval_layer_window.hip), `in` and `out` must be 16-byte aligned (COSKAD_ERR_ARG naming the pointer otherwise, before
- * anything is launched), wfold is [2*Ci][Co].  Other geometries fail with COSKAD_ERR_SHAPE ("unsupported ..."). */
+ * per workgroup (csrc/eval_layer_clip.hip, which also serves T = 12 at 17 / 25 joints and those channels), `in` and `out` must be
+ * 16-byte aligned at the window lengths 8 / 16 / 24 (COSKAD_ERR_ARG naming the pointer otherwise, before anything is launched; not asked
+ * for at T = 12), wfold is [2*Ci][Co].  Other geometries fail with COSKAD_ERR_SHAPE ("unsupported ..."). */
 int coskad_layer_apply_window_ok(int T, int V, int Ci, int Co);
 int coskad_layer_apply_f32(const float* in, float* out, const float* A, const float* Tm,
                            const float* wfold, const float* bias, const float* in_slope,
@@ -540,7 +541,7 @@ int coskad_layer_apply_next_flat_f32(const float* Z, const float* in, float* out
 /* The FIRST two ST_GCNN layers of the encoder with folded BatchNorm (coskad_layer_apply_f32 twice: models/graph_layers/stsgcn.py:94-116
  * in eval mode, entries 0 and 1 of the nn.Sequential of models/common/components.py:94-105) in ONE pass -- x [B, 2, T, V] is the network
  * input, the first layer (2 -> 32) is formed per clip on the VALU inside the second layer's kernel and its output never reaches HBM
- * (csrc/eval_layer_bpc.hip; window lengths 8 / 16 / 24: csrc/eval_layer_window.hip, x and out 16-byte aligned).  ok: 1 when
+ * (csrc/eval_layer_clip.hip, FIRST form; at the window lengths 8 / 16 / 24 x and out must be 16-byte aligned).  ok: 1 when
  * (n_frames, n_joints, C_in, C_mid, C_out) is built (8 | 12 | 16 | 24, 17 | 25, 2, 32, 16 | 32 | 64).
  * wfold1 [4, 32] / bias1, wfold2 [64, Co] / bias2 from coskad_bn_fold_f32; mid_slope: the first layer's PReLU weight; out_slope NULL:
  * pre-activation output. */

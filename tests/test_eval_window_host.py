@@ -1,4 +1,4 @@
-"""CPU checks of the folded one-clip layer kernels at the window lengths 8 / 16 / 24 (csrc/eval_layer_window.hip): the set the
+"""CPU checks of the folded one-clip layer kernel at the window lengths 8 / 16 / 24 (csrc/eval_layer_clip.hip): the set the
 library's predicate states, how plan_stack routes a stack of layers, and what the C ABI says before it touches a
 device.  No kernel runs."""
 import ctypes

@@ -1,6 +1,6 @@
-"""GPU parity of the folded one-clip layer kernels at the window lengths 8 / 16 / 24 (csrc/eval_layer_window.hip) against the fp64
-formula on the CPU: every layer shape through the C ABI, the persistent loop, the first pair, the encoder model on the new route and
-on the composed one, a fold that must not survive a training step, and a decoder stack that mixes the routes."""
+"""GPU parity of the folded one-clip layer kernel (csrc/eval_layer_clip.hip: 8 / 12 / 16 / 24 frames) against the fp64 formula on the
+CPU: every layer shape through the C ABI, the persistent loop, the first pair; and at the window lengths 8 / 16 / 24 the encoder model
+on the window route and on the composed one, a fold that must not survive a training step, and a decoder stack that mixes the routes."""
 import numpy as np
 import pytest
 import torch
@@ -93,14 +93,14 @@ class _Layer:
             _guards_untouched(p, NAN, n)
 
 
-LAYER_CASES = [(T, V, Ci, Co) for T, V in GEOMETRIES for Ci in (16, 32) for Co in (16, 32, 64)]
+LAYER_CASES = [(T, V, Ci, Co) for T, V in GEOMETRIES + [(12, 17), (12, 25)] for Ci in (16, 32) for Co in (16, 32, 64)]
 
 
 @pytest.mark.parametrize("T,V,Ci,Co", LAYER_CASES)
 def test_layer_matches_fp64(T, V, Ci, Co):
     """(8, 17, *, 16): 9 position tiles, 3 per wave -- the fourth wave owns none"""
     from coskad_amd import ops
-    assert ops.layer_apply_window_ok(T, V, Ci, Co)
+    assert ops.layer_apply_window_ok(T, V, Ci, Co) == (T != 12)
     first_half = LAYER_CASES.index((T, V, Ci, Co)) % 2 == 0
     L = _Layer(T, V, Ci, Co, seed=T * 1000 + V * 10 + Ci + Co, slope_in=first_half, slope_out=not first_half)
     x = torch.randn(3, Ci, T, V, generator=L.g)
@@ -120,8 +120,9 @@ def test_layer_matches_fp64(T, V, Ci, Co):
 # the persistent grid: a workgroup takes clips blockIdx.x, blockIdx.x + grid, ..; grid = min(B, 256 CUs x workgroups per CU).
 # (8, 17, 32 -> 32): 17.7 KB of image and 110 registers: 3 per CU, cap 768.  (24, 17, 32 -> 64): 52 KB of image (the 64 channels leave in
 # two rounds through 32 rows) and 229 registers: 2 per CU, cap 512.  B = 2 cap + 3: three workgroups go round three times, the others
-# twice, and the last round's prefetch finds no clip.
-LOOP_CASES = [(8, 17, 32, 32, 768), (24, 17, 32, 64, 512)]
+# twice, and the last round's prefetch finds no clip.  (12, 17, 32 -> 32) and (12, 25, 16 -> 32): the 12-frame choices are pinned
+# where Geo<>'s rule would ask for 3 and for 2 per CU: 2 per CU, cap 512, and 3 per CU, cap 768.
+LOOP_CASES = [(8, 17, 32, 32, 768), (24, 17, 32, 64, 512), (12, 17, 32, 32, 512), (12, 25, 16, 32, 768)]
 
 
 @pytest.mark.parametrize("T,V,Ci,Co,cap", LOOP_CASES)
@@ -140,8 +141,10 @@ def test_persistent_loop(T, V, Ci, Co, cap):
         assert torch.equal(one.cpu()[0], got[clip]), f"clip {clip} differs from a one-clip call"
 
 
-# first pair at (16, 25) -> 16: 38 rows = 61 KB of image: 2 per CU, cap 512
-PAIR_CASES = [(T, V, Co, 3) for T, V in GEOMETRIES for Co in (16, 32, 64)] + [(16, 25, 16, 512 + 2)]
+# first pair at (16, 25) -> 16: 38 rows = 61 KB of image: 2 per CU, cap 512; at (12, 25) -> 64: x, Y0, Z0 in rows 32..37 of the 64-row
+# image: 2 per CU, cap 512
+PAIR_CASES = ([(T, V, Co, 3) for T, V in GEOMETRIES + [(12, 17), (12, 25)] for Co in (16, 32, 64)]
+              + [(16, 25, 16, 512 + 2), (12, 25, 64, 512 + 2)])
 
 
 @pytest.mark.parametrize("T,V,Co,B", PAIR_CASES)

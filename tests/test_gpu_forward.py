@@ -308,7 +308,7 @@ def test_chain_forward_fused_next_vs_separate_25_joints(B):
 @pytest.mark.gpu
 @pytest.mark.parametrize("V,B", [(25, 3), (25, 1030), (17, 37)])
 def test_eval_first_layer_inside_the_second_layers_kernel(V, B, monkeypatch):
-    """Eval mode: layer 1 (2 -> 32) formed on the VALU inside layer 2's kernel (csrc/eval_layer_bpc.hip, FIRST form) against the same
+    """Eval mode: layer 1 (2 -> 32) formed on the VALU inside layer 2's kernel (csrc/eval_layer_clip.hip, FIRST form) against the same
     stack run layer by layer (17 joints: a non-default stack, the default one runs the fused encoder)."""
     import numpy as np
     from coskad_amd import engine, ops

@@ -1,4 +1,4 @@
-"""Scoring speed at the window lengths 8 / 16 / 24 (dataset_seg_len): the folded one-clip layer kernels of csrc/eval_layer_window.hip.
+"""Scoring speed at the window lengths 8 / 16 / 24 (dataset_seg_len): the folded one-clip layer kernel of csrc/eval_layer_clip.hip.
 
 (a) --model: the default-width encoder (STS-GCN 2-32-16-32-64, `linear` projector, latent 16) in eval mode under no_grad, `encode` at
     B = 4096, at (T, V) = (8, 17), (16, 17), (24, 17), (8, 25) (--all-geometries: all six).  Only the public model surface is used, so the
@@ -6,7 +6,7 @@
     --composed flips engine.EVAL_WINDOW where it exists: the composed route on this build, a cross-check and not the yardstick.
 (b) --kernels: every layer shape 16 / 32 -> 16 / 32 / 64 and every first pair 2 -> 32 -> 16 / 32 / 64 at every (T, V) through
     ops.layer_apply / ops.layer_first_pair_apply, as us and as GB/s on the algorithmic bytes (the input and the output tensor), beside
-    the T = 12 kernel at the same V and channels IN THE SAME RUN.  The yardstick is that T = 12 GB/s minus 3 % (twice the +-1.5 %
+    the same kernel at T = 12, same V and channels, IN THE SAME RUN.  The yardstick is that T = 12 GB/s minus 3 % (twice the +-1.5 %
     box-to-box spread); misses are printed as misses.
 
 Warm-up first, then the median of >= 3 timed blocks (HIP events; every block printed).
