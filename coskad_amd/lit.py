@@ -220,11 +220,25 @@ class LitEncoder(nn.Module):
     def _score_windows(self, scores, trans, meta, frames) -> float:
         """window scores -> frames -> persons -> smoothing -> transformations -> AUC (eval_COSKAD.py:140-253)."""
         num_transform = max(1, int(getattr(self.args, "dataset_num_transform", 1)))
-        auc, per_t, gt = eval_utils.score_dataset(scores, trans, meta, frames, self._load_gts(), num_transform,
-                                                  smoothing=int(getattr(self.args, "smoothing", 50)),
-                                                  dataname=getattr(self.args, "dataset_choice", "UBnormal"),
-                                                  pad_size=int(getattr(self.args, "pad_size", -1)),
-                                                  hr_masks=self._load_hr_masks())
+        gts, pad_size, hr_masks = self._load_gts(), int(getattr(self.args, "pad_size", -1)), self._load_hr_masks()
+        # `device_scoring` (not a key of the reference's yamls either): scores that live on the GPU are turned into the frame-level AUC
+        # by the scoring kernels on a plan of the window table, built at the first call and reused while the table is the same one,
+        # unless the yaml says `device_scoring: false` (then: eval_utils.score_dataset, as for scores on the host)
+        if bool(getattr(self.args, "device_scoring", True)) and torch.as_tensor(scores).is_cuda:
+            plan = getattr(self, "_score_plan", None)
+            if plan is None or plan.win_ptr.device != scores.device or not plan.same_setting(gts, num_transform, pad_size, hr_masks) \
+                    or not plan.matches(trans, meta, frames):
+                plan = eval_utils.ScorePlan(trans, meta, frames, gts, num_transform, pad_size=pad_size, hr_masks=hr_masks,
+                                            device=scores.device)
+                object.__setattr__(self, "_score_plan", plan)      # not a submodule, not part of the state dict
+            auc, per_t_dev, gt = eval_utils.score_dataset_device(scores, plan)
+            per_t_host = per_t_dev.cpu().numpy()                   # one device -> host copy
+            per_t = {t: per_t_host[t] for t in range(num_transform)}
+        else:
+            auc, per_t, gt = eval_utils.score_dataset(scores, trans, meta, frames, gts, num_transform,
+                                                      smoothing=int(getattr(self.args, "smoothing", 50)),
+                                                      dataname=getattr(self.args, "dataset_choice", "UBnormal"),
+                                                      pad_size=pad_size, hr_masks=hr_masks)
         self.log("validation_auc", auc)
         self.last_scores = per_t
         return auc

@@ -1376,3 +1376,58 @@ def gather_transform(xy, mats, index, T, V):
     out = torch.empty(B, 2, T, V, device=xy.device, dtype=torch.float32)
     call("coskad_gather_transform_f32", xy, index, mats, out, B, N, mats.shape[0], T * V, _stream())
     return out
+
+
+# ---- frame-level scoring of a validation pass (csrc/score_frames.hip; tables from utils/score_plan.ScorePlan) ----
+
+def score_person_frames(scores, win_ptr, win_idx):
+    """pf [win_ptr.numel() - 1] float64: per (person, frame) the mean of the covering windows' scores that are not exactly 0
+    (0 when none is left); scores float32 or float64, widened on load."""
+    if scores.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"scores: expected float32 or float64, got {scores.dtype}")
+    _chk(scores, "scores", dtype=scores.dtype); _chk(win_ptr, "win_ptr", dtype=torch.int32); _chk(win_idx, "win_idx", dtype=torch.int32)
+    rows = win_ptr.numel() - 1
+    pf = torch.empty(rows, device=scores.device, dtype=torch.float64)
+    call("coskad_score_person_frames_f64", scores, int(scores.dtype == torch.float64), win_ptr, win_idx, pf, scores.numel(), rows, _stream())
+    return pf
+
+
+def score_pad_(pf, row_ptr, pad_size, n_max):
+    """pad_scores (utils/eval_utils.py:232-248) on every person's row pf[row_ptr[p] : row_ptr[p + 1]], in place."""
+    _chk(pf, "pf", dtype=torch.float64); _chk(row_ptr, "row_ptr", dtype=torch.int32)
+    call("coskad_score_pad_f64", pf, row_ptr, row_ptr.numel() - 1, pad_size, n_max, _stream())
+    return pf
+
+
+def score_clip_max(pf, row_ptr, pc_ptr, out_clip, out_frame, n_clips, n_transform):
+    """raw [n_transform, F] float64: max over each clip's persons, gathered into the concatenated output layout."""
+    _chk(pf, "pf", dtype=torch.float64)
+    for n, t in (("row_ptr", row_ptr), ("pc_ptr", pc_ptr), ("out_clip", out_clip), ("out_frame", out_frame)):
+        _chk(t, n, dtype=torch.int32)
+    _chk(pc_ptr, "pc_ptr", (n_transform * n_clips + 1,), dtype=torch.int32); _chk(out_frame, "out_frame", out_clip.shape, dtype=torch.int32)
+    F = out_clip.numel()
+    raw = torch.empty(n_transform, F, device=pf.device, dtype=torch.float64)
+    call("coskad_score_clip_max_f64", pf, row_ptr, pc_ptr, out_clip, out_frame, raw, n_clips, n_transform, F, _stream())
+    return raw
+
+
+def score_smooth(raw, tiles, taps):
+    """Shift by 11 and gaussian_filter1d(sigma 30, reflect) per clip segment: raw [n_transform, F] -> (per_t [n_transform, F],
+    mean over the transformations [F]); tiles [n_tiles, 3] = (segment start, segment end, tile start)."""
+    _chk(raw, "raw", dtype=torch.float64); _chk(tiles, "tiles", (tiles.shape[0], 3), dtype=torch.int32); _chk(taps, "taps", dtype=torch.float64)
+    nt, F = raw.shape
+    per_t, mean = torch.empty_like(raw), torch.empty(F, device=raw.device, dtype=torch.float64)
+    call("coskad_score_smooth_f64", raw, tiles, taps, taps.numel(), per_t, mean, tiles.shape[0], nt, F, _stream())
+    return per_t, mean
+
+
+def score_auc(sorted_scores, gt_sorted, cum_neg):
+    """[AUC, n_pos, n_neg] float64 on the device from ascending scores, the ground truth in that order (int32, non-zero = positive) and
+    its inclusive count of negatives (int64): the tie-aware Mann-Whitney statistic, formed in int64.  AUC is NaN for a single class."""
+    F = sorted_scores.numel()
+    _chk(sorted_scores, "sorted_scores", dtype=torch.float64); _chk(gt_sorted, "gt_sorted", (F,), dtype=torch.int32)
+    _chk(cum_neg, "cum_neg", (F,), dtype=torch.int64)
+    out = torch.empty(3, device=sorted_scores.device, dtype=torch.float64)
+    ws = torch.empty(max(1, _lib.lib().coskad_score_auc_ws(F)), device=sorted_scores.device, dtype=torch.int64)
+    call("coskad_score_auc_f64", sorted_scores, gt_sorted, cum_neg, out, ws, ws.numel(), F, _stream())
+    return out

@@ -6,6 +6,9 @@ The reference walks transformations x clips x persons in Python and scatters one
 poincare_head: MSELoss(reduction='none')(c,z).mean(-1) resp. dist(c, zh)), and the aggregation is ONE segmented
 reduction keyed on (transformation, scene, clip, person, frame) with torch index ops on whatever device the
 scores live on.  Smoothing and AUC use the same scipy / sklearn calls as the reference (eval_utils.py:206,218).
+
+`score_dataset_device` (utils/score_plan.py) is the same scoring on the device: index tables derived once from the window table
+(`ScorePlan`) and the kernels of csrc/score_frames.hip per call; `score_dataset` below stays the host route and the yardstick.
 """
 from __future__ import annotations
 
@@ -15,6 +18,8 @@ import numpy as np
 import torch
 from scipy.ndimage import gaussian_filter1d
 from sklearn.metrics import roc_auc_score
+
+from .score_plan import ScorePlan, auc_device, gaussian_taps, score_dataset_device   # noqa: F401  (the device route of score_dataset)
 
 
 def score_process(score: np.ndarray, win_size: int = 50, dataname: str = 'STC', use_scaler: bool = False) -> np.ndarray:

@@ -460,6 +460,34 @@ int coskad_btlnk_bwd_chain_f32(const float* U, const float* W, const float* dz, 
 int coskad_gather_transform_f32(const float* xy, const long long* index, const float* mats, float* out, int B, int N,
                                 int ntrans, int TV, hipStream_t stream);
 
+/* ---- frame-level scoring of a validation pass (csrc/score_frames.hip) ------------------------------- */
+
+/* Per-window scores -> frame-level AUC on index tables that coskad_amd.utils.score_plan.ScorePlan derives once from the window table
+ * (eval_COSKAD.py:140-253, utils/eval_utils.py:200-248).  fp64, fixed summation order, no floating-point atomics: deterministic.
+ *   person_frames: pf[e] = mean of scores[win_idx[k]] != 0 over k in [win_ptr[e], win_ptr[e+1]) (0 when none is left); e = one
+ *                  (person, frame), n_rows of them; scores: n_scores floats (scores_f64 = 0) or doubles (1)
+ *   pad          : pad_scores on every person's row pf[row_ptr[p] .. row_ptr[p+1]) in place; n_max = the longest row, at most
+ *                  coskad_score_pad_row_max() frames
+ *   clip_max     : raw[t, o] = max over the persons pc_ptr[t n_clips + c] .. pc_ptr[t n_clips + c + 1] of pf[row_ptr[p] + out_frame[o]],
+ *                  c = out_clip[o]; 0 for a clip without persons; raw: [n_transform, F]
+ *   smooth       : per segment [seg0, seg1) of the F positions: shift by 11, reflect boundary, symmetric filter of taps[0] (centre) ..
+ *                  taps[120]; tiles: n_tiles rows of {seg0, seg1, tile start}, coskad_score_tile() outputs each; per_t [n_transform, F],
+ *                  mean [F] = their mean over the transformations
+ *   auc          : sorted_scores ascending, gt_sorted the ground truth in that order (non-zero = positive), cum_neg its inclusive count
+ *                  of negatives; out = {AUC, n_pos, n_neg} (AUC NaN when one class is empty); ws: coskad_score_auc_ws(F) elements */
+int coskad_score_pad_row_max(void);
+int coskad_score_tile(void);
+int coskad_score_auc_ws(int F);
+int coskad_score_person_frames_f64(const void* scores, int scores_f64, const int* win_ptr, const int* win_idx, double* pf,
+                                   int n_scores, int n_rows, hipStream_t stream);
+int coskad_score_pad_f64(double* pf, const int* row_ptr, int n_persons, int pad_size, int n_max, hipStream_t stream);
+int coskad_score_clip_max_f64(const double* pf, const int* row_ptr, const int* pc_ptr, const int* out_clip, const int* out_frame,
+                              double* raw, int n_clips, int n_transform, int F, hipStream_t stream);
+int coskad_score_smooth_f64(const double* raw, const int* tiles, const double* taps, int n_taps, double* per_t, double* mean,
+                            int n_tiles, int n_transform, int F, hipStream_t stream);
+int coskad_score_auc_f64(const double* sorted_scores, const int* gt_sorted, const long long* cum_neg, double* out, long long* ws,
+                         size_t ws_elems, int F, hipStream_t stream);
+
 /* ---- one-class heads, centre statistics, regulariser, optimiser ------------------------ */
 
 int coskad_head_slots(void);            /* floats in a stats / acc block (19) at latent <= 16 */
