@@ -256,5 +256,11 @@ int wide_btlnk_fwd(const float* U, const float* W, const float* bias, const floa
                    hipStream_t stream);
 int wide_btlnk_bwd(const float* U, const float* W, const float* dz, const float* slope, float* dU, float* dW, float* db,
                    float* dslope, void* ws, int accumulate, int B, int K, int L, hipStream_t stream);
+// rev_btlnk_wide.hip: the decoder entry at latents 17 .. 512 (N % 4 == 0), behind coskad_rev_btlnk_{fwd,bwd}_f32; ws in floats
+bool wide_rev_btlnk_ok(int N, int L);
+size_t wide_rev_btlnk_ws_floats(int B, int N, int L);
+int wide_rev_btlnk_fwd(const float* z, const float* W, const float* bias, float* H, int B, int N, int L, hipStream_t stream);
+int wide_rev_btlnk_bwd(const float* dH, const float* z, const float* W, float* dz, int dz_accumulate, float* dW, float* db, int accumulate,
+                       float* ws, int B, int N, int L, hipStream_t stream);
 
 }  // namespace coskad

@@ -1,5 +1,5 @@
 // `rev_btlnk` of the decoder models (reference models/sts/ae.py:223-227: nn.Linear(latent_dim -> hidden * T * V) in front of the
-// decoder) and its autograd, for latent_dim <= 16:
+// decoder) and its autograd, for latent_dim in {8, 16} (17 .. 512: the MFMA GEMMs of csrc/rev_btlnk_wide.hip, same entry points):
 //     H[b][n]   = sum_l z[b][l] W[n][l] + bias[n]                       forward   (N = hidden T V = 13 056 / 19 200 outputs)
 //     dz[b][l] (+)= sum_n dH[b][n] W[n][l]                              data gradient
 //     dW[n][l]  = sum_b dH[b][n] z[b][l],   db[n] = sum_b dH[b][n]      parameter gradients
@@ -9,6 +9,7 @@
 // consecutive outputs n (float4 lines), the latent row of a clip is wave-uniform (scalar loads), reductions over clips or over n are
 // two-stage in a fixed order (deterministic, no atomics).
 #include "common.h"
+#include "layer_launch.h"
 
 namespace coskad {
 namespace rb {
@@ -153,13 +154,21 @@ using namespace coskad;
 extern "C" {
 
 /* floats of scratch coskad_rev_btlnk_bwd_f32 needs (partial dW / db per clip slice) */
-size_t coskad_rev_btlnk_ws_floats(int B, int N, int L) { return (size_t)rb::slices(B, N) * (size_t)N * (L + 1); }
+size_t coskad_rev_btlnk_ws_floats(int B, int N, int L) {
+  if (L > 16) return wide_rev_btlnk_ws_floats(B, N, L);
+  return (size_t)rb::slices(B, N) * (size_t)N * (L + 1);
+}
 
-/* H = z W^T + bias  (ae.py:223-227): z [B, L], W [N, L], bias [N] or NULL, H [B, N]; L in {8, 16}, N % 4 == 0 */
+/* 1 when latent L takes the MFMA GEMMs of csrc/rev_btlnk_wide.hip: 16 < L <= 512, N % 4 == 0 */
+int coskad_rev_btlnk_wide_ok(int N, int L) { return wide_rev_btlnk_ok(N, L) ? 1 : 0; }
+
+/* H = z W^T + bias  (ae.py:223-227): z [B, L], W [N, L], bias [N] or NULL, H [B, N]; L in {8, 16} or 17 .. 512, N % 4 == 0 */
 int coskad_rev_btlnk_fwd_f32(const float* z, const float* W, const float* bias, float* H, int B, int N, int L, hipStream_t stream) {
   if (!z || !W || !H) return fail(COSKAD_ERR_ARG, "rev_btlnk_fwd: null pointer");
-  if (B <= 0 || N <= 0 || N % 4 || (L != 8 && L != 16)) return fail(COSKAD_ERR_SHAPE, "rev_btlnk_fwd: B=%d N=%d L=%d (L in {8,16}, N %% 4 == 0)", B, N, L);
+  if (B <= 0 || N <= 0 || N % 4 || (L != 8 && L != 16 && !wide_rev_btlnk_ok(N, L)))
+    return fail(COSKAD_ERR_SHAPE, "rev_btlnk_fwd: B=%d N=%d L=%d (L in {8,16} or 17..512, N %% 4 == 0)", B, N, L);
   if ((size_t)H & 15) return fail(COSKAD_ERR_ARG, "rev_btlnk_fwd: H must be 16-byte aligned");
+  if (L > 16) return wide_rev_btlnk_fwd(z, W, bias, H, B, N, L, stream);
   const int S = B < 64 ? 1 : (B < 1024 ? 4 : rb::slices(B, N));
   const int chunk = ceil_div(B, S);
   dim3 grid(ceil_div(N / 4, 256), S);
@@ -173,7 +182,9 @@ int coskad_rev_btlnk_fwd_f32(const float* z, const float* W, const float* bias, 
 int coskad_rev_btlnk_bwd_f32(const float* dH, const float* z, const float* W, float* dz, int dz_accumulate, float* dW, float* db,
                              int accumulate, float* ws, int B, int N, int L, hipStream_t stream) {
   if (!dH || !z || !W || !dz || !dW || !ws) return fail(COSKAD_ERR_ARG, "rev_btlnk_bwd: null pointer");
-  if (B <= 0 || N <= 0 || N % 4 || (L != 8 && L != 16)) return fail(COSKAD_ERR_SHAPE, "rev_btlnk_bwd: B=%d N=%d L=%d (L in {8,16}, N %% 4 == 0)", B, N, L);
+  if (B <= 0 || N <= 0 || N % 4 || (L != 8 && L != 16 && !wide_rev_btlnk_ok(N, L)))
+    return fail(COSKAD_ERR_SHAPE, "rev_btlnk_bwd: B=%d N=%d L=%d (L in {8,16} or 17..512, N %% 4 == 0)", B, N, L);
+  if (L > 16) return wide_rev_btlnk_bwd(dH, z, W, dz, dz_accumulate, dW, db, accumulate, ws, B, N, L, stream);
   if ((size_t)dH & 15) return fail(COSKAD_ERR_ARG, "rev_btlnk_bwd: dH must be 16-byte aligned");
   const int S = rb::slices(B, N), chunk = ceil_div(B, S);
   dim3 grid(ceil_div(N / 4, 256), S);

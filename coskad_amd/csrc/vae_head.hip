@@ -9,28 +9,15 @@
 //   sample  t = 2 x_0 - 1;  y = [t, sqrt(1 - t^2) eps / |eps|];  u = (e1 - mu) / |e1 - mu|;  z = y - 2 (y.u) u   (Householder)
 //           kl  = -H(PowerSpherical(mu, kappa)) + H(Uniform(S^{d-1}))  per row;  1 / kappa per row
 //   bwd     d m, d v from dz (the decoder's gradient) and the two scalar loss weights
-// One thread per clip, the latent (d <= 16) in registers; digamma / trigamma by recurrence + asymptotic series in fp64.
+// One thread per clip, the latent (d <= 16) in registers; digamma / trigamma by recurrence + asymptotic series in fp64 (ps_math.h).
+// 16 < d <= 512: csrc/vae_head_wide.hip, behind the same entry points.
 #include "common.h"
+#include "ps_math.h"
 
 namespace coskad {
 namespace vh {
 
 constexpr int LMAX = 16;
-constexpr double kLog2 = 0.6931471805599453, kLogPi = 1.1447298858494002;
-
-__device__ __forceinline__ double digamma_d(double x) {       // x > 0
-  double r = 0.0;
-  while (x < 6.0) { r -= 1.0 / x; x += 1.0; }
-  const double f = 1.0 / (x * x);
-  return r + log(x) - 0.5 / x - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))));
-}
-__device__ __forceinline__ double trigamma_d(double x) {      // x > 0
-  double r = 0.0;
-  while (x < 6.0) { r += 1.0 / (x * x); x += 1.0; }
-  const double f = 1.0 / (x * x);
-  return r + 1.0 / x + 0.5 * f + (1.0 / x) * f * (1.0 / 6 - f * (1.0 / 30 - f * (1.0 / 42 - f * (1.0 / 30 - f * (5.0 / 66)))));
-}
-__device__ __forceinline__ float softplus_f(float v) { return v > 20.f ? v : log1pf(expf(v)); }   // F.softplus(beta = 1, threshold = 20)
 
 struct Row {
   float v[LMAX];
@@ -180,7 +167,8 @@ extern "C" {
 int coskad_ps_head_prep_f32(const float* mean_raw, int ld_mean, const float* var_raw, int ld_var, float* mu, float* kappa,
                             float* concentration, float* total, int B, int L, hipStream_t stream) {
   if (!mean_raw || !var_raw || !mu || !kappa || !concentration || !total) return fail(COSKAD_ERR_ARG, "ps_head_prep: null pointer");
-  if (B <= 0 || L < 2 || L > vh::LMAX || ld_mean < L || ld_var < 1) return fail(COSKAD_ERR_SHAPE, "ps_head_prep: B=%d latent=%d", B, L);
+  if (B <= 0 || L < 2 || L > vh::kWideLMax || ld_mean < L || ld_var < 1) return fail(COSKAD_ERR_SHAPE, "ps_head_prep: B=%d latent=%d", B, L);
+  if (L > vh::LMAX) return wide_ps_head_prep(mean_raw, ld_mean, var_raw, ld_var, mu, kappa, concentration, total, B, L, stream);
   hipLaunchKernelGGL(vh::k_ps_prep, dim3(ceil_div(B, 256)), dim3(256), 0, stream, mean_raw, ld_mean, var_raw, ld_var, mu, kappa,
                      concentration, total, B, L);
   return check_launch("ps_head_prep");
@@ -189,7 +177,8 @@ int coskad_ps_head_prep_f32(const float* mean_raw, int ld_mean, const float* var
 int coskad_ps_head_sample_f32(const float* x, const float* eps, const float* mu, const float* kappa, float* z, float* kl,
                               float* inv_kappa, int B, int L, hipStream_t stream) {
   if (!x || !eps || !mu || !kappa || !z || !kl || !inv_kappa) return fail(COSKAD_ERR_ARG, "ps_head_sample: null pointer");
-  if (B <= 0 || L < 2 || L > vh::LMAX) return fail(COSKAD_ERR_SHAPE, "ps_head_sample: B=%d latent=%d", B, L);
+  if (B <= 0 || L < 2 || L > vh::kWideLMax) return fail(COSKAD_ERR_SHAPE, "ps_head_sample: B=%d latent=%d", B, L);
+  if (L > vh::LMAX) return wide_ps_head_sample(x, eps, mu, kappa, z, kl, inv_kappa, B, L, stream);
   hipLaunchKernelGGL(vh::k_ps_sample, dim3(ceil_div(B, 256)), dim3(256), 0, stream, x, eps, mu, kappa, z, kl, inv_kappa, B, L);
   return check_launch("ps_head_sample");
 }
@@ -200,8 +189,11 @@ int coskad_ps_head_bwd_f32(const float* dz, const float* x, const float* dirichl
                            hipStream_t stream) {
   if (!dz || !x || !dirichlet_grad || !eps || !mu || !kappa || !mean_raw || !var_raw || !d_mean_raw || !d_var_raw)
     return fail(COSKAD_ERR_ARG, "ps_head_bwd: null pointer");
-  if (B <= 0 || L < 2 || L > vh::LMAX || ld_mean < L || ld_var < 1 || ld_dmean < L || ld_dvar < 1)
+  if (B <= 0 || L < 2 || L > vh::kWideLMax || ld_mean < L || ld_var < 1 || ld_dmean < L || ld_dvar < 1)
     return fail(COSKAD_ERR_SHAPE, "ps_head_bwd: B=%d latent=%d", B, L);
+  if (L > vh::LMAX)
+    return wide_ps_head_bwd(dz, x, dirichlet_grad, eps, mu, kappa, mean_raw, ld_mean, var_raw, ld_var, w_kl, w_exp, d_mean_raw, ld_dmean,
+                            d_var_raw, ld_dvar, B, L, stream);
   hipLaunchKernelGGL(vh::k_ps_bwd, dim3(ceil_div(B, 256)), dim3(256), 0, stream, dz, x, dirichlet_grad, eps, mu, kappa, mean_raw,
                      ld_mean, var_raw, ld_var, w_kl, w_exp, d_mean_raw, ld_dmean, d_var_raw, ld_dvar, B, L);
   return check_launch("ps_head_bwd");

@@ -279,8 +279,10 @@ class _AutogradLit(LitEncoder):
         where the model is within its kernels; torch autograd + torch.optim.Adam over the module surface otherwise."""
         from .trainer import make_decoder_step
         self._flat = None
+        # `flat_wide_latent` (not a key of the reference's yamls; default on): false keeps a model with latent_dim > 16 on the autograd route
         if next(self.model.parameters()).is_cuda:
             self._flat = make_decoder_step(self.model, mode, fused_window=bool(getattr(self.args, "fused_window", True)),
+                                           wide_latent=bool(getattr(self.args, "flat_wide_latent", True)),
                                            lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)), **weights)
         if self._flat is None:
             self._opt = torch.optim.Adam(self.model.parameters(), lr=self.learning_rate)

@@ -43,7 +43,8 @@ class _BottleneckFn(torch.autograd.Function):
 
 
 class _RevBtlnkFn(torch.autograd.Function):
-    """H = Linear(latent -> hidden*T*V)(Z)  (reference ae.py:223-227) and its autograd on csrc/rev_btlnk.hip."""
+    """H = Linear(latent -> hidden*T*V)(Z)  (reference ae.py:223-227) and its autograd on csrc/rev_btlnk.hip (latent 8 / 16) or
+    csrc/rev_btlnk_wide.hip (17 .. 512)."""
 
     @staticmethod
     def forward(ctx, Z, W, b):
@@ -216,12 +217,17 @@ class STSAE(STSE):
         folded = self._decode_folded(Z, B * M, T, V)
         if folded is not None:
             return folded
-        if Z.is_cuda and Z.dtype == torch.float32 and ops.rev_btlnk_ok(self.rev_btlnk.out_features, self.latent_dim):
-            H = _RevBtlnkFn.apply(Z, self.rev_btlnk.weight, self.rev_btlnk.bias)   # streaming kernels of csrc/rev_btlnk.hip
+        if Z.is_cuda and Z.dtype == torch.float32 and self._rev_on_hip():
+            H = _RevBtlnkFn.apply(Z, self.rev_btlnk.weight, self.rev_btlnk.bias)   # csrc/rev_btlnk.hip / rev_btlnk_wide.hip
         else:
             H = self.rev_btlnk(Z)        # other latent sizes: torch
         H = H.view(B * M, C, T, V)
         return self.decoder(H)
+
+    def _rev_on_hip(self) -> bool:
+        """rev_btlnk has kernels of its own at this latent: the streaming ones (8 / 16) or the MFMA GEMMs (17 .. 512)"""
+        N, L = self.rev_btlnk.out_features, self.latent_dim
+        return ops.rev_btlnk_ok(N, L) or ops.rev_btlnk_wide_ok(N, L)
 
     def _tail_layer(self, t: Tensor):
         """the decoder's last layer where ops.layer_tail takes it: eval mode, nobody asks for a gradient, fp32 on the device, running
@@ -245,7 +251,7 @@ class STSAE(STSE):
         head = self._decode_folded(Z, N, T, V, mods=mods)
         if head is not None:
             return head
-        if ops.rev_btlnk_ok(self.rev_btlnk.out_features, self.latent_dim):
+        if self._rev_on_hip():
             H = ops.rev_btlnk_fwd(Z.contiguous(), self.rev_btlnk.weight.contiguous(), self.rev_btlnk.bias)
         else:
             H = self.rev_btlnk(Z)

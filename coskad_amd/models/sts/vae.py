@@ -33,6 +33,25 @@ class HypersphericalUniform:
         return torch.tensor(math.log(2) + (d / 2) * math.log(math.pi) - math.lgamma(d / 2), device=self.device)
 
 
+class _BetaDraw(torch.autograd.Function):
+    """torch.distributions.Beta(alpha, beta).rsample() for concentration = stack([alpha, beta], -1): the same draw
+    (torch._sample_dirichlet) and torch's _Dirichlet_backward, with torch._dirichlet_grad evaluated in float64
+    (ops.dirichlet_grad: its float32 device kernel loses the gradient at the concentrations of a wide latent)."""
+
+    @staticmethod
+    def forward(ctx, concentration):
+        x = torch._sample_dirichlet(concentration)
+        ctx.save_for_backward(x, concentration)
+        return x
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        x, concentration = ctx.saved_tensors
+        total = concentration.sum(-1, True).expand_as(concentration)
+        grad = ops.dirichlet_grad(x, concentration, total, f64=True)
+        return grad * (grad_output - (x * grad_output).sum(-1, True))
+
+
 class PowerSpherical:
     """p(x; mu, kappa) ∝ (1 + mu^T x)^kappa on S^{d-1}; rsample via t ~ 2 Beta(a,b) - 1 and a Householder
     reflection of e1 onto mu (reparameterised through the Beta sample)."""
@@ -45,7 +64,10 @@ class PowerSpherical:
 
     def rsample(self) -> Tensor:
         d = self.loc.shape[-1]
-        z = torch.distributions.Beta(self.alpha, self.beta).rsample()
+        if d > 16 and self.alpha.requires_grad:      # (a latent within 16 keeps torch's own float32 gradient)
+            z = _BetaDraw.apply(torch.stack([self.alpha, self.beta], -1)).select(-1, 0)
+        else:
+            z = torch.distributions.Beta(self.alpha, self.beta).rsample()
         t = (2 * z - 1).unsqueeze(-1)
         v = F.normalize(torch.randn(*self.loc.shape[:-1], d - 1, device=self.loc.device, dtype=self.loc.dtype), dim=-1)
         y = torch.cat([t, torch.sqrt(torch.clamp(1 - t * t, min=0)) * v], -1)
@@ -113,7 +135,7 @@ class STSVAE(STSAE):
         if heads is not None:
             return heads
         U, slope = self.encoder.forward_preact(X)
-        if isinstance(self.btlnk, nn.Identity) and self.latent_dim + n_var <= 16:
+        if isinstance(self.btlnk, nn.Identity) and self.latent_dim + n_var <= ops.BTLNK_LMAX:   # > 16 rows: csrc/btlnk_wide.hip
             # `linear` projector (vae.py:147-150): both heads read the flattened encoder output -- ONE pass of the
             # bottleneck kernel over U (PReLU fused into the load) with the two weights stacked
             from .ae import _BottleneckFn
@@ -169,8 +191,9 @@ class STSVAE(STSAE):
 
     def sample(self, X: Tensor):
         """-> (Z, input_shape, (q_Z, p_Z, Z_var)): forward up to the sampled latent -- every random draw of a forward, in its order"""
-        if (not self.training and not torch.is_grad_enabled() and X.is_cuda and self.distribution == 'ps' and 2 <= self.latent_dim <= 16):
-            # scoring forward (spherical_vae.py:76-78): normalise, softplus + 1 and the PowerSpherical sample on csrc/vae_head.hip
+        if (not self.training and not torch.is_grad_enabled() and X.is_cuda and self.distribution == 'ps'
+                and 2 <= self.latent_dim <= ops.PS_HEAD_LMAX):
+            # scoring forward (spherical_vae.py:76-78): normalise, softplus + 1 and the PowerSpherical sample on csrc/vae_head.hip / _wide
             # (two launches around torch's Beta draw and Gaussian direction: the module path's noise streams) instead of ~40
             # element-wise launches
             assert len(X.shape) == 4, f'Input tensor must have shape [batch_size, input_dim, n_frames, n_joints]. Got {X.shape}'

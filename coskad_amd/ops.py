@@ -1179,8 +1179,11 @@ def _rows(t: Tensor, name: str, cols: int):
     return t.stride(0)
 
 
+PS_HEAD_LMAX = 512          # widest latent of the PowerSpherical head (csrc/vae_head.hip to 16, csrc/vae_head_wide.hip above)
+
+
 def ps_head_forward(mean_raw: Tensor, var_raw: Tensor, generator=None):
-    """The spherical VAE's latent head on csrc/vae_head.hip (reference models/sts/vae.py:79-91,104-118; PowerSpherical restated in
+    """The spherical VAE's latent head on csrc/vae_head.hip / vae_head_wide.hip (2 <= L <= PS_HEAD_LMAX; reference models/sts/vae.py:79-91,104-118; PowerSpherical restated in
     coskad_amd/models/sts/vae.py): mean_raw [B, L], var_raw [B, 1] (views of one tensor are fine) -> (z [B, L] sampled latent,
     kl [B], inv_kappa [B], saved) with saved = what ps_head_backward needs.  The Beta draw and the Gaussian direction are torch's
     (torch._sample_dirichlet, torch.randn): the noise streams are the module path's."""
@@ -1201,6 +1204,15 @@ def ps_head_forward(mean_raw: Tensor, var_raw: Tensor, generator=None):
     return z, kl, ik, (mean_raw, var_raw, mu, kappa, conc, total, x, eps)
 
 
+def dirichlet_grad(x: Tensor, conc: Tensor, total: Tensor, f64: bool) -> Tensor:
+    """torch._dirichlet_grad, the Beta draw's implicit reparameterisation gradient.  f64 (the callers ask at a latent beyond 16):
+    evaluated in float64.  In float32 on the device (no wider accumulator there, unlike torch's CPU kernel) it is off from the
+    float64 value by 0.5 % at the total concentration of latent 16, 5 % at 17, 12 % at 200 and 62 % at 512."""
+    if not f64:
+        return torch._dirichlet_grad(x, conc, total)
+    return torch._dirichlet_grad(x.double(), conc.double(), total.double()).to(x.dtype)
+
+
 def ps_head_backward(saved, dz: Tensor, w_kl: float, w_exp: float, d_mean_raw: Optional[Tensor] = None,
                      d_var_raw: Optional[Tensor] = None):
     """-> (d_mean_raw [B, L], d_var_raw [B, 1]) for loss = <dz, z> + w_kl * sum kl + w_exp * sum inv_kappa; the destinations may be
@@ -1208,7 +1220,7 @@ def ps_head_backward(saved, dz: Tensor, w_kl: float, w_exp: float, d_mean_raw: O
     mean_raw, var_raw, mu, kappa, conc, total, x, eps = saved
     B, L = mean_raw.shape
     _chk(dz, "dz", (B, L))
-    g = torch._dirichlet_grad(x, conc, total.unsqueeze(-1).expand(B, 2).contiguous())
+    g = dirichlet_grad(x, conc, total.unsqueeze(-1).expand(B, 2).contiguous(), f64=L > 16)
     if d_mean_raw is None:
         d_mean_raw = torch.empty(B, L, device=dz.device, dtype=torch.float32)
     if d_var_raw is None:
@@ -1288,16 +1300,51 @@ def rev_btlnk_ok(N: int, L: int) -> bool:
     return L in (8, 16) and N % 4 == 0
 
 
+def rev_btlnk_wide_ok(N: int, L: int) -> bool:
+    """coskad_rev_btlnk_wide_ok: the latent takes the three MFMA GEMMs of csrc/rev_btlnk_wide.hip (16 < L <= 512, N % 4 == 0)"""
+    return 16 < L <= 512 and N > 0 and N % 4 == 0
+
+
+# latent sizes above 16 that the decoder models' flat step (trainer.STSAETrainStep.supports) leaves on the autograd route because a
+# measurement found the step no faster there (DESIGN 5.19; the idiom of TRAIN_WINDOW_OFF)
+AE_WIDE_OFF = frozenset()
+# latent sizes above 16 at which a product of rev_btlnk keeps the strided-GEMM fallback because the wide kernel did not beat it
+# (DESIGN 5.19): {'fwd' | 'bwd': set of L}; the backward's two products share one entry point and move together
+REV_WIDE_FALLBACK = {'fwd': frozenset(), 'bwd': frozenset()}
+
+
 def rev_btlnk_fwd(z: Tensor, W: Tensor, bias: Optional[Tensor]) -> Tensor:
-    """H = z W^T + bias (rev_btlnk, ae.py:223-227) as one streaming pass (csrc/rev_btlnk.hip); other latent sizes: the strided GEMM."""
+    """H = z W^T + bias (rev_btlnk, ae.py:223-227): one streaming pass (csrc/rev_btlnk.hip) at latent 8 / 16, an MFMA GEMM with the
+    bias in its epilogue (csrc/rev_btlnk_wide.hip) at 17 .. 512; other latent sizes: the strided GEMM."""
     B, L = z.shape
     N = W.shape[0]
     _chk(z, "z"); _chk(W, "W", (N, L)); _chk(bias, "bias", (N,), optional=True)
-    if not rev_btlnk_ok(N, L):
+    wide = rev_btlnk_wide_ok(N, L) and L not in REV_WIDE_FALLBACK['fwd']
+    if not (rev_btlnk_ok(N, L) or wide):
         return gemm(z, W.t(), bias=bias, bias_mode=2 if bias is not None else 0)
     H = torch.empty(B, N, device=z.device, dtype=torch.float32)
     call("coskad_rev_btlnk_fwd_f32", z, W, bias, H, B, N, L, _stream())
     return H
+
+
+def _rev_btlnk_bwd_gemm(dH, z, W, dW, db, dz, accumulate):
+    """the products of rev_btlnk's backward on the strided GEMM (a ones column behind z gives db)"""
+    B, N = dH.shape
+    L = z.shape[1]
+    zs1 = torch.cat([z, torch.ones(B, 1, device=z.device)], 1)
+    gw = torch.empty(N, L + 1, device=dH.device, dtype=torch.float32)
+    gemm_rows_outer(dH, zs1, gw)
+    if accumulate:
+        dW.add_(gw[:, :-1])
+        if db is not None:
+            db.add_(gw[:, -1])
+    else:
+        dW.copy_(gw[:, :-1])
+        if db is not None:
+            db.copy_(gw[:, -1])
+    if dz is None:
+        return gemm(dH, W)
+    return gemm(dH, W, out=dz, accumulate=True)
 
 
 def rev_btlnk_bwd(dH: Tensor, z: Tensor, W: Tensor, dW: Tensor, db: Optional[Tensor], dz: Optional[Tensor] = None,
@@ -1307,21 +1354,9 @@ def rev_btlnk_bwd(dH: Tensor, z: Tensor, W: Tensor, dW: Tensor, db: Optional[Ten
     L = z.shape[1]
     _chk(dH, "dH"); _chk(z, "z", (B, L)); _chk(W, "W", (N, L)); _chk(dW, "dW", (N, L)); _chk(db, "db", (N,), optional=True)
     _chk(dz, "dz", (B, L), optional=True)
-    if not rev_btlnk_ok(N, L) or dH.data_ptr() % 16:
-        zs1 = torch.cat([z, torch.ones(B, 1, device=z.device)], 1)
-        gw = torch.empty(N, L + 1, device=dH.device, dtype=torch.float32)
-        gemm_rows_outer(dH, zs1, gw)
-        if accumulate:
-            dW.add_(gw[:, :-1])
-            if db is not None:
-                db.add_(gw[:, -1])
-        else:
-            dW.copy_(gw[:, :-1])
-            if db is not None:
-                db.copy_(gw[:, -1])
-        if dz is None:
-            return gemm(dH, W)
-        return gemm(dH, W, out=dz, accumulate=True)
+    wide = rev_btlnk_wide_ok(N, L) and L not in REV_WIDE_FALLBACK['bwd']
+    if not wide and (not rev_btlnk_ok(N, L) or dH.data_ptr() % 16):
+        return _rev_btlnk_bwd_gemm(dH, z, W, dW, db, dz, accumulate)
     ws = torch.empty(_lib.lib().coskad_rev_btlnk_ws_floats(B, N, L), device=dH.device, dtype=torch.float32)
     acc_dz = dz is not None
     if dz is None:

@@ -794,7 +794,7 @@ class _CentreLatent(_LatentHead):
 
 
 class _PowerSphericalLatent(_LatentHead):
-    """The PowerSpherical head on csrc/vae_head.hip (normalise, softplus + 1, Householder sample, KL, 1 / kappa: three launches +
+    """The PowerSpherical head on csrc/vae_head.hip / vae_head_wide.hip (normalise, softplus + 1, Householder sample, KL, 1 / kappa: three launches +
     torch's Beta draw instead of ~80 element-wise launches under autograd); the two small Linears of the `mlp` projector's heads ride
     on the strided GEMM with the weights stacked"""
 
@@ -854,8 +854,9 @@ class _AutogradLatent(_LatentHead):
 
 class _PlainEntry:
     """The decoder entry where the decoder's first layer is not folded into it (else: lowrank.LowRankFirstLayer, the same two calls):
-    rev_btlnk (ae.py:223-227), H = z Wr^T + br on the strided MFMA GEMM, straight into the decoder's [B, hid, T, V] view; backward
-    dWr = dH^T z, dbr = sum dH, dz (+)= dH Wr on streaming kernels over dH (csrc/rev_btlnk.hip)"""
+    rev_btlnk (ae.py:223-227), H = z Wr^T + br straight into the decoder's [B, hid, T, V] view; backward dWr = dH^T z, dbr = sum dH,
+    dz (+)= dH Wr into the flat gradient views: streaming kernels over H / dH at latent 8 / 16 (csrc/rev_btlnk.hip), three MFMA GEMMs at
+    17 .. 512 (csrc/rev_btlnk_wide.hip), the strided GEMM at the other small latents"""
 
     def __init__(self, model, gviews) -> None:
         self.rev, self.shape = model.rev_btlnk, (model.hidden_dimension, model.n_frames, model.n_joints)
@@ -896,8 +897,8 @@ class STSAETrainStep(_FlatStep):
         if mode not in ('ae', 'vae') or (mode == 'vae') != isinstance(model, STSVAE):
             raise ValueError(f"mode {mode!r} does not fit {type(model).__name__}")
         if not self.supports(model):
-            raise TypeError("STSAETrainStep: projector / latent size outside the bottleneck kernels (latent rows <= 16, "
-                            "'linear' projector)")
+            raise TypeError("STSAETrainStep: projector / latent size outside the bottleneck, head and decoder-entry kernels ('linear' "
+                            f"projector with head rows <= {ops.BTLNK_LMAX}, or an 'mlp' within MLP.hip_ok; not in ops.AE_WIDE_OFF)")
         # a stack ending `wide` hands over an activated output (no slope, no `last_slope_grad`), which neither the bottleneck kernels
         # nor the reconstruction head take: refused before anything touches the model (its parameters are not re-homed yet)
         for kinds, which in zip(self.segment_kinds(model, fused_window), ("an encoder", "a decoder")):
@@ -927,13 +928,19 @@ class STSAETrainStep(_FlatStep):
 
     @staticmethod
     def supports(model) -> bool:
+        """the stages take the model: latents up to 512 -- above 16 on csrc/btlnk_wide.hip, vae_head_wide.hip and rev_btlnk_wide.hip
+        (the decoder entry is then _PlainEntry), unless a measurement switched that latent off (ops.AE_WIDE_OFF)"""
         from .models.sts.vae import STSVAE
         from .models.common.components import MLP
+        L = model.latent_dim
+        if L > ops.BTLNK_LMAX or (L > 16 and L in ops.AE_WIDE_OFF):
+            return False
+        rows = 16 if L <= 16 else ops.BTLNK_LMAX          # a latent within 16 keeps the narrow kernels' rule
         if isinstance(model, STSVAE):
             if isinstance(model.btlnk, MLP):              # `projector: 'mlp'` (spherical_vae.yaml:37): MLP, then the heads on its output
-                return model.btlnk.hip_ok and model.btlnk.hidden_layers[0] <= 16 and model.latent_dim <= 16
-            return isinstance(model.btlnk, torch.nn.Identity) and model.latent_dim + model.fc_var.out_features <= 16
-        return isinstance(model.btlnk, torch.nn.Linear) and model.latent_dim <= 16
+                return model.btlnk.hip_ok and (L > 16 or model.btlnk.hidden_layers[0] <= 16)
+            return isinstance(model.btlnk, torch.nn.Identity) and L + model.fc_var.out_features <= rows
+        return isinstance(model.btlnk, torch.nn.Linear)
 
     @staticmethod
     def _folds_first(model) -> bool:
@@ -1049,14 +1056,17 @@ def make_train_step(model, flat_plain_gcn: bool = False, fused_window: bool = Fa
     return AutogradTrainStep(model, **kw)
 
 
-def make_decoder_step(model, mode: str, fused_window: bool = True, **kw) -> Optional[STSAETrainStep]:
+def make_decoder_step(model, mode: str, fused_window: bool = True, wide_latent: bool = False, **kw) -> Optional[STSAETrainStep]:
     """STSAETrainStep for an autoencoder / VAE within its kernels, None for what stays on torch autograd + torch.optim.Adam: another
     encoder, a projector / latent outside `supports`, a stack ending in a `wide` segment.  `fused_window` (not a key of the reference's
     yamls): at window length 8 / 16 / 24 the flat step takes the model when the stored-Z layer kernels serve EVERY layer of both stacks
     (no `wide` segment: such a stack -- 8-channel layers, a joint layout without window kernels -- stays on the autograd route, as
-    does every model with `fused_window` off)."""
+    does every model with `fused_window` off).  `wide_latent` (the wrappers ask for it; their yaml key `flat_wide_latent`): a latent
+    beyond 16 that `supports` admits takes the flat step too (csrc/vae_head_wide.hip, rev_btlnk_wide.hip); off: the autograd route."""
     from .models.common.components import Encoder
     if not isinstance(getattr(model, 'encoder', None), Encoder) or not STSAETrainStep.supports(model):
+        return None
+    if model.latent_dim > 16 and not wide_latent:
         return None
     window = (fused_window and ops.window_ok(model.n_frames, model.n_joints)
               and not any('wide' in kinds for kinds in STSAETrainStep.segment_kinds(model, fused_window=True)))

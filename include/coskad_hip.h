@@ -96,11 +96,14 @@ int coskad_rec_head_f32(const float* U, const float* x, const float* slope, floa
                         float upstream, float* ws, int accumulate, size_t n, hipStream_t stream);
 
 /* `rev_btlnk` of the decoder models (models/sts/ae.py:223-227: nn.Linear(latent_dim -> hidden * T * V)) and its autograd as
- * streaming kernels over the one large tensor (csrc/rev_btlnk.hip); latent_dim L in {8, 16}, N % 4 == 0:
+ * streaming kernels over the one large tensor (csrc/rev_btlnk.hip) at latent_dim L in {8, 16}, and as three fp32 MFMA GEMMs
+ * (csrc/rev_btlnk_wide.hip) where coskad_rev_btlnk_wide_ok(N, L) holds: 16 < L <= 512; N % 4 == 0 at either; every other L fails
+ * with COSKAD_ERR_SHAPE.  H 16-byte aligned (and dH at L in {8, 16}).
  *   fwd: H [B, N] = z [B, L] W^T + bias        (W [N, L])
  *   bwd: dz [B, L] (+)= dH W (dz_accumulate);  dW [N, L], db [N] (may be NULL) (+)= their batch sums (accumulate);
  *        ws: coskad_rev_btlnk_ws_floats(B, N, L) floats; two-stage fixed-order reductions (deterministic) */
 size_t coskad_rev_btlnk_ws_floats(int B, int N, int L);
+int coskad_rev_btlnk_wide_ok(int N, int L);
 int coskad_rev_btlnk_fwd_f32(const float* z, const float* W, const float* bias, float* H, int B, int N, int L, hipStream_t stream);
 int coskad_rev_btlnk_bwd_f32(const float* dH, const float* z, const float* W, float* dz, int dz_accumulate, float* dW, float* db,
                              int accumulate, float* ws, int B, int N, int L, hipStream_t stream);
@@ -612,7 +615,8 @@ size_t coskad_commute_below_floats(int B);
 /* The spherical VAE's latent head between the raw outputs of fc_mean / fc_var and the decoder's input (models/sts/vae.py:79-91,
  * 104-118; loss terms of models/spherical_vae.py:86-94; PowerSpherical of the un-vendored `power_spherical` package, restated in
  * coskad_amd/models/sts/vae.py).  Rows are clips; mean_raw [B, L] and var_raw [B] are addressed with row strides ld_* (floats), so both
- * may be columns of ONE [B, L + 1] tensor.  L <= 16.
+ * may be columns of ONE [B, L + 1] tensor.  2 <= L <= 512 (to 16: one thread per clip, csrc/vae_head.hip; above: one wave per clip,
+ * csrc/vae_head_wide.hip); other L fail with COSKAD_ERR_SHAPE.
  *   prep  : mu = mean_raw / |mean_raw|, kappa = softplus(var_raw) + 1, concentration [B, 2] = ((L-1)/2 + kappa, (L-1)/2), total [B]
  *   (the caller draws x ~ Dirichlet(concentration) [B, 2] and eps ~ N(0, I) [B, L-1]; torch._dirichlet_grad gives the sampler's
  *    implicit reparameterisation gradient [B, 2] for the backward)
