@@ -45,13 +45,13 @@ class LayerTensors:
     slope: Tensor           # prelu.weight [1]
     momentum: float = 0.1
     bn: object = None       # the tcn BatchNorm module when its momentum is None (cumulative moving average: the factor changes per step)
-    cache: Optional[dict] = None   # owned by the layer module: eval-mode folded weights, keyed by tensor versions
+    cache: Optional[dict] = None   # owned by the layer module: eval-mode folded weights, keyed by fold_key()
 
     def fold_key(self):
         """Identity + in-place version of everything the eval-mode fold reads (torch optimizers and load_state_dict bump
-        the versions; a training forward clears the cache because this library's kernels write through raw pointers)."""
+        the versions) and the raw-write epoch (this library's kernels write through raw pointers: ops.note_raw_write)."""
         ts = (self.Wt, self.bt, self.gt, self.bet, self.rm_t, self.rv_t, self.Wr, self.br, self.gr, self.ber, self.rm_r, self.rv_r)
-        return tuple((t.data_ptr(), t._version) if t is not None else None for t in ts)
+        return tuple((t.data_ptr(), t._version) if t is not None else None for t in ts) + (ops.raw_write_epoch(),)
 
     def step_momentum(self) -> float:
         """exponential_average_factor of this training forward (both BatchNorms of a layer count their batches in lockstep)"""
@@ -193,9 +193,6 @@ def chain_forward(x: Tensor, layers: List[LayerTensors], training: bool, ws: Wor
             raise ValueError(f"layer expects {L.Ci} input channels, got {h.shape[1]}")
         Z = None
         if batch_stats[i]:
-            if L.cache:
-                L.cache.clear()   # running stats (and, after the optimiser, the weights) change through raw-pointer kernels
-                                  # that do not bump torch's version counters: drop the eval-mode fold
             buf = ws.get(ops.train_stats_ws_bytes(L.Ci), x.device)
             if sync_count is not None:
                 if pending is not None:
@@ -389,12 +386,10 @@ class FusedEncoderPlan:
     weights (coskad_bn_fold_f32), the mixing matrices and the bottleneck weight by ONE gather launch per stream
     (index maps: coskad_amd/fused_plan.py), cached until a parameter changes.
 
-    Validity: torch version counters of every tensor the streams read, plus a token left in each layer's fold cache --
-    training forwards clear those caches (their kernels and the fused Adam write through raw pointers)."""
+    Validity: torch version counters of every tensor the streams read and the raw-write epoch (in the layers' fold keys)."""
 
     def __init__(self) -> None:
         self.key = None
-        self.token = None
         self.tab = self.wreg = self.wb = self.slopes = None
         self._idx = {}
 
@@ -412,13 +407,13 @@ class FusedEncoderPlan:
         Ws = tuple(W) if isinstance(W, (tuple, list)) else (W,)
         key = tuple(L.fold_key() for L in layers) + tuple((t.data_ptr(), t._version) for L in layers for t in (L.A, L.T, L.slope)) \
             + tuple((w.data_ptr(), w._version) for w in Ws) + tuple(ver_extra)
-        if self.key == key and self.token is not None and all(L.cache is not None and L.cache.get("fused") is self.token for L in layers):
+        if self.key == key:
             return self
         from . import fused_plan as FP
         latent = sum(w.shape[0] for w in Ws)
         parts = []
         for L in layers:
-            wfold, bias = ops.bn_fold(L.w2(L.Wt), L.bt, L.gt, L.bet, L.rm_t, L.rv_t, L.w2(L.Wr), L.br, L.gr, L.ber, L.rm_r, L.rv_r)
+            wfold, bias = eval_fold(L)
             parts += [L.A.detach().reshape(-1), L.T.detach().reshape(-1), wfold.reshape(-1), bias.reshape(-1)]
         parts += [w.detach().reshape(-1) for w in Ws]
         src = torch.cat(parts)
@@ -427,10 +422,7 @@ class FusedEncoderPlan:
         self.tab, self.wreg = ops.gather(src, ti), ops.gather(src, wi)
         self.wb = ops.gather(src, bi).view(latent, FP.KP)
         self.slopes = torch.cat([L.slope.detach().reshape(1) for L in layers]).contiguous()
-        self.key, self.token = key, object()
-        for L in layers:
-            if L.cache is not None:
-                L.cache["fused"] = self.token
+        self.key = key
         return self
 
 

@@ -246,8 +246,6 @@ class LowRankFirstLayer:
         """z [B, Lz] (no autograd) -> U1 [B, C_out, T, V]: the first decoder layer's PRE-activation (apply its PReLU on load)"""
         lay = self.layer
         B, Lz = z.shape
-        lay.__dict__.pop("_lowrank_eval", None)               # eval-mode folds of this layer go stale with this step
-        lay.__dict__.get("_fold_cache", {}).clear()
         zt = torch.cat([z, torch.ones(B, 1, device=z.device, dtype=z.dtype)], 1)
         # G = sum_n zt zt^T: 256-row pieces on the fp32 MFMA GEMM, pieces summed in fp64 in a fixed order (ONE [K, B] x [B, K] fp64
         # library product is a single-workgroup kernel: 224 us at B = 4096)
@@ -258,6 +256,7 @@ class LowRankFirstLayer:
             with torch.no_grad():
                 fg.G.copy_(G32)
             fg.fwd.replay()
+            ops.note_raw_write()                              # the replay updates the running statistics without ops.lowrank_fold_fwd
             G, Mw, Mb = fg.G, fg.Mw, fg.Mb
         elif EXPLICIT and not isinstance(lay.residual, nn.Identity):
             G = G32.double()

@@ -308,15 +308,6 @@ class ST_GCNN_layer(nn.Module):
             self.residual = nn.Identity()
         self.prelu = nn.PReLU()
 
-    def train(self, mode: bool = True):
-        if mode:
-            # eval-mode folds (the BatchNorm-folded weights of engine.chain_forward, the folded images of models/sts/ae.py): training is
-            # about to change what they fold, through raw-pointer kernels that move no torch version counter -- and not every training
-            # path runs through this layer's own LayerTensors (trainer._FlatStack `narrow` segments, coskad_amd/lowrank.py)
-            self.__dict__.pop("_lowrank_eval", None)
-            self.__dict__.get("_fold_cache", {}).clear()
-        return super().train(mode)
-
     @property
     def is_wide(self) -> bool:
         """Beyond the LDS-resident tile kernels: more than 64 channels on either side, a window length other than 12, or a clip whose

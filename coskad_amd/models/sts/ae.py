@@ -294,14 +294,12 @@ class STSAE(STSE):
         if (self.training or torch.is_grad_enabled() or not Z.is_cuda or Z.dtype != torch.float32 or len(mods) < 2
                 or not lowrank.eval_supported(self.rev_btlnk, mods[0])):
             return None
-        # the folded images depend on parameters and running statistics only: kept until one of them changes (torch-side writes
-        # move the version counters; this library's training kernels write through raw pointers, but training needs .train() first,
-        # which drops the cache: ST_GCNN_layer.train)
+        # the folded images depend on parameters and running statistics only: kept until one of them changes
         l0, rev = mods[0], self.rev_btlnk
         ts = [rev.weight, rev.bias, l0.gcn.A, l0.gcn.T] + [t for seq in (l0.tcn, l0.residual) if not isinstance(seq, nn.Identity)
                                                           for t in (seq[0].weight, seq[0].bias, seq[1].weight, seq[1].bias,
                                                                     seq[1].running_mean, seq[1].running_var) if t is not None]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (ops.raw_write_epoch(),)
         cached = l0.__dict__.get("_lowrank_eval")
         if cached is None or cached[0] != key:
             cached = (key, lowrank.fold_eval(rev, l0))

@@ -38,6 +38,20 @@ def _chk(t: Optional[Tensor], name: str, shape=None, dtype=torch.float32, option
         raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
 
 
+# A wrapper that hands the library a pointer to module state the kernel will write (a parameter, a BatchNorm running buffer or
+# num_batches_tracked) calls note_raw_write(); any cache of tensors derived from module state puts raw_write_epoch() in its key.
+_raw_write_epoch = 0
+
+
+def note_raw_write() -> None:
+    global _raw_write_epoch
+    _raw_write_epoch += 1
+
+
+def raw_write_epoch() -> int:
+    return _raw_write_epoch
+
+
 def _bytes(t: Tensor) -> int:
     return t.numel() * t.element_size()
 
@@ -227,6 +241,7 @@ def layer_train_stats(x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t,
     _chk(Z, "Z", tuple(x.shape), optional=True)
     args = (x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r, nbt_r, momentum, wfold, bias, stat, ws,
             ws.numel() * ws.element_size(), B, Ci, Co, T, V, _stream())
+    note_raw_write()
     if Z is None:
         call("coskad_layer_train_stats_f32", *args)
     else:
@@ -269,6 +284,7 @@ def layer_train_fold_sums(sums, count, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, b
     wfold = torch.empty(2 * Ci, cop(Co), device=Wt.device, dtype=torch.float32)
     bias = torch.empty(cop(Co), device=Wt.device, dtype=torch.float32)
     stat = torch.empty(stat_floats(Ci, Co), device=Wt.device, dtype=torch.float32)
+    note_raw_write()
     call("coskad_layer_train_fold_sums_f32", sums, float(count), Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r, nbt_r,
          momentum, wfold, bias, stat, Ci, Co, _stream())
     return wfold, bias, stat
@@ -395,6 +411,7 @@ def layer_train_fold(partials, rows, B, T, V, Wt, bt, gt, bet, rm_t, rv_t, nbt_t
     wfold = torch.empty(2 * Ci, cop(Co), device=Wt.device, dtype=torch.float32)
     bias = torch.empty(cop(Co), device=Wt.device, dtype=torch.float32)
     stat = torch.empty(stat_floats(Ci, Co), device=Wt.device, dtype=torch.float32)
+    note_raw_write()
     call("coskad_layer_train_fold_f32", partials, rows, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r, nbt_r, momentum,
          wfold, bias, stat, ws, _bytes(ws), B, Ci, Co, T, V, _stream())
     return wfold, bias, stat
@@ -765,6 +782,7 @@ def bn2_stats_parts(parts: Tensor, bn, count: int) -> Tensor:
     rows, C, _ = parts.shape
     _chk(parts, "parts", (rows, C, 2), dtype=torch.float64)
     stat = torch.empty(2 * C, device=parts.device, dtype=torch.float32)
+    note_raw_write()
     call("coskad_bn2_stats_parts_f32", parts, rows, stat, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn_momentum(bn), bn.eps,
          float(count), C, _stream())
     return stat
@@ -857,6 +875,8 @@ def bn2_stats(x: Tensor, bn, training: bool) -> Tensor:
     _chk(x, "x")
     stat = torch.empty(2 * C, device=x.device, dtype=torch.float32)
     ws = _bn2_ws(Nb, C, x.device)
+    if training:
+        note_raw_write()
     call("coskad_bn2_stats_f32", x, stat, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn_momentum(bn) if training else 0.0,
          bn.eps, 1 if training else 0, ws, ws.numel(), Nb, C, P, _stream())
     return stat
@@ -914,6 +934,8 @@ def mlp_head_fwd(y1, gamma, beta, running_mean, running_var, nbt, W2, b2, traini
     _chk(nbt, "num_batches_tracked", (), dtype=torch.int64, optional=True)
     z = torch.empty(B, L, device=y1.device, dtype=torch.float32)
     stat = torch.empty(mlp_head_ws_floats(B, H, L), device=y1.device, dtype=torch.float32)
+    if training:
+        note_raw_write()
     call("coskad_mlp_head_fwd_f32", y1, gamma, beta, running_mean, running_var, nbt, momentum, eps, 1 if training else 0, W2, b2, z, stat,
          B, H, L, _stream())
     return z, stat
@@ -1032,6 +1054,7 @@ def lowrank_fold_fwd(X: Tensor, G: Tensor, bn_t, bn_r, bias_t, bias_r, n_pos: fl
     args = []
     for bn, cb in ((bn_t, bias_t), (bn_r, bias_r)):
         args += [bn.weight, bn.bias, cb, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn_momentum(bn), bn.eps]
+    note_raw_write()
     call("coskad_lowrank_fold_fwd_f32", X, G, *args, n_pos, Mw, Mb, saved, xbar, xx, Co, TV, _stream())
     return Mw, Mb, (saved, xbar, xx)
 
@@ -1131,6 +1154,7 @@ def commute_fwd(U_prev: Tensor, in_slope: Optional[Tensor], Wt: Tensor, Wr: Tens
         _chk(An, "A_next", (T, V, V)); _chk(Tn, "T_next", (V, T, T)); _chk(slope_out, "slope_out", (1,))
         Zn = torch.empty(B, 16, T, V, device=dev, dtype=torch.float32)
         pn = torch.empty(768 * 2 * (16 * 16 + 16), device=dev, dtype=torch.float32)
+    note_raw_write()
     call("coskad_commute_fwd_f32", U_prev, in_slope, Wt, Wr, A, Tm, gamma_t, beta_t, gamma_r, beta_r, bias_t, bias_r, rm_t, rv_t, rm_r,
          rv_r, nbt_t, nbt_r, momentum, eps, YR, Zy, U, stat, ws, ws.numel(), An, Tn, slope_out if next_layer is not None else None, Zn, pn,
          ctypes.byref(rows), B, T, V, _stream())
@@ -1257,6 +1281,7 @@ def adam(p, g, m, v, mask, lr, beta1, beta2, eps, step, gscale=1.0, reg_coef=0.0
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _chk(t, n, p.shape)
     _chk(mask, "mask", p.shape, optional=True)
+    note_raw_write()
     call("coskad_adam_f32", p, g, m, v, mask, p.numel(), lr, beta1, beta2, eps, step, gscale, reg_coef, _stream())
 
 
@@ -1265,6 +1290,7 @@ def adam_pow(p, g, m, v, mask, lr, beta1, beta2, eps, b1pow, b2pow, gscale=1.0, 
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _chk(t, n, p.shape)
     _chk(mask, "mask", p.shape, optional=True)
+    note_raw_write()
     call("coskad_adam_pow_f32", p, g, m, v, mask, p.numel(), lr, beta1, beta2, eps, b1pow, b2pow, gscale, reg_coef, _stream())
 
 
@@ -1399,6 +1425,7 @@ def adam_dev(p, g, m, v, mask, hyper, beta1, beta2, eps, gscale=1.0, reg_coef=0.
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _chk(t, n, p.shape)
     _chk(mask, "mask", p.shape, optional=True); _chk(hyper, "hyper", (4,))
+    note_raw_write()
     call("coskad_adam_dev_f32", p, g, m, v, mask, p.numel(), hyper, beta1, beta2, eps, gscale, reg_coef, _stream())
 
 

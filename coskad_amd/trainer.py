@@ -238,7 +238,6 @@ class _CommuteLayer(_Segment):
         """-> (h, slope, saved, pending)"""
         mod = self.mod
         tc, tb, rc, rb = mod.tcn[0], mod.tcn[1], mod.residual[0], mod.residual[1]
-        mod.__dict__.get("_fold_cache", {}).clear()                    # (the layer's eval-mode fold goes stale with this step)
         u, sv, pend = ops.commute_fwd(h, slope, tc.weight, rc.weight, mod.gcn.A, mod.gcn.T, tb.weight, tb.bias, rb.weight, rb.bias,
                                       tc.bias, rc.bias, tb.running_mean, tb.running_var, rb.running_mean, rb.running_var,
                                       tb.num_batches_tracked, rb.num_batches_tracked, tb.momentum, tb.eps,
@@ -273,7 +272,6 @@ class _NarrowLayer(_Segment):
         mod = self.mod
         Co, Ci = mod.out_channels, mod.in_channels
         W4 = torch.cat([mod.tcn[0].weight.view(Co, Ci), mod.residual[0].weight.view(Co, Ci)], 0)
-        mod.__dict__.get("_fold_cache", {}).clear()                    # (the real layer's eval-mode fold goes stale with this step)
         YR = ops.narrow_conv_fwd(h, slope, W4)                         # [Wt X; Wr X] with X = PReLU(h)
         u, ctx = engine.chain_forward(YR, [self.virt], True, ws, want_ctx=True)
         return u, self.virt.slope, (ctx, h, slope, W4)
@@ -768,6 +766,7 @@ class STSETrainStep(_FlatStep, _OneClassHead):
                 self._stats_static = self._body(self._x_static)
         self._x_static.copy_(x)
         self._graph.replay()
+        ops.note_raw_write()                    # the replay runs the captured writers without their wrappers
         return self._stats_static
 
 
