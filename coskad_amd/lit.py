@@ -280,12 +280,18 @@ class _AutogradLit(LitEncoder):
         from .trainer import make_decoder_step
         self._flat = None
         # `flat_wide_latent` (not a key of the reference's yamls; default on): false keeps a model with latent_dim > 16 on the autograd route
+        # `flat_gaussian_head` (likewise): false keeps the `distribution: 'normal'` head of the flat step under its local autograd graph
         if next(self.model.parameters()).is_cuda:
             self._flat = make_decoder_step(self.model, mode, fused_window=bool(getattr(self.args, "fused_window", True)),
                                            wide_latent=bool(getattr(self.args, "flat_wide_latent", True)),
+                                           gaussian_head=bool(getattr(self.args, "flat_gaussian_head", True)),
                                            lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)), **weights)
         if self._flat is None:
             self._opt = torch.optim.Adam(self.model.parameters(), lr=self.learning_rate)
+        if parallel.rank() == 0:           # one line of the training log: which step and which stage forms drive this model
+            print("train step: " + ("torch autograd + torch.optim.Adam" if self._flat is None else
+                                    f"{type(self._flat).__name__} (projector {type(self._flat.projector).__name__}, "
+                                    f"latent {type(self._flat.latent).__name__}, entry {type(self._flat.entry).__name__})"), flush=True)
 
     def _reg_loss(self) -> torch.Tensor:
         """utils/model_utils.py:90-105 (differentiable: it is part of these wrappers' loss)."""
@@ -462,6 +468,9 @@ class LitVAE(_AutogradLit):
     training_epoch_end = on_train_epoch_end
 
     def window_scores_from_batch(self, x: torch.Tensor) -> torch.Tensor:
+        scores = self.model.cosine_scores(x, self.model.mean_vector)     # the Gaussian head's scoring form (one launch), or None
+        if scores is not None:
+            return scores
         z = self.model.sample(x)[0]            # forward's latent (its draws, in its order) without the decoder behind it
         return 1 - F.cosine_similarity(self.model.mean_vector.expand_as(z), z)
 

@@ -203,9 +203,32 @@ class STSVAE(STSAE):
             Z_var = saved[3].unsqueeze(-1)
             q_Z, p_Z = self.reparameterize(saved[2], Z_var)
             return Z, input_shape, (q_Z, p_Z, Z_var)
+        if self._normal_head_on_hip(X):
+            # the Gaussian head's scoring forward: softplus + 1 and the sample in ONE launch of csrc/vae_head_normal.hip on the noise
+            # Normal.rsample would draw; the distributions are built from the kernel's sigma for the callers that read them
+            assert len(X.shape) == 4, f'Input tensor must have shape [batch_size, input_dim, n_frames, n_joints]. Got {X.shape}'
+            input_shape = (X.shape[0], self.hidden_dimension, self.n_frames, self.n_joints, 1)
+            m_raw, v_raw = self._raw_heads(X)
+            Z, _, _, saved = ops.normal_head_forward(m_raw, v_raw)
+            Z_var = saved[3]
+            q_Z, p_Z = self.reparameterize(m_raw, Z_var)
+            return Z, input_shape, (q_Z, p_Z, Z_var)
         Z_mean, Z_var, input_shape = self.encode(X, return_shape=True)
         q_Z, p_Z = self.reparameterize(Z_mean, Z_var)
         return q_Z.rsample(), input_shape, (q_Z, p_Z, Z_var)
+
+    def _normal_head_on_hip(self, X: Tensor) -> bool:
+        return (not self.training and not torch.is_grad_enabled() and X.is_cuda and self.distribution == 'normal'
+                and 1 <= self.latent_dim <= ops.NORMAL_HEAD_LMAX)
+
+    def cosine_scores(self, X: Tensor, ref: Tensor):
+        """1 - cos(ref, z) of the sampled latent per window (spherical_vae.py:76-78,200) from the Gaussian head's scoring form: one
+        launch behind the raw heads, z itself is not written.  The noise is sample()'s draw.  None where that form does not apply
+        (another distribution, training mode, gradients enabled, a CPU tensor): the caller keeps its torch expression."""
+        if not self._normal_head_on_hip(X):
+            return None
+        m_raw, v_raw = self._raw_heads(X)
+        return ops.normal_head_forward(m_raw, v_raw, ref=ref, need_saved=False)[0]
 
     def _latent(self, X: Tensor):
         Z, input_shape, _ = self.sample(X)

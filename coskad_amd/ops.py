@@ -1255,6 +1255,71 @@ def ps_head_backward(saved, dz: Tensor, w_kl: float, w_exp: float, d_mean_raw: O
     return d_mean_raw, d_var_raw
 
 
+NORMAL_HEAD_LMAX = 512      # widest latent of the Gaussian head (csrc/vae_head_normal.hip)
+# (projector, latent) ranges that a measurement found no faster on the Gaussian head's kernels than under the local autograd graph
+# stay on trainer._AutogradLatent (the idiom of AE_WIDE_OFF): entries (projector, first latent, last latent).  None
+NORMAL_HEAD_OFF = frozenset()
+
+
+def normal_head_ok(L: int) -> bool:
+    """Host arithmetic of `coskad_normal_head_ok`: the Gaussian head's kernels take the latent (1 .. NORMAL_HEAD_LMAX).  Restated here
+    so that building a train step needs no native library; tests/test_gaussian_head_host.py holds the two in agreement."""
+    return 1 <= L <= NORMAL_HEAD_LMAX
+
+
+def normal_head_forward(mean_raw: Tensor, var_raw: Tensor, generator=None, ref: Optional[Tensor] = None, need_saved: bool = True,
+                        eps: Optional[Tensor] = None):
+    """The Gaussian VAE's latent head in one launch of csrc/vae_head_normal.hip (1 <= L <= NORMAL_HEAD_LMAX; reference
+    models/sts/vae.py:85,106-108,129, loss terms of models/spherical_vae.py:89-90,98): mean_raw [B, L], var_raw [B, L] (column blocks of
+    one tensor are fine) -> (z [B, L] = mean_raw + sigma eps, kl [B] = KL(Normal(mean_raw, sigma) || Normal(0, 1)) summed over the
+    latent, inv [B] = sum_l 1 / sigma, saved) with sigma = softplus(var_raw) + 1 and saved = (mean_raw, var_raw, eps, sigma, z), what
+    normal_head_backward needs (None without `need_saved`: sigma is then not written).
+    ref [L] or [1, L]: the scoring form -> (score [B] = 1 - F.cosine_similarity(ref, z), kl, inv, saved); without `need_saved` only
+    the score is formed (z, sigma, kl and inv are not written: None).
+    eps: the noise [B, L]; None: drawn as Normal.rsample draws it (torch.distributions.utils._standard_normal: ONE
+    torch.empty(shape).normal_() of shape [B, L] on the input's device), so the module path's noise stream is kept."""
+    B, L = mean_raw.shape
+    ldm, ldv = _rows(mean_raw, "mean_raw", L), _rows(var_raw, "var_raw", L)
+    if var_raw.shape[0] != B:
+        raise ValueError(f"var_raw: expected {B} rows, got {var_raw.shape[0]}")
+    dev = mean_raw.device
+    if eps is None:
+        eps = torch.empty(B, L, device=dev, dtype=torch.float32).normal_(generator=generator)
+    _chk(eps, "eps", (B, L))
+    scoring = ref is not None
+    if scoring:
+        ref = ref.reshape(-1)
+        _chk(ref, "ref", (L,))
+    new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+    full = need_saved or not scoring
+    z = new(B, L) if full else None
+    sigma = new(B, L) if need_saved else None
+    kl, inv = (new(B), new(B)) if full else (None, None)
+    score = new(B) if scoring else None
+    call("coskad_normal_head_fwd_f32", mean_raw, ldm, var_raw, ldv, eps, z, sigma, kl, inv, ref, score, B, L, _stream())
+    saved = (mean_raw, var_raw, eps, sigma, z) if need_saved else None
+    return (score if scoring else z), kl, inv, saved
+
+
+def normal_head_backward(saved, dz: Tensor, w_kl: float, w_exp: float, d_mean_raw: Optional[Tensor] = None,
+                         d_var_raw: Optional[Tensor] = None):
+    """-> (d_mean_raw [B, L], d_var_raw [B, L]) for loss = <dz, z> + w_kl * sum kl + w_exp * sum inv, in one launch; the destinations
+    may be the column blocks of one [B, 2L] tensor."""
+    mean_raw, var_raw, eps, sigma, _ = saved
+    B, L = mean_raw.shape
+    _chk(dz, "dz", (B, L))
+    if d_mean_raw is None:
+        d_mean_raw = torch.empty(B, L, device=dz.device, dtype=torch.float32)
+    if d_var_raw is None:
+        d_var_raw = torch.empty(B, L, device=dz.device, dtype=torch.float32)
+    for t, name in ((d_mean_raw, "d_mean_raw"), (d_var_raw, "d_var_raw")):
+        if t.shape[0] != B:
+            raise ValueError(f"{name}: expected {B} rows, got {t.shape[0]}")
+    call("coskad_normal_head_bwd_f32", dz, eps, sigma, mean_raw, _rows(mean_raw, "mean_raw", L), var_raw, _rows(var_raw, "var_raw", L),
+         w_kl, w_exp, d_mean_raw, _rows(d_mean_raw, "d_mean_raw", L), d_var_raw, _rows(d_var_raw, "d_var_raw", L), B, L, _stream())
+    return d_mean_raw, d_var_raw
+
+
 def center_finalize(acc, eps: float, L: int):
     _chk(acc, "acc", (head_slots(L),))
     c = torch.empty(L, device=acc.device, dtype=torch.float32)

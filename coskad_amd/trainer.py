@@ -819,8 +819,43 @@ class _PowerSphericalLatent(_LatentHead):
         return ops.gemm(dH2, Wc)
 
 
+class _GaussianLatent(_LatentHead):
+    """The Gaussian head (`distribution: 'normal'`) on csrc/vae_head_normal.hip: softplus + 1, the reparameterised sample, KL to the
+    standard normal and 1 / sigma in one launch on torch's normal draw, their backward in another -- instead of the element-wise
+    launches of _AutogradLatent and its autograd graph; the two small Linears of the `mlp` projector's heads ride on the strided GEMM
+    with the weights stacked ([2L, L]), as in _PowerSphericalLatent"""
+
+    def __init__(self, step: "STSAETrainStep", heads: bool = False) -> None:
+        super().__init__(step, heads)
+        names = ("fc_mean.weight", "fc_mean.bias", "fc_var.weight", "fc_var.bias") if heads else ()
+        self.head_params, self.head_grads = [step.model.get_parameter(n) for n in names], [self.gv[n] for n in names]
+
+    def forward(self, y: Tensor):
+        m, L = self.model, self.model.latent_dim
+        Wc, H2 = None, y
+        if self.heads:
+            Wc, bc = _stacked_heads(m)                                        # [2L, L]
+            H2 = ops.gemm(y, Wc.t(), bias=bc, bias_mode=2)
+        zs, kl_rows, inv_rows, saved = ops.normal_head_forward(H2[:, :L], H2[:, L:])
+        losses = {'head': kl_rows.mean().reshape(1), 'exp': (inv_rows.sum() / (y.shape[0] * L)).reshape(1)}
+        return zs, None, losses, (y, H2, Wc, saved)
+
+    def backward(self, saved, dz: Tensor) -> Tensor:
+        y, H2, Wc, head_saved = saved
+        L, B = self.model.latent_dim, dz.shape[0]
+        dH2 = torch.empty_like(H2)
+        ops.normal_head_backward(head_saved, dz, self.beta / B, self.gamma / (B * L), dH2[:, :L], dH2[:, L:])
+        if Wc is None:
+            return dH2
+        # the two heads' Linears (weights stacked): dWc = dH2^T y, db = column sums, dy = dH2 Wc
+        dWc = ops.gemm_rows_outer(dH2, y.contiguous(), torch.empty(2 * L, L, device=dH2.device, dtype=torch.float32))
+        _unstack_head_grads(self.gv, L, dWc, dH2.sum(0))
+        return ops.gemm(dH2, Wc)
+
+
 class _AutogradLatent(_LatentHead):
-    """every other distribution of the VAE: torch ops on [B, latent] tensors under a local autograd graph (vae.py:79-91,104-118)"""
+    """every other distribution of the VAE, and the Gaussian head without `gaussian_head` (the yardstick _GaussianLatent is held
+    against): torch ops on [B, latent] tensors under a local autograd graph (vae.py:79-91,104-118)"""
 
     def __init__(self, step: "STSAETrainStep", heads: bool = False) -> None:
         super().__init__(step, heads)
@@ -878,16 +913,18 @@ class STSAETrainStep(_FlatStep):
       mode 'vae' (models/spherical_vae.py:81-107):          phi * MSE(x_rec, x) + alpha * reg + beta * KL(q || p) + gamma * mean(1 / kappa)
 
     encoder stack -> `projector` (the bottleneck, one kernel pass; the VAE's mean | concentration heads stacked) -> `latent` (MSE to
-    the centre | the PowerSpherical head | another distribution under a local autograd graph) -> `entry` (rev_btlnk, with the first
-    decoder layer folded in where lowrank.py takes it) -> decoder stack -> reconstruction head -> the same stages backwards.  The
+    the centre | the PowerSpherical head | the Gaussian head | another distribution under a local autograd graph) -> `entry` (rev_btlnk,
+    with the first decoder layer folded in where lowrank.py takes it) -> decoder stack -> reconstruction head -> the same stages backwards.  The
     constructor picks every stage's form and refuses what they do not take; gradients land in the flat buffer; data-parallel
     all-reduce and Adam as in STSETrainStep."""
 
     def __init__(self, model, mode: str = 'ae', lr: float = 1e-4, alpha: float = 0.0, lambda_: float = 0.01, phi: float = 1.0,
                  beta: float = 1.0, gamma: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None,
-                 fused_window: bool = False) -> None:
+                 fused_window: bool = False, gaussian_head: bool = False) -> None:
         """fused_window: layers of window length 8 / 16 / 24 train on the stored-Z layer kernels where those are built (`window` runs
-        of both stacks, the last decoder layer as a `narrow` segment; off: the composed path, as before).  Eager, main stream."""
+        of both stacks, the last decoder layer as a `narrow` segment; off: the composed path, as before).  Eager, main stream.
+        gaussian_head: a `distribution: 'normal'` VAE runs its latent head on csrc/vae_head_normal.hip (_GaussianLatent) where
+        `gaussian_head_ok` admits it; off: under the local autograd graph (_AutogradLatent), as before."""
         from .models.sts.ae import STSAE
         from .models.sts.vae import STSVAE
         from .models.common.components import Encoder
@@ -922,6 +959,8 @@ class STSAETrainStep(_FlatStep):
         self.dec = _FlatStack(dec_layers[first:], self.fp, "decoder.model.", first=first, window=fused_window)
         self.center_acc = torch.zeros(ops.head_slots(model.latent_dim), device=self.fp.flat.device, dtype=torch.float32)
         latent = _CentreLatent if mode == 'ae' else _PowerSphericalLatent if model.distribution == 'ps' else _AutogradLatent
+        if gaussian_head and mode == 'vae' and self.gaussian_head_ok(model):
+            latent = _GaussianLatent
         self.latent = latent(self, heads=isinstance(self.projector, _MLPProjector))
         self.last = {}
 
@@ -940,6 +979,15 @@ class STSAETrainStep(_FlatStep):
                 return model.btlnk.hip_ok and (L > 16 or model.btlnk.hidden_layers[0] <= 16)
             return isinstance(model.btlnk, torch.nn.Identity) and L + model.fc_var.out_features <= rows
         return isinstance(model.btlnk, torch.nn.Linear)
+
+    @staticmethod
+    def gaussian_head_ok(model) -> bool:
+        """a `distribution: 'normal'` VAE whose latent the Gaussian head's kernels take, unless a measurement switched its
+        (projector, latent) off (ops.NORMAL_HEAD_OFF)"""
+        from .models.common.components import MLP
+        L, proj = model.latent_dim, 'mlp' if isinstance(model.btlnk, MLP) else 'linear'
+        return (getattr(model, 'distribution', None) == 'normal' and ops.normal_head_ok(L)
+                and not any(p == proj and lo <= L <= hi for p, lo, hi in ops.NORMAL_HEAD_OFF))
 
     @staticmethod
     def _folds_first(model) -> bool:
@@ -1055,13 +1103,16 @@ def make_train_step(model, flat_plain_gcn: bool = False, fused_window: bool = Fa
     return AutogradTrainStep(model, **kw)
 
 
-def make_decoder_step(model, mode: str, fused_window: bool = True, wide_latent: bool = False, **kw) -> Optional[STSAETrainStep]:
+def make_decoder_step(model, mode: str, fused_window: bool = True, wide_latent: bool = False, gaussian_head: bool = False,
+                      **kw) -> Optional[STSAETrainStep]:
     """STSAETrainStep for an autoencoder / VAE within its kernels, None for what stays on torch autograd + torch.optim.Adam: another
     encoder, a projector / latent outside `supports`, a stack ending in a `wide` segment.  `fused_window` (not a key of the reference's
     yamls): at window length 8 / 16 / 24 the flat step takes the model when the stored-Z layer kernels serve EVERY layer of both stacks
     (no `wide` segment: such a stack -- 8-channel layers, a joint layout without window kernels -- stays on the autograd route, as
     does every model with `fused_window` off).  `wide_latent` (the wrappers ask for it; their yaml key `flat_wide_latent`): a latent
-    beyond 16 that `supports` admits takes the flat step too (csrc/vae_head_wide.hip, rev_btlnk_wide.hip); off: the autograd route."""
+    beyond 16 that `supports` admits takes the flat step too (csrc/vae_head_wide.hip, rev_btlnk_wide.hip); off: the autograd route.
+    `gaussian_head` (the wrappers ask for it; their yaml key `flat_gaussian_head`): the step of a `distribution: 'normal'` VAE runs its
+    latent head on csrc/vae_head_normal.hip; off: that head stays under its local autograd graph."""
     from .models.common.components import Encoder
     if not isinstance(getattr(model, 'encoder', None), Encoder) or not STSAETrainStep.supports(model):
         return None
@@ -1071,4 +1122,4 @@ def make_decoder_step(model, mode: str, fused_window: bool = True, wide_latent: 
               and not any('wide' in kinds for kinds in STSAETrainStep.segment_kinds(model, fused_window=True)))
     if any(kinds[-1] == 'wide' for kinds in STSAETrainStep.segment_kinds(model, fused_window=window)):
         return None
-    return STSAETrainStep(model, mode=mode, fused_window=window, **kw)
+    return STSAETrainStep(model, mode=mode, fused_window=window, gaussian_head=gaussian_head, **kw)

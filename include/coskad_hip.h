@@ -632,6 +632,25 @@ int coskad_ps_head_bwd_f32(const float* dz, const float* x, const float* dirichl
                            float w_exp, float* d_mean_raw, int ld_dmean, float* d_var_raw, int ld_dvar, int B, int L,
                            hipStream_t stream);
 
+/* The Gaussian VAE's latent head (`distribution: 'normal'`: models/sts/vae.py:85,106-108,129; loss terms of
+ * models/spherical_vae.py:89-90,98), csrc/vae_head_normal.hip.  Rows are clips; mean_raw [B, L] and var_raw [B, L] are addressed with
+ * row strides ld_* (floats), so both may be column blocks of ONE [B, 2L] tensor, and so are the gradient destinations; eps, z, sigma
+ * and dz are contiguous [B, L].  1 <= L <= 512 (coskad_normal_head_ok); other L fail with COSKAD_ERR_SHAPE, as does B = 0; B < 0, a
+ * stride below L, score without ref, and neither z nor score fail with COSKAD_ERR_ARG.
+ *   fwd: sigma = softplus(var_raw) + 1;  z = mean_raw + sigma eps (eps: the caller's N(0, 1) draw);
+ *        kl [B] = sum_l 0.5 (sigma^2 + mu^2 - 1 - log sigma^2);  inv [B] = sum_l 1 / sigma;  sigma, kl, inv may be NULL.
+ *        ref [L] with score [B]: score[n] = 1 - F.cosine_similarity(ref, z[n]) (each norm clamped at 1e-8); z may then be NULL.
+ *   bwd: d_mean_raw = dz + w_kl mu;  d_var_raw = (dz eps + w_kl (sigma - 1 / sigma) - w_exp / sigma^2) softplus'(var_raw), with
+ *        w_kl = d loss / d kl[n] and w_exp = d loss / d (1 / sigma) per element.
+ * Every sum is formed in an order that depends on L alone: a clip's results do not depend on the batch. */
+int coskad_normal_head_ok(int L);
+int coskad_normal_head_fwd_f32(const float* mean_raw, int ld_mean, const float* var_raw, int ld_var, const float* eps, float* z,
+                               float* sigma, float* kl, float* inv, const float* ref, float* score, int B, int L,
+                               hipStream_t stream);
+int coskad_normal_head_bwd_f32(const float* dz, const float* eps, const float* sigma, const float* mean_raw, int ld_mean,
+                               const float* var_raw, int ld_var, float w_kl, float w_exp, float* d_mean_raw, int ld_dmean,
+                               float* d_var_raw, int ld_dvar, int B, int L, hipStream_t stream);
+
 /* c = acc[1..L] / acc[17], then |c| < eps -> +-eps (staticCenter.py:118-121). */
 int coskad_center_finalize_f32(const float* acc, float* c, float eps, int L, hipStream_t stream);
 /* gyromidpoint from acc of coskad_poincare_head_f32 (hyperbolic_encoder.py:122,179). */
