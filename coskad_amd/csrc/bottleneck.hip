@@ -12,6 +12,7 @@
 //             as the mask of dU = (dz W) * PReLU'(U), and U itself for the slope gradient.
 #include "tile_ops.h"
 #include "layer_launch.h"
+#include "heads_common.h"
 
 namespace coskad {
 
@@ -256,15 +257,21 @@ __global__ __launch_bounds__(kBtlBlock) void k_btlnk_bwd(const float* __restrict
 //   block  nE + L        : dslope (+)= sum of the nda block partials   (dslope may be NULL)
 //   blocks beyond        : rsum[e] = sum_p rows[p][e] in fp64, 16 columns x 16 row slices per block (the top layer's backward chain
 //                          buffer of btlnk_chain.hip: its partial rows are summed in this launch instead of one of their own)
+//   block  fin.block     : the one-class head's statistics from its blocks' partial rows (k_head_finalize's sums, when the head's
+//                          rows rode in the backward's launch: btlnk_chain.hip); the last block of the grid
 __global__ __launch_bounds__(256) void k_btlnk_reduce(const float* __restrict__ partials, int P, size_t E,
                                                        float* __restrict__ out, const float* __restrict__ dz,
                                                        int B, int L, float* __restrict__ db,
                                                        const float* __restrict__ dap, int nda,
                                                        float* __restrict__ dslope, int accumulate,
                                                        const float* __restrict__ rows, int RP, int RE,
-                                                       double* __restrict__ rsum) {
+                                                       double* __restrict__ rsum, HeadFin fin) {
   __shared__ double sh[256];
   const unsigned nE = (unsigned)((E + 255) / 256);
+  if (fin.part && blockIdx.x == fin.block) {
+    head_finalize_slot(fin.part, fin.P, fin.scale0, fin.stats, fin.acc, threadIdx.x);
+    return;
+  }
   if (blockIdx.x > nE + L) {
     const int col = threadIdx.x & 15, slice = threadIdx.x >> 4;
     const int e = (int)(blockIdx.x - (nE + L + 1)) * 16 + col;
@@ -342,10 +349,12 @@ static int btl_chunks(int B, int K) {
 // every reduction of the bottleneck backward in one launch (also used by btlnk_chain.hip)
 int launch_btlnk_reduce(const float* partials, int P, size_t E, float* out, const float* dz, int B, int L, float* db,
                         const float* dap, int nda, float* dslope, int accumulate, hipStream_t stream, const float* rows,
-                        int RP, int RE, double* rsum) {
+                        int RP, int RE, double* rsum, HeadFin fin) {
   const unsigned extra = rows ? (unsigned)ceil_div(RE, 16) : 0u;
-  hipLaunchKernelGGL(k_btlnk_reduce, dim3((unsigned)((E + 255) / 256) + L + 1 + extra), dim3(256), 0, stream, partials, P, E, out, dz,
-                     B, L, db, dap, nda, dslope, accumulate, rows, RP, RE, rsum);
+  unsigned blocks = (unsigned)((E + 255) / 256) + L + 1 + extra;
+  if (fin.part) fin.block = blocks++;
+  hipLaunchKernelGGL(k_btlnk_reduce, dim3(blocks), dim3(256), 0, stream, partials, P, E, out, dz,
+                     B, L, db, dap, nda, dslope, accumulate, rows, RP, RE, rsum, fin);
   return check_launch("btlnk_bwd_reduce");
 }
 
@@ -395,6 +404,21 @@ int coskad_btlnk_fwd_ws_f32(const float* U, const float* W, const float* bias, c
   if ((rc = check_launch("btlnk_fwd_t"))) return rc;
   hipLaunchKernelGGL(k_btlnk_fwd_sum, dim3(ceil_div(B * 16, 256)), dim3(256), 0, stream, part, bias, z, B, L, kBtlKS);
   return check_launch("btlnk_fwd_sum");
+}
+
+/* The split-K partials of coskad_btlnk_fwd_ws_f32 alone: part [coskad_btlnk_fwd_ks()][B][16] (coskad_btlnk_fwd_ws_bytes(B) bytes),
+ * z[n][l] = (sum over the slices in order) + bias[l] left to the consumer (coskad_btlnk_bwd_chain_head_f32).  L <= 16, K % 16 == 0. */
+int coskad_btlnk_fwd_ks(void) { return kBtlKS; }
+
+int coskad_btlnk_fwd_parts_f32(const float* U, const float* W, const float* slope, float* part, size_t part_bytes, int B, int K,
+                               int L, hipStream_t stream) {
+  if (!U || !W || !part) return fail(COSKAD_ERR_ARG, "btlnk_fwd_parts: null pointer");
+  if (B <= 0 || K <= 0 || L <= 0) return fail(COSKAD_ERR_ARG, "btlnk_fwd_parts: B=%d K=%d L=%d", B, K, L);
+  if (L > 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_parts: latent_dim=%d > 16 not supported", L);
+  if (K % 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_parts: K=%d must be a multiple of 16", K);
+  if (part_bytes < coskad_btlnk_fwd_ws_bytes(B)) return fail(COSKAD_ERR_WORKSPACE, "btlnk_fwd_parts: partials buffer too small");
+  hipLaunchKernelGGL(k_btlnk_fwd_t, dim3(ceil_div(B, 64), kBtlKS), dim3(256), 0, stream, U, W, slope, part, B, K, L);
+  return check_launch("btlnk_fwd_t");
 }
 
 size_t coskad_btlnk_bwd_ws_bytes(int B, int K, int L) {

@@ -30,6 +30,7 @@
 //     row / dW slab per workgroup, summed in fp64 in a fixed order by the reduce launches (deterministic, no atomics).
 #include "fused_ops.h"
 #include "layer_launch.h"
+#include "heads_common.h"
 
 namespace coskad {
 namespace bc {
@@ -55,11 +56,60 @@ constexpr int kThreads = 512;
                     // 8 no LDS staging of them, 16 no P / Q products, 32 no dW products, 64 no G image
 #endif
 
-template <int CT>
+// HD form: the Euclidean one-class head rides in the launch.  The bottleneck forward left its split-K partials part[KS][B][16]; the
+// latent, the head and dz = 2 (z - c) gscale are formed here with the expressions of k_btlnk_fwd_sum and k_mse_head (bit-identical):
+//   * the backward workgroups [0, nbwd) build their tile's dz[16 clips][16 latents] from the partials: waves 0-3, one element per
+//     thread, fetched one tile ahead at the top of phase 2 and handed over through a 16 x kDzStr LDS image at its end (both operand
+//     layouts are then conflict-free ds_read_b32) -- the eight waves do not each repeat the six loads per element;
+//   * blocks [nbwd, nbwd + nhead) are k_mse_head's: one clip per thread, z / dz / score stored, one partial row per block (or the
+//     finished statistics when there is one).  The backward's grid leaves CUs idle (247 workgroups of 140 KB LDS on 256 CUs at
+//     B = 4096), so they run beside it; nobody in this launch reads what they store.
+struct HeadRide {
+  const float *part, *bias, *c;
+  float gscale, scale0;
+  float *z, *dz, *score, *hpart, *stats, *acc;
+  int KS, nbwd, nhead;
+};
+constexpr int kDzStr = 20;       // row stride of the dz image: = 4 (mod 16), clips x latents and latents x clips reads hit 64 banks once
+constexpr int kMaxKS = 8;        // split-K slices the HD form takes
+
+__device__ __forceinline__ void head_ride_block(const HeadRide& hr, int B, int L) {
+  float vals[kHeadSlots];
+#pragma unroll
+  for (int k = 0; k < kHeadSlots; ++k) vals[k] = 0.f;
+  const Vec c = load_vec(hr.c, L);
+  const int bid = (int)blockIdx.x - hr.nbwd;
+  const int n = bid * kFlatBlock + (int)threadIdx.x;
+  if (n < B) {
+    Vec u, g;
+#pragma unroll
+    for (int j = 0; j < LMAX; ++j) {
+      float z = 0.f;
+      if (j < L) {
+        float sum = 0.f;
+        for (int k = 0; k < hr.KS; ++k) sum += hr.part[((size_t)k * B + n) * 16 + j];
+        z = sum + (hr.bias ? hr.bias[j] : 0.f);
+      }
+      u.v[j] = z;
+    }
+    store_vec(hr.z + (size_t)n * L, u, L);
+    const float sq = mse_head_row(u, c, L, hr.gscale, vals, g);
+    store_vec(hr.dz + (size_t)n * L, g, L);
+    if (hr.score) hr.score[n] = sq / (float)L;
+  }
+  block_partials(vals, hr.hpart, hr.scale0, hr.stats, hr.acc, bid, hr.nhead);
+}
+
+template <int CT, bool HD>
 __global__ __launch_bounds__(kThreads, 1) void k_btlnk_bwd_stats(
     const float* __restrict__ U, const float* __restrict__ W, const float* __restrict__ dz, const float* __restrict__ slope,
     float* __restrict__ dU, float* __restrict__ dWp, float* __restrict__ dap, const float* __restrict__ xin,
-    const float* __restrict__ Zg, const float* __restrict__ in_slope, float* __restrict__ prow, int B, int TV, int L, int chunk) {
+    const float* __restrict__ Zg, const float* __restrict__ in_slope, float* __restrict__ prow, int B, int TV, int L, int chunk, HeadRide hr) {
+  static_assert(kFlatBlock == kThreads, "the riding head blocks are k_mse_head's");
+  if (HD && (int)blockIdx.x >= hr.nbwd) {
+    head_ride_block(hr, B, L);
+    return;
+  }
   constexpr int Ci = 16 * CT, NR = 2 * Ci;              // B-side rows: Z's channels, then the layer input's
   constexpr int GCS = HID * RSTR + 4, ZCS = NR * RSTR + 4;   // clip strides (both = 4 mod 8)
   constexpr int NL = NR * NCL * (PT / 4) / kThreads;    // float4 per thread and tile (4 / 8)
@@ -67,6 +117,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_btlnk_bwd_stats(
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* G = lds;
   float* ZX = lds + NCL * GCS;
+  float* DZ = ZX + NCL * ZCS;                           // HD: dz image of the tile, [clip][kDzStr]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wc = wave & 3, h = wave >> 2;
@@ -76,7 +127,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_btlnk_bwd_stats(
   // (rows are 4 T V bytes, never line-aligned), so the tiles of one chunk must sit behind ONE L2: blocks b and b + 8 share an XCD
   // (observed round-robin placement: speed only), hence the bijective remap of cdna_hip_programming.md T1 -- each XCD takes a
   // contiguous run of the chunk-major (chunk, tile) order.  Without it every line crosses the fabric twice (315 vs 254 us at B = 4096).
-  const int nwg = gridDim.x, npt = (TV + PT - 1) / PT;
+  const int nwg = HD ? hr.nbwd : (int)gridDim.x, npt = (TV + PT - 1) / PT;
   int wg = blockIdx.x;
   if (BC_XCD) {
     const int xq = nwg / 8, xr = nwg % 8, xcd = wg % 8;
@@ -163,11 +214,49 @@ __global__ __launch_bounds__(kThreads, 1) void k_btlnk_bwd_stats(
     }
   };
 
+  // HD: thread (clip tid / 16, latent tid % 16) of waves 0-3 forms one element of the next tile's dz from the split-K partials
+  const bool dz_maker = HD && wave < 4;
+  const int mk_cl = tid >> 4, mk_l = tid & 15;
+  const bool mk_ok = dz_maker && mk_l < L;
+  const float mk_c = mk_ok ? hr.c[mk_l] : 0.f, mk_b = (mk_ok && hr.bias) ? hr.bias[mk_l] : 0.f;
+  auto dz_fetch = [&](int n0, float (&pv)[kMaxKS]) {
+    const int n = n0 + mk_cl;
+#pragma unroll
+    for (int k = 0; k < kMaxKS; ++k) pv[k] = (mk_ok && n < nend && k < hr.KS) ? hr.part[((size_t)k * B + n) * 16 + mk_l] : 0.f;
+  };
+  auto dz_put = [&](int n0, const float (&pv)[kMaxKS]) {
+    if (!dz_maker) return;
+    float g = 0.f;
+    if (mk_ok && n0 + mk_cl < nend) {
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < kMaxKS; ++k)
+        if (k < hr.KS) sum += pv[k];
+      const float d = (sum + mk_b) - mk_c;               // k_btlnk_fwd_sum's z, k_mse_head's d
+      g = 2.f * d * hr.gscale;
+    }
+    DZ[mk_cl * kDzStr + mk_l] = g;
+  };
+  auto dz_read = [&](float (&da_)[4], float (&db_)[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) da_[g] = DZ[c * kDzStr + 4 * g + q];       // A operand of dx: row = clip c, k = latent 4 g + q
+#pragma unroll
+    for (int r = 0; r < 4; ++r) db_[r] = DZ[(4 * q + r) * kDzStr + c];     // A operand of dW: row = latent c, k = clip 4 q + r
+  };
+
   float4 zx[NL];
-  float ucur[8][4], dza[4], dzb[4];
+  float ucur[8][4], dza[4], dzb[4], pv[kMaxKS];
   u_load(nbeg, ucur);
-  dz_load(nbeg, dza, dzb);
+  if (HD) {
+    dz_fetch(nbeg, pv);
+  } else {
+    dz_load(nbeg, dza, dzb);
+  }
   zx_load(nbeg, zx);
+  if (HD) {
+    dz_put(nbeg, pv);
+    lds_barrier();
+  }
 
   float* gw = G + 4 * q * GCS + ch0 * RSTR + c;                      // phase 1: G[clip 4 q + r][channel ch0 + i][position c]
   const float* ga = G + 4 * q * GCS + (16 * wc + c) * RSTR + 8 * h;  // phase 2: G[clip 4 q + r][channel 16 wc + c][position 8 h + pl]
@@ -176,6 +265,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_btlnk_bwd_stats(
   for (int n0 = nbeg; n0 < nend; n0 += NCL) {
     // ---- phase 1: dx, dU rows, dW, the G image; the B-side tile into LDS ------------------------------------------------
     float unext[8][4];
+    if (HD) dz_read(dza, dzb);
     if (BC_PF == 2) { zx_store(zx); zx_load(n0 + NCL, zx); }
     if (BC_PF) u_load(n0 + NCL, unext);    // in front of this tile's stores: a whole tile to arrive
     {
@@ -216,7 +306,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_btlnk_bwd_stats(
     } else {
       u_load(n0 + NCL, ucur);              // (dead since phase 1: the next tile travels in the same registers)
     }
-    dz_load(n0 + NCL, dza, dzb);
+    if (HD) {
+      dz_fetch(n0 + NCL, pv);
+    } else {
+      dz_load(n0 + NCL, dza, dzb);
+    }
     if (BC_PF != 2) zx_load(n0 + NCL, zx);
 #pragma unroll
     for (int pl = 0; pl < 8; ++pl)
@@ -231,6 +325,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_btlnk_bwd_stats(
           qacc[t] = mfma(av, zb[r * ZCS + (Ci + 16 * t) * RSTR + pl], qacc[t]);
         }
       }
+    if (HD) dz_put(n0 + NCL, pv);          // (this tile's image was read at the top of phase 1, two barriers ago)
     lds_barrier();                         // every wave has left G and the B-side tile
   }
 
@@ -324,10 +419,11 @@ size_t coskad_btlnk_bwd_chain_ws_bytes(int B, int K, int L, int TV) {
   return ((size_t)p.S * L * K + (size_t)p.S * p.npt + 64) * sizeof(float);
 }
 
-int coskad_btlnk_bwd_chain_f32(const float* U, const float* W, const float* dz, const float* slope, float* dU, float* dW,
-                               float* db, float* dslope, void* ws, size_t ws_bytes, int accumulate, int B, int K, int L,
-                               const float* below_in, const float* below_Z, const float* below_in_slope, int below_Ci, int TV,
-                               float* stats_out, size_t stats_out_bytes, int* stats_rows, hipStream_t stream) {
+/* the shared body: `hr` NULL -> dz is given; else the head rides (hr->nbwd / nhead are set here) and dz is hr->dz */
+static int btlnk_bwd_chain_run(const float* U, const float* W, const float* dz, const float* slope, float* dU, float* dW, float* db,
+                               float* dslope, void* ws, size_t ws_bytes, int accumulate, int B, int K, int L, const float* below_in,
+                               const float* below_Z, const float* below_in_slope, int below_Ci, int TV, float* stats_out,
+                               size_t stats_out_bytes, int* stats_rows, bc::HeadRide* hr, hipStream_t stream) {
   if (!U || !W || !dz || !dU || !dW || !ws || !below_in || !below_Z || !stats_out || !stats_rows)
     return fail(COSKAD_ERR_ARG, "btlnk_bwd_chain: null pointer");
   if (B <= 0 || K <= 0 || L <= 0) return fail(COSKAD_ERR_ARG, "btlnk_bwd_chain: B=%d K=%d L=%d", B, K, L);
@@ -343,27 +439,75 @@ int coskad_btlnk_bwd_chain_f32(const float* U, const float* W, const float* dz, 
   const int E = 2 * bc::HID * below_Ci + bc::HID;
   float* dWp = reinterpret_cast<float*>(ws);
   float* dap = dWp + (size_t)p.S * L * K;
-  const size_t lds = (size_t)bc::NCL * ((bc::HID * bc::RSTR + 4) + (2 * below_Ci * bc::RSTR + 4)) * sizeof(float);
+  size_t lds = (size_t)bc::NCL * ((bc::HID * bc::RSTR + 4) + (2 * below_Ci * bc::RSTR + 4)) * sizeof(float);
+  bc::HeadRide ride = {};
+  int grid = rows;
+  if (hr) {
+    hr->nbwd = rows;
+    hr->nhead = head_blocks(B);
+    ride = *hr;
+    grid += hr->nhead;
+    lds += (size_t)bc::NCL * bc::kDzStr * sizeof(float);
+  }
   int rc;
   {
   ProbeScope probe(KID_BTLNK_BWD, below_Ci, L, stream);
+#define BC_LAUNCH(CT_, HD_)                                                                                                          \
+  do {                                                                                                                               \
+    auto k = bc::k_btlnk_bwd_stats<CT_, HD_>;                                                                                        \
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
+    hipLaunchKernelGGL(k, dim3(grid), dim3(bc::kThreads), lds, stream, U, W, dz, slope, dU, dWp, dap, below_in, below_Z,             \
+                       below_in_slope, stats_out, B, TV, L, p.chunk, ride);                                                          \
+  } while (0)
   if (below_Ci == 32) {
-    auto k = bc::k_btlnk_bwd_stats<2>;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(p.npt * p.S), dim3(bc::kThreads), lds, stream, U, W, dz, slope, dU, dWp, dap, below_in, below_Z,
-                       below_in_slope, stats_out, B, TV, L, p.chunk);
+    if (hr) BC_LAUNCH(2, true); else BC_LAUNCH(2, false);
   } else {
-    auto k = bc::k_btlnk_bwd_stats<1>;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(p.npt * p.S), dim3(bc::kThreads), lds, stream, U, W, dz, slope, dU, dWp, dap, below_in, below_Z,
-                       below_in_slope, stats_out, B, TV, L, p.chunk);
+    if (hr) BC_LAUNCH(1, true); else BC_LAUNCH(1, false);
   }
+#undef BC_LAUNCH
   }
   if ((rc = check_launch("btlnk_bwd_stats"))) return rc;
-  // one launch sums the dW slabs, the bias / slope gradients and the chain buffer's partial rows
+  // one launch sums the dW slabs, the bias / slope gradients and the chain buffer's partial rows (and, behind the riding head's
+  // blocks, their partial rows: k_head_finalize's sums)
   *stats_rows = rows;
+  HeadFin fin;
+  if (hr && hr->nhead > 1 && (hr->stats || hr->acc)) {
+    fin.part = hr->hpart; fin.P = hr->nhead; fin.scale0 = hr->scale0; fin.stats = hr->stats; fin.acc = hr->acc;
+  }
   return launch_btlnk_reduce(dWp, p.S, (size_t)L * K, dW, dz, B, L, db, dap, rows, (dslope && slope) ? dslope : nullptr, accumulate, stream,
-                             stats_out, rows, E, reinterpret_cast<double*>(stats_out + bc::sums_offset(rows, E)));
+                             stats_out, rows, E, reinterpret_cast<double*>(stats_out + bc::sums_offset(rows, E)), fin);
+}
+
+int coskad_btlnk_bwd_chain_f32(const float* U, const float* W, const float* dz, const float* slope, float* dU, float* dW,
+                               float* db, float* dslope, void* ws, size_t ws_bytes, int accumulate, int B, int K, int L,
+                               const float* below_in, const float* below_Z, const float* below_in_slope, int below_Ci, int TV,
+                               float* stats_out, size_t stats_out_bytes, int* stats_rows, hipStream_t stream) {
+  return btlnk_bwd_chain_run(U, W, dz, slope, dU, dW, db, dslope, ws, ws_bytes, accumulate, B, K, L, below_in, below_Z, below_in_slope,
+                             below_Ci, TV, stats_out, stats_out_bytes, stats_rows, nullptr, stream);
+}
+
+/* coskad_btlnk_bwd_chain_f32 with the Euclidean one-class head in the same launch: instead of a finished dz it takes the split-K
+ * partials `part` [KS][B][16] of coskad_btlnk_fwd_parts_f32 (KS = coskad_btlnk_fwd_ks()), the Linear's bias (or NULL), the centre c
+ * and `upstream`, and forms z = (sum of the slices in order) + bias and dz = 2 (z - c) upstream / (B L) itself -- the values of
+ * coskad_btlnk_fwd_ws_f32 + coskad_mse_head_f32, bit for bit.  z, dz [B][L] are written; score [B], stats, acc as in
+ * coskad_mse_head_f32 (NULL to skip); head_ws: coskad_head_ws_floats(B) floats. */
+int coskad_btlnk_bwd_chain_head_f32(const float* U, const float* W, const float* part, int KS, const float* bias, const float* c,
+                                    float upstream, float* z, float* dz, float* score, float* stats, float* acc, float* head_ws,
+                                    const float* slope, float* dU, float* dW, float* db, float* dslope, void* ws, size_t ws_bytes,
+                                    int accumulate, int B, int K, int L, const float* below_in, const float* below_Z,
+                                    const float* below_in_slope, int below_Ci, int TV, float* stats_out, size_t stats_out_bytes,
+                                    int* stats_rows, hipStream_t stream) {
+  if (!part || !c || !z || !dz || !head_ws) return fail(COSKAD_ERR_ARG, "btlnk_bwd_chain_head: null pointer");
+  if (KS <= 0 || KS > bc::kMaxKS) return fail(COSKAD_ERR_SHAPE, "btlnk_bwd_chain_head: %d K slices (1 .. %d)", KS, bc::kMaxKS);
+  if (B <= 0 || L <= 0 || L > 16) return fail(COSKAD_ERR_SHAPE, "btlnk_bwd_chain_head: B=%d latent_dim=%d (1 .. 16)", B, L);
+  bc::HeadRide hr = {};
+  hr.part = part; hr.bias = bias; hr.c = c;
+  hr.gscale = upstream / ((float)B * (float)L);
+  hr.scale0 = 1.f / ((float)B * (float)L);
+  hr.z = z; hr.dz = dz; hr.score = score; hr.hpart = head_ws; hr.stats = stats; hr.acc = acc;
+  hr.KS = KS;
+  return btlnk_bwd_chain_run(U, W, dz, slope, dU, dW, db, dslope, ws, ws_bytes, accumulate, B, K, L, below_in, below_Z, below_in_slope,
+                             below_Ci, TV, stats_out, stats_out_bytes, stats_rows, &hr, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 //                   the dA / dT sums in registers for the whole launch; rows [dA][dT] as k_reduce_gcn reads them
 #include "mfma_ops.h"
 #include "layer_launch.h"
+#include "ftab_ops.h"
 
 namespace coskad {
 namespace fl {
@@ -226,11 +227,22 @@ __global__ __launch_bounds__((64 * first_bwd_waves<T, V>()), 4) void k_first_bwd
 //   wave round, a lane owns positions lane + 64 k; the mixing is 12 + 17 FMAs per element on LDS operands.  Partial row per
 //   block: [MX C^2][sumX C][MZ C^2][sumZ C] (what k_reduce_partials / k_train_fold consume).
 constexpr int NWM = 8;   // waves per block of k_first_moments: 512 blocks x 8 waves take B = 4096 in ONE round (4 x 768: two, the second a third full)
+constexpr int kFtabBlocks = (ftab_elems<12, 17>() + 64 * NWM - 1) / (64 * NWM);   // blocks per operand table riding in the launch
 template <int T, int V, int CI>
 __global__ __launch_bounds__(64 * NWM, 4) void k_first_moments(const float* __restrict__ in, const float* __restrict__ Aw,
                                                           const float* __restrict__ Tw, const float* __restrict__ in_slope,
-                                                          float* __restrict__ partials, int B, float* __restrict__ Zout) {
+                                                          float* __restrict__ partials, int B, float* __restrict__ Zout, int nmom,
+                                                          FtabArgs tabs) {
   constexpr int TV = T * V, NA = T * V * V, NT = V * T * T, KP = (TV + 63) / 64;
+  // blocks nmom..: the forward operand tables of the layers above (k_build_ftab's elements; tabs.n layers, kFtabBlocks blocks each) --
+  // parameter-only work that rides in this launch, which depends on the clips only, instead of opening the step as a launch of its own
+  if ((int)blockIdx.x >= nmom) {
+    if constexpr (T == 12 && V == 17) {
+      const int b = (int)blockIdx.x - nmom;
+      ftab_store<T, V>(tabs, b / kFtabBlocks, (b % kFtabBlocks) * 64 * NWM + (int)threadIdx.x);
+    }
+    return;
+  }
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* AwL = lds;
   float* TwL = AwL + NA;
@@ -253,9 +265,9 @@ __global__ __launch_bounds__(64 * NWM, 4) void k_first_moments(const float* __re
     for (int b = 0; b < CI; ++b) { mx[a][b] = 0.f; mz[a][b] = 0.f; }
   }
   __syncthreads();
-  const int rounds = (B + gridDim.x * NWM - 1) / (gridDim.x * NWM);
+  const int rounds = (B + nmom * NWM - 1) / (nmom * NWM);
   for (int r = 0; r < rounds; ++r) {              // every wave runs every round (the block barriers below are uniform)
-    const int clip = (r * gridDim.x + blockIdx.x) * NWM + wave;
+    const int clip = (r * nmom + blockIdx.x) * NWM + wave;
     const bool live = clip < B;
     const float* gx = in + (size_t)(live ? clip : 0) * CI * TV;
 #pragma unroll
@@ -451,17 +463,23 @@ int launch_first_bwd(const float* in, const float* Zg, const float* dU, const fl
 // training forward of a few-channel layer: moments + stored Z (partial rows: *rows_out, each 2 (Ci^2 + Ci) floats)
 template <int T, int V>
 static int launch_first_moments_tv(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B,
-                                   int Ci, float* Zout, int max_rows, hipStream_t st, int* rows_out) {
+                                   int Ci, float* Zout, int max_rows, hipStream_t st, int* rows_out, const FtabArgs* ride) {
   int grid = (B + fl::NWM - 1) / fl::NWM;
   if (grid > 512) grid = 512;
   if (grid > max_rows) grid = max_rows;
   *rows_out = grid;
+  FtabArgs tabs{};
+  if (ride && ride->n > 0) {
+    if (T != 12 || V != 17 || ride->n > 4) return fail(COSKAD_ERR_SHAPE, "first_moments: operand tables ride at T=12, V=17, 1..4 layers");
+    tabs = *ride;
+  }
+  const int nmom = grid, ntab = tabs.n * fl::kFtabBlocks;
   const size_t lds = ((size_t)T * V * V + (size_t)V * T * T + 2 * fl::NWM * (size_t)Ci * T * V) * sizeof(float);
 #define LAUNCH_FM(CI)                                                                                                   \
   do {                                                                                                                  \
     auto k = fl::k_first_moments<T, V, CI>;                                                                             \
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * fl::NWM), lds, st, in, Aw, Tw, in_slope, partials, B, Zout);                    \
+    hipLaunchKernelGGL(k, dim3(nmom + ntab), dim3(64 * fl::NWM), lds, st, in, Aw, Tw, in_slope, partials, B, Zout, nmom, tabs); \
   } while (0)
   {
     ProbeScope probe(KID_FWD_MOMENTS, Ci, 0, st);
@@ -475,8 +493,8 @@ static int launch_first_moments_tv(const float* in, const float* Aw, const float
 }
 
 int launch_first_moments(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B, int Ci,
-                         int T, int V, float* Zout, int max_rows, hipStream_t st, int* rows_out) {
-#define CALL(T_, V_) return launch_first_moments_tv<T_, V_>(in, Aw, Tw, in_slope, partials, B, Ci, Zout, max_rows, st, rows_out)
+                         int T, int V, float* Zout, int max_rows, hipStream_t st, int* rows_out, const FtabArgs* ride) {
+#define CALL(T_, V_) return launch_first_moments_tv<T_, V_>(in, Aw, Tw, in_slope, partials, B, Ci, Zout, max_rows, st, rows_out, ride)
   COSKAD_DISPATCH_TV(T, V, CALL);
 #undef CALL
 }

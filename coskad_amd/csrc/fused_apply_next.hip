@@ -14,6 +14,7 @@
 // k_first_apply / k_layer_apply_ring of layers 1..3 at T = 12, V = 17, <= 32 output channels.
 #include "fused_ops.h"
 #include "layer_launch.h"
+#include "ftab_ops.h"
 
 #ifndef FN_ABLATE
 #define FN_ABLATE 0   // timing-only builds (tools/bench_apply_next.py): bit 0 U rows, 1 Gram x, 2 temporal, 3 spatial, 4 Z rows, 5 Gram z, 6 GEMM
@@ -24,33 +25,10 @@ namespace fn {
 
 using namespace ff;
 
-// forward operand tables of up to 4 layers, the tab-stream layout of the eval-mode encoder (coskad_amd/fused_plan.py):
-//   temporal  rec[v][l][s]     = T[v][4s+q][j]   (s < 3, j < 12)
-//   spatial   rec[t][l][0..4]  = A[t][4s+q][j]   (4s+q < 17),  [5..9] = A[t][4s+q][16]
-struct FtabArgs {
-  const float* A[4];
-  const float* Tm[4];
-  float* tab[4];
-};
+// forward operand tables of up to 4 layers (ftab_ops.h), one grid row per layer
+static_assert(ftab_elems<T, V>() == LAYER_F4 * 4, "the table layout of ftab_ops.h is this file's");
 __global__ void k_build_ftab(FtabArgs args) {
-  const int layer = blockIdx.y;
-  const float* __restrict__ Aw = args.A[layer];
-  const float* __restrict__ Tw = args.Tm[layer];
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= LAYER_F4 * 4) return;
-  float val = 0.f;
-  if (e < TEMP_F4 * 4) {
-    const int v = e / 256, l = (e >> 2) & 63, s = e & 3, j = l & 15, q = l >> 4;
-    if (s < 3 && j < T) val = Tw[v * T * T + (4 * s + q) * T + j];
-  } else {
-    const int r = e - TEMP_F4 * 4;
-    const int t = r / (3 * 256), c = (r / 256) % 3, l = (r >> 2) & 63, k = 4 * c + (r & 3), j = l & 15, q = l >> 4;
-    if (k < 10) {
-      const int s = k < 5 ? k : k - 5, w = 4 * s + q;
-      if (w < V) val = Aw[t * V * V + w * V + (k < 5 ? j : 16)];
-    }
-  }
-  args.tab[layer][e] = val;
+  ftab_store<T, V>(args, blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // CT: 16-row groups of the input (0: TWO input channels, the first layer: Z rows | X rows are ONE k-step);
@@ -378,7 +356,8 @@ int ftab_floats() { return ff::LAYER_F4 * 4; }
 
 int launch_build_ftab(const float* const* A, const float* const* Tm, float* const* tab, int n, hipStream_t st) {
   if (n < 1 || n > 4) return fail(COSKAD_ERR_ARG, "build_ftab: 1..4 layers per launch, got %d", n);
-  fn::FtabArgs args{};
+  FtabArgs args{};
+  args.n = n;
   for (int i = 0; i < n; ++i) {
     if (!A[i] || !Tm[i] || !tab[i]) return fail(COSKAD_ERR_ARG, "build_ftab: null pointer (layer %d)", i);
     args.A[i] = A[i]; args.Tm[i] = Tm[i]; args.tab[i] = tab[i];

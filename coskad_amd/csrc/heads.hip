@@ -18,28 +18,6 @@
 
 namespace coskad {
 
-struct Vec {
-  float v[LMAX];
-};
-
-__device__ __forceinline__ Vec load_vec(const float* p, int L) {
-  Vec r;
-#pragma unroll
-  for (int j = 0; j < LMAX; ++j) r.v[j] = j < L ? p[j] : 0.f;
-  return r;
-}
-__device__ __forceinline__ void store_vec(float* p, const Vec& a, int L) {
-#pragma unroll
-  for (int j = 0; j < LMAX; ++j)
-    if (j < L) p[j] = a.v[j];
-}
-__device__ __forceinline__ float dot(const Vec& a, const Vec& b) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < LMAX; ++j) s = fmaf(a.v[j], b.v[j], s);
-  return s;
-}
-
 // e = expmap0(u), p = project(e); returns p and the pieces the backward needs
 struct Embed {
   Vec p;
@@ -128,38 +106,6 @@ __device__ __forceinline__ Vec hyp_embed_bwd(const Vec& u, const Embed& em, cons
   return gu;
 }
 
-// Per-block partial row of kHeadSlots floats (fixed slots, summed in block order later):
-//   [0] loss term   [1..16] vector sum   [17] scalar A   [18] scalar B
-constexpr int kHeadSlots = LMAX + 3;
-
-// A one-block launch (B <= kHeadSingleRows clips) writes the finished statistics itself -- no partial row, no k_head_finalize
-// launch behind it.  Larger batches keep one row per thread: ONE block striding over 4096 rows measured 65 us against 12 + 5 us
-// for eight blocks + k_head_finalize (eight dependent load rounds per thread).
-constexpr int kHeadSingleRows = kFlatBlock;
-__host__ __device__ inline int head_blocks(int B) { return B <= kHeadSingleRows ? 1 : ceil_div(B, kFlatBlock); }
-
-__device__ __forceinline__ void block_partials(const float (&vals)[kHeadSlots], float* partials, float scale0, float* stats,
-                                               float* acc) {
-  __shared__ float sh[kFlatBlock / 64][kHeadSlots];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kHeadSlots; ++k) {
-    const float s = wave_sum(vals[k]);
-    if (lane == 0) sh[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kHeadSlots) {
-    float s = 0.f;
-    for (int w = 0; w < kFlatBlock / 64; ++w) s += sh[w][threadIdx.x];
-    if (gridDim.x == 1) {
-      if (stats) stats[threadIdx.x] = threadIdx.x == 0 ? s * scale0 : s;
-      if (acc) acc[threadIdx.x] += s;
-    } else {
-      partials[blockIdx.x * kHeadSlots + threadIdx.x] = s;
-    }
-  }
-}
-
 // Euclidean head.  slots: [0] sum (z-c)^2, [1..L] sum z, [17] #clips, [18] sum |z|
 __global__ __launch_bounds__(kFlatBlock) void k_mse_head(const float* __restrict__ z,
                                                     const float* __restrict__ cvec,
@@ -175,21 +121,11 @@ __global__ __launch_bounds__(kFlatBlock) void k_mse_head(const float* __restrict
   for (int n = blockIdx.x * kFlatBlock + threadIdx.x; n < B; n += gridDim.x * kFlatBlock) {
     const Vec u = load_vec(z + (size_t)n * L, L);
     Vec g;
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < LMAX; ++j) {
-      const float d = j < L ? u.v[j] - c.v[j] : 0.f;
-      sq = fmaf(d, d, sq);
-      g.v[j] = 2.f * d * gscale;  // d mean((z-c)^2)/dz, gscale = upstream / (B*L)
-      vals[1 + j] += u.v[j];
-    }
-    vals[0] += sq;
-    vals[LMAX + 1] += 1.f;
-    vals[LMAX + 2] += sqrtf(dot(u, u));
+    const float sq = mse_head_row(u, c, L, gscale, vals, g);
     if (dz) store_vec(dz + (size_t)n * L, g, L);
     if (score) score[n] = sq / (float)L;  // MSELoss(reduction='none')(c, z).mean(-1), eval_utils.py:63-64
   }
-  block_partials(vals, partials, scale0, stats, acc);
+  block_partials(vals, partials, scale0, stats, acc, blockIdx.x, gridDim.x);
 }
 
 // Mahalanobis head (eval_utils.py:28-38; staticCenter.py:178-181).  slots: [0] sum dist, [1..L] sum z, [17] #clips,
@@ -239,7 +175,7 @@ __global__ __launch_bounds__(kFlatBlock) void k_mahalanobis_head(const float* __
       store_vec(dz + (size_t)n * L, g, L);
     }
   }
-  block_partials(vals, partials, scale0, stats, acc);
+  block_partials(vals, partials, scale0, stats, acc, blockIdx.x, gridDim.x);
 }
 
 // gram (+)= sum_n z_n z_n^T  [L x L]; one block, thread (i, j), clips staged through LDS in fixed order.
@@ -298,19 +234,14 @@ __global__ __launch_bounds__(kFlatBlock) void k_poincare_head(const float* __res
       }
     }
   }
-  block_partials(vals, partials, scale0, stats, acc);
+  block_partials(vals, partials, scale0, stats, acc, blockIdx.x, gridDim.x);
 }
 
 // stats[k] = sum_p partials[p][k] (slot 0 additionally * scale0);  acc[k] += raw sums
 __global__ __launch_bounds__(64) void k_head_finalize(const float* __restrict__ partials, int P,
                                                        float scale0, float* __restrict__ stats,
                                                        float* __restrict__ acc) {
-  const int k = threadIdx.x;
-  if (k >= kHeadSlots) return;
-  double s = 0.0;
-  for (int p = 0; p < P; ++p) s += (double)partials[p * kHeadSlots + k];
-  if (stats) stats[k] = (float)(k == 0 ? s * (double)scale0 : s);
-  if (acc) acc[k] += (float)s;
+  head_finalize_slot(partials, P, scale0, stats, acc, threadIdx.x);
 }
 
 // dist(c, zh) per row for points already on the ball (eval scoring, eval_utils.py:66-67)

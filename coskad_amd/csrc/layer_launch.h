@@ -119,7 +119,9 @@ struct FoldOut {
   float* bias = nullptr;
   float* stat = nullptr;
 };
+struct FtabArgs;        // ftab_ops.h
 struct LayerStatsArgs {
+  const FtabArgs* ftab = nullptr;    // operand tables of the layers above, built by extra blocks of the first layer's moments launch
   const float* in = nullptr;
   const float* A = nullptr;
   const float* Tm = nullptr;
@@ -200,8 +202,9 @@ int launch_first_stats(const float* in, const float* Zg, const float* dU, const 
 int launch_first_bwd(const float* in, const float* Zg, const float* dU, const float* Aw, const float* Tw, const float* coef,
                      const float* in_slope, float* partials, int B, int Ci, int Co, int T, int V, int max_rows, hipStream_t st,
                      int* rows_out);
+// ride (n > 0; T = 12, V = 17): extra blocks build the forward operand tables of n layers (ftab_ops.h) in the same launch
 int launch_first_moments(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B, int Ci,
-                         int T, int V, float* Zout, int max_rows, hipStream_t st, int* rows_out);
+                         int T, int V, float* Zout, int max_rows, hipStream_t st, int* rows_out, const FtabArgs* ride = nullptr);
 int launch_first_apply(const float* Z, const float* in, float* out, const float* wfold, const float* bias, const float* in_slope,
                        int B, int Ci, int Co, int TVr, hipStream_t st);
 // fwd_moments_bpc.hip
@@ -245,10 +248,19 @@ int apply_next_bpc_rows(int B);
 int launch_layer_apply_next_bpc(const float* Z, const float* in, float* out, const float* wfold, const float* bias,
                                 const float* in_slope, const float* out_slope, const float* ftab, float* Znext, float* partials,
                                 int B, int Ci, int Co, hipStream_t st);
-// bottleneck.hip: every reduction of the bottleneck backward in one launch
+// bottleneck.hip: every reduction of the bottleneck backward in one launch.  fin (part != NULL): one more block turns the P partial
+// rows of the one-class head's blocks into stats / acc (k_head_finalize's sums; `block` is set by the launcher)
+struct HeadFin {
+  const float* part = nullptr;
+  int P = 0;
+  float scale0 = 0.f;
+  float* stats = nullptr;
+  float* acc = nullptr;
+  unsigned block = 0;
+};
 int launch_btlnk_reduce(const float* partials, int P, size_t E, float* out, const float* dz, int B, int L, float* db,
                         const float* dap, int nda, float* dslope, int accumulate, hipStream_t stream, const float* rows,
-                        int RP, int RE, double* rsum);
+                        int RP, int RE, double* rsum, HeadFin fin = HeadFin());
 // btlnk_wide.hip: latents above 64
 size_t wide_btlnk_fwd_ws_bytes(int B, int K, int L);
 size_t wide_btlnk_bwd_ws_bytes(int B, int K, int L);

@@ -15,6 +15,7 @@
 //   k_train_fold    : stats -> folded weights, saved stats for backward, running-stat update
 #include "mfma_ops.h"
 #include "layer_launch.h"
+#include "ftab_ops.h"
 
 namespace coskad {
 
@@ -331,9 +332,11 @@ static int launch_train_stats(const LayerStatsArgs& a) {
   double* red = reinterpret_cast<double*>(reinterpret_cast<char*>(a.ws) + round_up((int)(kMaxGrid * (size_t)E * sizeof(float)), 256));
   const int need_x = a.sums ? 1 : (a.p.Wr != nullptr);
   int rows = grid;
+  if (a.ftab && !(a.Zout && Ci <= 4 && T == 12 && V == 17))
+    return fail(COSKAD_ERR_SHAPE, "train_stats: operand tables ride only in the first layer's moments launch (stored Z, C_in <= 4, T=12, V=17)");
   if (a.Zout && Ci <= 4 && TV % 4 == 0) {
     // a handful of input channels (the first layer): plain FMAs, one clip per wave (first_layer.hip)
-    int rc1 = launch_first_moments(a.in, a.A, a.Tm, a.in_slope, partials, B, Ci, T, V, a.Zout, kMaxGrid, st, &rows);
+    int rc1 = launch_first_moments(a.in, a.A, a.Tm, a.in_slope, partials, B, Ci, T, V, a.Zout, kMaxGrid, st, &rows, a.ftab);
     if (rc1) return rc1;
   } else if (a.Zout && fwd_moments_bpc_ok(T, V, Ci)) {
     // the 25-joint layout, 16 / 32 channels: one clip per four-wave workgroup, mixing operands in registers (fwd_moments_bpc.hip)
@@ -400,7 +403,7 @@ static int dispatch_train_stats(const char* who, const LayerStatsArgs& a, int T,
     if ((size_t)a.Zout & 15) return fail(COSKAD_ERR_ARG, "%s: `Z` must be 16-byte aligned at window lengths 8, 16 and 24", who);
     if (full ? (coskad_layer_train_window_ok(T, V, a.Ci, a.Co) || coskad_layer_train_window_narrow_ok(T, V, a.Ci, a.Co))
              : window_moments_ok(T, V, a.Ci))
-      return launch_train_stats_window(a, T, V);
+      return a.ftab ? fail(COSKAD_ERR_SHAPE, "%s: no operand tables ride at window lengths 8, 16 and 24", who) : launch_train_stats_window(a, T, V);
   }
 #define CALL(T_, V_) return launch_train_stats<T_, V_>(a)
   COSKAD_DISPATCH_TV(T, V, CALL);
@@ -435,6 +438,37 @@ int coskad_layer_train_stats_z_f32(const float* in, const float* A, const float*
   if (int rc = check_layer_stats("layer_train_stats", a, kNeedInput | kNeedFold | kNeedWs)) return rc;
   if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_train_stats: B=%d Ci=%d Co=%d", B, Ci, Co);
   return dispatch_train_stats("layer_train_stats", a, T, V, true);
+}
+
+/* The same with the forward operand tables of ntab <= 4 layers above (coskad_build_ftab_f32's: tab[i] from tab_A[i], tab_Tm[i]) built
+ * by extra blocks of the statistics pass's launch instead of a launch of their own: the first layer of a stack (C_in <= 4, stored
+ * Z, T = 12, V = 17), whose moments depend on the clips only while the tables depend on parameters only. */
+int coskad_layer_train_stats_z_ftab_f32(const float* in, const float* A, const float* Tm, const float* in_slope,
+                                        const float* Wt, const float* bt, const float* gamma_t,
+                                        const float* beta_t, float* rmean_t, float* rvar_t, long long* nbt_t,
+                                        const float* Wr, const float* br, const float* gamma_r,
+                                        const float* beta_r, float* rmean_r, float* rvar_r, long long* nbt_r,
+                                        float momentum, float* wfold, float* bias, float* stat, void* ws,
+                                        size_t ws_bytes, int B, int Ci, int Co, int T, int V,
+                                        hipStream_t stream, float* Z, const float* const* tab_A, const float* const* tab_Tm,
+                                        float* const* tab, int ntab) {
+  if (!tab_A || !tab_Tm || !tab || !Z) return fail(COSKAD_ERR_ARG, "layer_train_stats_ftab: null pointer");
+  if (ntab < 1 || ntab > 4) return fail(COSKAD_ERR_ARG, "layer_train_stats_ftab: 1..4 operand tables, got %d", ntab);
+  FtabArgs tabs{};
+  tabs.n = ntab;
+  for (int i = 0; i < ntab; ++i) {
+    if (!tab_A[i] || !tab_Tm[i] || !tab[i]) return fail(COSKAD_ERR_ARG, "layer_train_stats_ftab: null pointer (table %d)", i);
+    tabs.A[i] = tab_A[i]; tabs.Tm[i] = tab_Tm[i]; tabs.tab[i] = tab[i];
+  }
+  const LayerStatsArgs a{
+      .ftab = &tabs, .in = in, .A = A, .Tm = Tm, .in_slope = in_slope,
+      .p = {.Wt = Wt, .bt = bt, .gt = gamma_t, .bet = beta_t, .rm_t = rmean_t, .rv_t = rvar_t, .nbt_t = nbt_t, .Wr = Wr, .br = br,
+            .gr = gamma_r, .ber = beta_r, .rm_r = rmean_r, .rv_r = rvar_r, .nbt_r = nbt_r, .momentum = momentum},
+      .out = {.wfold = wfold, .bias = bias, .stat = stat},
+      .Zout = Z, .ws = ws, .ws_bytes = ws_bytes, .B = B, .Ci = Ci, .Co = Co, .stream = stream};
+  if (int rc = check_layer_stats("layer_train_stats_ftab", a, kNeedInput | kNeedFold | kNeedWs)) return rc;
+  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_train_stats_ftab: B=%d Ci=%d Co=%d", B, Ci, Co);
+  return dispatch_train_stats("layer_train_stats_ftab", a, T, V, true);
 }
 
 /* The same, Z not stored. */

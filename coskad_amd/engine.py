@@ -166,16 +166,20 @@ def chain_forward(x: Tensor, layers: List[LayerTensors], training: bool, ws: Wor
     # fuse[i]: layer i's apply kernel also forms layer i+1's Z and moment partials (csrc/fused_apply_next.hip), so
     # layer i+1 needs no statistics pass of its own
     fuse = [False] * n
-    ftab = None
+    ftab = ftab_ride = None
     if all(batch_stats) and STORE_Z and FUSE_NEXT:
         for i in range(n - 1):
             fuse[i] = layers[i + 1].Ci == layers[i].Co and ops.layer_apply_next_ok(layers[i].Ci, layers[i].Co, T, V)
         nxt = [i + 1 for i in range(n - 1) if fuse[i]]
         if nxt:
             ftab = torch.empty(n, ops.ftab_floats(), device=x.device, dtype=torch.float32)
-            for k in range(0, len(nxt), 4):
-                grp = nxt[k:k + 4]
-                ops.build_ftabs([layers[i].A for i in grp], [layers[i].T for i in grp], [ftab[i] for i in grp])
+            if FTAB_RIDES and len(nxt) <= 4 and pending0 is None and sync_count is None and layers[0].Ci <= 4 and fuse[0]:
+                # the chain starts with the few-channel first layer's own statistics pass: the tables ride in its launch
+                ftab_ride = ([layers[i].A for i in nxt], [layers[i].T for i in nxt], [ftab[i] for i in nxt])
+            else:
+                for k in range(0, len(nxt), 4):
+                    grp = nxt[k:k + 4]
+                    ops.build_ftabs([layers[i].A for i in grp], [layers[i].T for i in grp], [ftab[i] for i in grp])
     # the same fusion on the 25-joint layout (csrc/fused_apply_flat.hip, NX form): no operand tables, the next layer's A / T directly
     fuse_flat = [False] * n
     if all(batch_stats) and STORE_Z and FUSE_NEXT and sync is None:
@@ -215,7 +219,8 @@ def chain_forward(x: Tensor, layers: List[LayerTensors], training: bool, ws: Wor
                     Z = torch.empty_like(h)     # gcn(PReLU(h)): written by the statistics pass, read by everything after
                 wfold, bias, stat = ops.layer_train_stats(
                     h, L.A, L.T, slope, L.w2(L.Wt), L.bt, L.gt, L.bet, L.rm_t, L.rv_t, L.nbt_t,
-                    L.w2(L.Wr), L.br, L.gr, L.ber, L.rm_r, L.rv_r, L.nbt_r, buf, momentum=L.step_momentum(), Z=Z)
+                    L.w2(L.Wr), L.br, L.gr, L.ber, L.rm_r, L.rv_r, L.nbt_r, buf, momentum=L.step_momentum(), Z=Z,
+                    ftabs=ftab_ride if i == 0 else None)
         else:
             wfold, bias = eval_fold(L)
             stat = None
@@ -262,6 +267,13 @@ FUSE_TOP = True
 # with the stored-Z path: layer i's apply kernel also produces layer i+1's Z and BatchNorm moment partials where
 # csrc/fused_apply_next.hip takes the shape (tests flip it to cover the separate statistics pass)
 FUSE_NEXT = True
+# with FUSE_NEXT: the operand tables of the layers above are built by extra blocks of the first layer's moments launch
+# (csrc/first_layer.hip) where the chain starts with the few-channel first layer, instead of a launch of their own in front of it.
+# Off: bit-identical and one launch fewer, but its 2-4 us stayed inside the run-to-run spread of the step
+FTAB_RIDES = False
+# the Euclidean head rides in the bottleneck backward's launch, which forms dz from the forward's split-K partials itself
+# (csrc/btlnk_chain.hip, HD form): no summing launch, no head launch, no finalize launch.  Needs FUSE_TOP's conditions.
+HEAD_RIDES = True
 
 
 class SideStream:
@@ -285,6 +297,16 @@ class SideStream:
             self.ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8)
 
 
+def _chain_top(ctx: Optional[ChainCtx], layers: List[LayerTensors], U: Tensor, L: int):
+    """(index, stored Z) of the top layer when the bottleneck's backward can form its batch reductions (csrc/btlnk_chain.hip), else None"""
+    i = len(layers) - 1 if layers else -1
+    Z = ctx.zs[i] if (ctx is not None and ctx.zs and i >= 0) else None
+    if (FUSE_TOP and Z is not None and U.dim() == 4 and layers[i].Wr is not None and L <= 16
+            and ops.btlnk_bwd_chain_ok(U.numel() // U.shape[0], U.shape[2] * U.shape[3], layers[i].Ci)):
+        return i, Z
+    return None
+
+
 def btlnk_backward(ctx: Optional[ChainCtx], layers: List[LayerTensors], U: Tensor, W: Tensor, dz: Tensor, slope: Optional[Tensor],
                    dW: Tensor, db: Optional[Tensor], dslope: Optional[Tensor], ws: Workspace):
     """Backward of the bottleneck Linear on the chain's output U (ae.py:97-101) -> (dU, top_stats).  Where the shapes allow
@@ -292,14 +314,30 @@ def btlnk_backward(ctx: Optional[ChainCtx], layers: List[LayerTensors], U: Tenso
     reductions; `top_stats` is then chain_backward's `stats_in`, else None."""
     B = U.shape[0]
     K, L = U.numel() // B, W.shape[0]
-    i = len(layers) - 1 if layers else -1
-    Z = ctx.zs[i] if (ctx is not None and ctx.zs and i >= 0) else None
-    if (FUSE_TOP and Z is not None and U.dim() == 4 and layers[i].Wr is not None and L <= 16
-            and ops.btlnk_bwd_chain_ok(K, U.shape[2] * U.shape[3], layers[i].Ci)):
+    top = _chain_top(ctx, layers, U, L)
+    if top is not None:
+        i, Z = top
         in_slope = layers[i - 1].slope if i > 0 else ctx.in_slope
         return ops.btlnk_bwd_chain(U, W, dz, slope, dW, db, dslope, ws, ctx.inputs[i], Z, in_slope)
     buf = ws.get(ops.btlnk_bwd_ws_bytes(B, K, L), U.device)
     return ops.btlnk_bwd(U, W, dz, slope, dW, db, dslope, buf), None
+
+
+def head_rides(ctx: Optional[ChainCtx], layers: List[LayerTensors], U: Tensor, L: int) -> bool:
+    """btlnk_head_backward takes the step: HEAD_RIDES, the top layer's reductions ride in the bottleneck's backward, split-K forward"""
+    return bool(HEAD_RIDES and _chain_top(ctx, layers, U, L) is not None and (U.numel() // U.shape[0]) % 16 == 0)
+
+
+def btlnk_head_backward(ctx: ChainCtx, layers: List[LayerTensors], U: Tensor, W: Tensor, part: Tensor, bias: Optional[Tensor],
+                        c: Tensor, slope: Optional[Tensor], dW: Tensor, db: Optional[Tensor], dslope: Optional[Tensor], ws: Workspace,
+                        acc: Optional[Tensor] = None):
+    """The Euclidean head and btlnk_backward in one pass from the bottleneck forward's split-K partials `part`
+    (ops.btlnk_fwd_parts) where head_rides(...) holds -> (stats, dU, top_stats); z and dz are by-products nobody reads here."""
+    i, Z = _chain_top(ctx, layers, U, W.shape[0])
+    in_slope = layers[i - 1].slope if i > 0 else ctx.in_slope
+    _, _, _, stats, dU, top_stats = ops.btlnk_bwd_chain_head(U, W, part, bias, c, slope, dW, db, dslope, ws, ctx.inputs[i], Z, in_slope,
+                                                             acc=acc)
+    return stats, dU, top_stats
 
 
 def chain_backward(ctx: ChainCtx, layers: List[LayerTensors], dU: Tensor, ws: Workspace,

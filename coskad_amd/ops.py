@@ -218,9 +218,11 @@ def train_stats_ws_bytes(Ci: int) -> int:
 
 
 def layer_train_stats(x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t,
-                      Wr, br, gr, ber, rm_r, rv_r, nbt_r, ws, momentum: float = 0.1, Z: Optional[Tensor] = None):
+                      Wr, br, gr, ber, rm_r, rv_r, nbt_r, ws, momentum: float = 0.1, Z: Optional[Tensor] = None, ftabs=None):
     """Train-mode BN statistics of one layer -> (wfold, bias, stat); updates running stats in place.
-    Z (optional, same shape as x): receives gcn(PReLU(x)) for layer_apply_z and the stored-Z backward."""
+    Z (optional, same shape as x): receives gcn(PReLU(x)) for layer_apply_z and the stored-Z backward.
+    ftabs (optional; a stack's first layer, Z stored, T = 12, V = 17): build_ftabs' (As, Ts, tabs) -- the tables are built by extra
+    blocks of the statistics pass's launch instead of a launch of their own."""
     B, Ci, T, V = x.shape
     Co = Wt.shape[0]
     _chk(x, "x"); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T))
@@ -242,7 +244,13 @@ def layer_train_stats(x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t,
     args = (x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r, nbt_r, momentum, wfold, bias, stat, ws,
             ws.numel() * ws.element_size(), B, Ci, Co, T, V, _stream())
     note_raw_write()
-    if Z is None:
+    if ftabs is not None:
+        _chk(Z, "Z", tuple(x.shape))
+        tab_A, tab_T, tabs, ntab = _ftab_pointers(*ftabs, T, V)
+        call("coskad_layer_train_stats_z_ftab_f32", x, A, Tm, in_slope, Wt, bt, gt, bet, rm_t, rv_t, nbt_t, Wr, br, gr, ber, rm_r, rv_r,
+             nbt_r, momentum, wfold, bias, stat, ws, ws.numel() * ws.element_size(), B, Ci, Co, T, V, _stream(), Z, tab_A, tab_T, tabs,
+             ntab)
+    elif Z is None:
         call("coskad_layer_train_stats_f32", *args)
     else:
         call("coskad_layer_train_stats_z_f32", *args, Z)
@@ -339,18 +347,23 @@ def ftab_floats() -> int:
     return _lib.lib().coskad_ftab_floats()
 
 
-def build_ftabs(As, Ts, tabs) -> None:
-    """Forward mixing tables of up to 4 layers (lists of A [T,V,V], T [V,T,T], tab [ftab_floats()]) in one launch."""
+def _ftab_pointers(As, Ts, tabs, T, V):
+    """(A pointers, T pointers, table pointers, n) of up to 4 layers' forward mixing tables, checked"""
     n = len(As)
     if not (1 <= n <= 4) or len(Ts) != n or len(tabs) != n:
         raise ValueError("build_ftabs: 1..4 layers, equal list lengths")
-    T, V = As[0].shape[0], As[0].shape[1]
     nf = ftab_floats()
     for A, Tm, tab in zip(As, Ts, tabs):
         _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T)); _chk(tab, "tab", (nf,))
     arr = ctypes.c_void_p * n
-    call("coskad_build_ftab_f32", arr(*[t.data_ptr() for t in As]), arr(*[t.data_ptr() for t in Ts]),
-         arr(*[t.data_ptr() for t in tabs]), n, T, V, _stream())
+    return arr(*[t.data_ptr() for t in As]), arr(*[t.data_ptr() for t in Ts]), arr(*[t.data_ptr() for t in tabs]), n
+
+
+def build_ftabs(As, Ts, tabs) -> None:
+    """Forward mixing tables of up to 4 layers (lists of A [T,V,V], T [V,T,T], tab [ftab_floats()]) in one launch."""
+    T, V = (As[0].shape[0], As[0].shape[1]) if len(As) else (0, 0)
+    pa, pt, ptab, n = _ftab_pointers(As, Ts, tabs, T, V)
+    call("coskad_build_ftab_f32", pa, pt, ptab, n, T, V, _stream())
 
 
 def layer_apply_next(Z, x, wfold, bias, Co, in_slope, out_slope, ftab_next, partials, T, V, out=None, Z_next=None):
@@ -621,6 +634,54 @@ def btlnk_bwd_chain(U, W, dz, slope, dW, db, dslope, ws, below_in, below_Z, belo
     call("coskad_btlnk_bwd_chain_f32", U, W, dz, slope, dU, dW, db, dslope, buf, _bytes(buf), 1 if accumulate else 0, B, K, L, below_in,
          below_Z, below_in_slope, Ci, TV, stats, _bytes(stats), ctypes.byref(rows), _stream())
     return dU, (stats, rows.value)
+
+
+def btlnk_fwd_parts(U: Tensor, W: Tensor, slope: Optional[Tensor]) -> Tensor:
+    """The split-K partials [KS, B, 16] of btlnk_fwd's large-batch path without the launch that sums them (L <= 16, K % 16 == 0):
+    z = part.sum(0)[:, :L] + bias, in slice order, is left to btlnk_bwd_chain_head."""
+    B = U.shape[0]
+    K = U.numel() // B
+    L = W.shape[0]
+    _chk(U, "U"); _chk(W, "W", (L, K)); _chk(slope, "slope", (1,), optional=True)
+    part = torch.empty(_lib.lib().coskad_btlnk_fwd_ks(), B, 16, device=U.device, dtype=torch.float32)
+    call("coskad_btlnk_fwd_parts_f32", U, W, slope, part, _bytes(part), B, K, L, _stream())
+    return part
+
+
+def btlnk_bwd_chain_head(U, W, part, bias, c, slope, dW, db, dslope, ws, below_in, below_Z, below_in_slope, acc=None, need_score=False,
+                         upstream=1.0, dU=None, accumulate=False):
+    """btlnk_fwd's summing launch, mse_head and btlnk_bwd_chain in the launches of the last (csrc/btlnk_chain.hip, HD form): from the
+    partials of btlnk_fwd_parts, the Linear's bias and the centre c -> (z, dz, score or None, stats, dU, (chain buffer, rows)), every
+    value bit-identical to the three calls; acc (+)= the head's raw sums.  `ws`: an engine.Workspace."""
+    B, Ch, T, V = U.shape
+    TV = T * V
+    K = Ch * TV
+    L = W.shape[0]
+    Ci = below_in.shape[1]
+    KS = part.shape[0]
+    S = head_slots(L)
+    _chk(U, "U"); _chk(W, "W", (L, K)); _chk(part, "part", (KS, B, 16)); _chk(bias, "bias", (L,), optional=True); _chk(c, "c", (L,))
+    _chk(dW, "dW", (L, K)); _chk(db, "db", (L,), optional=True); _chk(dslope, "dslope", (1,), optional=True)
+    _chk(slope, "slope", (1,), optional=True); _chk(acc, "acc", (S,), optional=True)
+    _chk(below_in, "below_in", (B, Ci, T, V)); _chk(below_Z, "below_Z", (B, Ci, T, V)); _chk(below_in_slope, "below_in_slope", (1,), optional=True)
+    if not btlnk_bwd_chain_ok(K, TV, Ci):
+        raise ValueError(f"btlnk_bwd_chain_head: shape K={K} TV={TV} Ci={Ci} not supported")
+    lib = _lib.lib()
+    need = lib.coskad_btlnk_bwd_chain_ws_bytes(B, K, L, TV)
+    buf = ws.get(need, U.device)
+    chain = torch.empty(lib.coskad_btlnk_bwd_chain_floats(B, TV, Ci), device=U.device, dtype=torch.float32)
+    if dU is None:
+        dU = torch.empty_like(U)
+    z = torch.empty(B, L, device=U.device, dtype=torch.float32)
+    dz = torch.empty_like(z)
+    score = torch.empty(B, device=U.device, dtype=torch.float32) if need_score else None
+    stats = torch.empty(S, device=U.device, dtype=torch.float32)
+    hws = head_ws(B, U.device, L)
+    rows = ctypes.c_int(0)
+    call("coskad_btlnk_bwd_chain_head_f32", U, W, part, KS, bias, c, upstream, z, dz, score, stats, acc, hws, slope, dU, dW, db, dslope,
+         buf, _bytes(buf), 1 if accumulate else 0, B, K, L, below_in, below_Z, below_in_slope, Ci, TV, chain, _bytes(chain),
+         ctypes.byref(rows), _stream())
+    return z, dz, score, stats, dU, (chain, rows.value)
 
 
 def _cuda_f32(t: Tensor, name: str) -> None:

@@ -549,6 +549,16 @@ class _LinearProjector:
     def backward(self, W, dy, U, slope, ctx, top_layers, last_slope_grad):
         return engine.btlnk_backward(ctx, top_layers or [], U, W, dy, slope, self.gW, self.gb, last_slope_grad, self.ws)
 
+    def forward_parts(self, U: Tensor, slope):
+        """forward without the launch that sums the split-K partials -> (partials, saved): head_backward's input"""
+        W = self.lin.weight
+        return ops.btlnk_fwd_parts(U, W, slope), W
+
+    def head_backward(self, W, part, c, acc, U, slope, ctx, top_layers, last_slope_grad):
+        """the Euclidean head against centre c and `backward` from the partials in one pass -> (stats, dU, top_stats)"""
+        return engine.btlnk_head_backward(ctx, top_layers, U, W, part, self.lin.bias, c, slope, self.gW, self.gb, last_slope_grad,
+                                          self.ws, acc=acc)
+
 
 class _MLPProjector(_LinearProjector):
     """`mlp` projector (components.py:209-226): the wide first Linear on the bottleneck kernel, then every [BatchNorm1d, ReLU, Linear]
@@ -728,11 +738,18 @@ class STSETrainStep(_FlatStep, _OneClassHead):
     def _body(self, x: Tensor) -> Tensor:
         U, slope, saved_stack = self.stack.forward(x, self.ws)          # slope None: the stack ended in a wide layer (activated output)
         ctx, top_layers = self.stack.top(saved_stack)
-        z, saved = self.projector.forward(U, slope)
-        stats, dz = self._head(z)
-        # (the side-stream backward runs its own batch reductions: no ChainCtx, so the bottleneck's backward forms none)
-        dU, top_stats = self.projector.backward(saved, dz, U, slope, ctx if self.side is None else None, top_layers,
-                                                self.stack.last_slope_grad)
+        if (type(self.projector) is _LinearProjector and self.head == 'euclidean' and self.side is None
+                and engine.head_rides(ctx, top_layers or [], U, self.model.latent_dim)):
+            # the head rides in the bottleneck backward's launch, which forms dz from the forward's partials (engine.HEAD_RIDES)
+            part, saved = self.projector.forward_parts(U, slope)
+            stats, dU, top_stats = self.projector.head_backward(saved, part, self.model.c, self.center_acc, U, slope, ctx, top_layers,
+                                                                self.stack.last_slope_grad)
+        else:
+            z, saved = self.projector.forward(U, slope)
+            stats, dz = self._head(z)
+            # (the side-stream backward runs its own batch reductions: no ChainCtx, so the bottleneck's backward forms none)
+            dU, top_stats = self.projector.backward(saved, dz, U, slope, ctx if self.side is None else None, top_layers,
+                                                    self.stack.last_slope_grad)
         work = None
         if self.world > 1 and self.tail_off is not None:
             # bucket 1 (87 % of the bytes: the bottleneck weight) is complete now: its all-reduce runs on the collective

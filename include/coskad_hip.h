@@ -180,6 +180,19 @@ int coskad_ftab_floats(void);
 int coskad_layer_apply_next_rows(int B, int Ci, int Co);
 int coskad_build_ftab_f32(const float* const* A, const float* const* Tm, float* const* tab, int n, int T, int V,
                           hipStream_t stream);
+/* coskad_layer_train_stats_z_f32 of a stack's first layer (C_in <= 4, Z stored, T = 12, V = 17) with the tables of
+ * coskad_build_ftab_f32 (ntab <= 4 layers: tab[i] from tab_A[i], tab_Tm[i]) built by extra blocks of the statistics pass's launch:
+ * the moments depend on the clips only, the tables on parameters only, so neither waits for the other and one launch leaves the step. */
+int coskad_layer_train_stats_z_ftab_f32(const float* in, const float* A, const float* Tm, const float* in_slope,
+                                        const float* Wt, const float* bt, const float* gamma_t,
+                                        const float* beta_t, float* rmean_t, float* rvar_t, long long* nbt_t,
+                                        const float* Wr, const float* br, const float* gamma_r,
+                                        const float* beta_r, float* rmean_r, float* rvar_r, long long* nbt_r,
+                                        float momentum, float* wfold, float* bias, float* stat, void* ws,
+                                        size_t ws_bytes, int B, int Ci, int Co, int T, int V,
+                                        hipStream_t stream, float* Z, const float* const* tab_A, const float* const* tab_Tm,
+                                        float* const* tab, int ntab);
+
 int coskad_layer_apply_next_f32(const float* Z, const float* in, float* out, const float* wfold, const float* bias,
                                 const float* in_slope, const float* out_slope, const float* ftab_next, float* Z_next,
                                 float* partials, size_t partials_bytes, int B, int Ci, int Co, int T, int V,
@@ -454,6 +467,23 @@ int coskad_btlnk_bwd_chain_f32(const float* U, const float* W, const float* dz, 
                                float* db, float* dslope, void* ws, size_t ws_bytes, int accumulate, int B, int K, int L,
                                const float* below_in, const float* below_Z, const float* below_in_slope, int below_Ci, int TV,
                                float* stats_out, size_t stats_out_bytes, int* stats_rows, hipStream_t stream);
+
+/* The same with the Euclidean one-class head riding in the backward's launch (csrc/btlnk_chain.hip, HD form).  Instead of a finished
+ * dz the call takes the split-K partials part [KS][B][16] of coskad_btlnk_fwd_parts_f32 (KS = coskad_btlnk_fwd_ks(); the forward
+ * without its summing launch), the Linear's bias (or NULL), the centre c and `upstream`; the backward's workgroups form their
+ * tiles of dz = 2 (z - c) upstream / (B L), z = (sum of the slices, in order) + bias, on chip, and extra blocks of the same launch
+ * do the head: z, dz [B][L] written, score [B] / stats / acc as in coskad_mse_head_f32 (NULL to skip; head_ws:
+ * coskad_head_ws_floats(B) floats; above 512 clips the statistics are finished by one more block of the reduce launch).  Every
+ * value is bit-identical to coskad_btlnk_fwd_ws_f32 + coskad_mse_head_f32 + coskad_btlnk_bwd_chain_f32: three launches fewer. */
+int coskad_btlnk_fwd_ks(void);
+int coskad_btlnk_fwd_parts_f32(const float* U, const float* W, const float* slope, float* part, size_t part_bytes, int B, int K,
+                               int L, hipStream_t stream);
+int coskad_btlnk_bwd_chain_head_f32(const float* U, const float* W, const float* part, int KS, const float* bias, const float* c,
+                                    float upstream, float* z, float* dz, float* score, float* stats, float* acc, float* head_ws,
+                                    const float* slope, float* dU, float* dW, float* db, float* dslope, void* ws, size_t ws_bytes,
+                                    int accumulate, int B, int K, int L, const float* below_in, const float* below_Z,
+                                    const float* below_in_slope, int below_Ci, int TV, float* stats_out, size_t stats_out_bytes,
+                                    int* stats_rows, hipStream_t stream);
 
 /* ---- batch formation from the HBM-resident window table (callers' side of the path) ----- */
 
