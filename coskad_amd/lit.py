@@ -224,6 +224,9 @@ class LitEncoder(nn.Module):
         # `device_scoring` (not a key of the reference's yamls either): scores that live on the GPU are turned into the frame-level AUC
         # by the scoring kernels on a plan of the window table, built at the first call and reused while the table is the same one,
         # unless the yaml says `device_scoring: false` (then: eval_utils.score_dataset, as for scores on the host)
+        # `eval_report` (no key of the reference's yamls; off unless set): also the reference's per-clip AUCs, per-transformation AUCs
+        # and ROC thresholds, on the same route as the scoring, kept as `self.last_report`
+        report = bool(getattr(self.args, "eval_report", False))
         if bool(getattr(self.args, "device_scoring", True)) and torch.as_tensor(scores).is_cuda:
             plan = getattr(self, "_score_plan", None)
             if plan is None or plan.win_ptr.device != scores.device or not plan.same_setting(gts, num_transform, pad_size, hr_masks) \
@@ -231,7 +234,11 @@ class LitEncoder(nn.Module):
                 plan = eval_utils.ScorePlan(trans, meta, frames, gts, num_transform, pad_size=pad_size, hr_masks=hr_masks,
                                             device=scores.device)
                 object.__setattr__(self, "_score_plan", plan)      # not a submodule, not part of the state dict
-            auc, per_t_dev, gt = eval_utils.score_dataset_device(scores, plan)
+            if report:
+                self.last_report, per_t_dev, gt = eval_utils.score_report_device(scores, plan)
+                auc = self.last_report.auc
+            else:
+                auc, per_t_dev, gt = eval_utils.score_dataset_device(scores, plan)
             per_t_host = per_t_dev.cpu().numpy()                   # one device -> host copy
             per_t = {t: per_t_host[t] for t in range(num_transform)}
         else:
@@ -239,6 +246,12 @@ class LitEncoder(nn.Module):
                                                       smoothing=int(getattr(self.args, "smoothing", 50)),
                                                       dataname=getattr(self.args, "dataset_choice", "UBnormal"),
                                                       pad_size=pad_size, hr_masks=hr_masks)
+            if report:
+                keys, segments = eval_utils.clip_segments(gts, hr_masks)
+                self.last_report = eval_utils.score_report(per_t, gt, segments, keys)
+        if report:
+            defined = self.last_report.clip_auc_mean_t[~np.isnan(self.last_report.clip_auc_mean_t)]
+            self.log("validation_clip_auc_mean", defined.mean() if defined.size else float("nan"))
         self.log("validation_auc", auc)
         self.last_scores = per_t
         return auc

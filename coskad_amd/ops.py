@@ -1619,3 +1619,48 @@ def score_auc(sorted_scores, gt_sorted, cum_neg):
     ws = torch.empty(max(1, _lib.lib().coskad_score_auc_ws(F)), device=sorted_scores.device, dtype=torch.int64)
     call("coskad_score_auc_f64", sorted_scores, gt_sorted, cum_neg, out, ws, ws.numel(), F, _stream())
     return out
+
+
+# ---- the evaluation report (csrc/score_report.hip): per-segment AUCs and ROC thresholds of rows ordered by the caller ----
+
+REPORT_TILE = 256                   # elements per workgroup of the report kernels (coskad_score_report_tile())
+
+
+def score_report_auc(sorted_scores, gt_sorted, cum_neg, segments, tile_ptr, n_tiles, out=None):
+    """out [n_rows, n_seg, 3] float64 = {AUC, n_pos, n_neg} of every segment [start, end) (int32 [n_seg, 2], not overlapping) of every
+    row: sorted_scores [n_rows, F] ascending inside each segment, gt_sorted in that order (int32), cum_neg its inclusive count of
+    negatives along the row (int64); tile_ptr [n_seg + 1] int32 the running sum of the segments' tile counts, n_tiles >= its last entry.
+    Two launches whatever n_seg; AUC is NaN for a segment of one class or without frames."""
+    _chk(sorted_scores, "sorted_scores", dtype=torch.float64)
+    if sorted_scores.dim() != 2:
+        raise ValueError(f"sorted_scores: expected [n_rows, F], got {tuple(sorted_scores.shape)}")
+    R, F = sorted_scores.shape
+    _chk(gt_sorted, "gt_sorted", (R, F), dtype=torch.int32); _chk(cum_neg, "cum_neg", (R, F), dtype=torch.int64)
+    S = segments.shape[0]
+    _chk(segments, "segments", (S, 2), dtype=torch.int32); _chk(tile_ptr, "tile_ptr", (S + 1,), dtype=torch.int32)
+    if out is None:
+        out = torch.empty(R, S, 3, device=sorted_scores.device, dtype=torch.float64)
+    else:
+        _chk(out, "out", (R, S, 3), dtype=torch.float64)
+    ws = torch.empty(max(1, R * n_tiles), device=sorted_scores.device, dtype=torch.int64)
+    call("coskad_score_report_auc_f64", sorted_scores, gt_sorted, cum_neg, segments, tile_ptr, out, ws, ws.numel(), n_tiles, R, S, F,
+         _stream())
+    return out
+
+
+def score_report_thresholds(sorted_scores, cum_neg, out=None):
+    """out [n_rows, 3] float64 = {n, thr0, thr1}: the n thresholds (1 or 2; 0 for a single-class row) at which the ROC curve of each row
+    crosses tpr = 1 - fpr, as sklearn's roc_curve (drop_intermediate=True) and the reference's ROC() give them; sorted_scores [n_rows, F]
+    ascending along each row, cum_neg the inclusive count of negatives in that order (int64).  Two launches."""
+    _chk(sorted_scores, "sorted_scores", dtype=torch.float64)
+    if sorted_scores.dim() != 2:
+        raise ValueError(f"sorted_scores: expected [n_rows, F], got {tuple(sorted_scores.shape)}")
+    R, F = sorted_scores.shape
+    _chk(cum_neg, "cum_neg", (R, F), dtype=torch.int64)
+    if out is None:
+        out = torch.empty(R, 3, device=sorted_scores.device, dtype=torch.float64)
+    else:
+        _chk(out, "out", (R, 3), dtype=torch.float64)
+    ws = torch.empty(max(1, 2 * R * ((F + REPORT_TILE - 1) // REPORT_TILE)), device=sorted_scores.device, dtype=torch.int32)
+    call("coskad_score_report_thresholds_f64", sorted_scores, cum_neg, out, ws, ws.numel(), R, F, _stream())
+    return out

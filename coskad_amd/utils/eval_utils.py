@@ -17,9 +17,10 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 from scipy.ndimage import gaussian_filter1d
-from sklearn.metrics import roc_auc_score
+from sklearn.metrics import roc_auc_score, roc_curve
 
 from .score_plan import ScorePlan, auc_device, gaussian_taps, score_dataset_device   # noqa: F401  (the device route of score_dataset)
+from .score_plan import ScoreReport, check_segments, report_from_frame_scores, score_report_device   # noqa: F401  (the report)
 
 
 def score_process(score: np.ndarray, win_size: int = 50, dataname: str = 'STC', use_scaler: bool = False) -> np.ndarray:
@@ -189,3 +190,59 @@ def eval_loss_type(rec_loss_weight: float) -> str:
 def ROC(y_test, y_pred):
     """AUC (reference eval_utils.py:216-230 without the matplotlib plot)."""
     return roc_auc_score(y_test, y_pred)
+
+
+# ---- the evaluation report on the host: the reference's loops (eval_COSKAD.py:222-242), the yardstick of
+# ---- score_plan.score_report_device
+
+def roc_crossing_thresholds(y, s) -> np.ndarray:
+    """The first return value of the reference's ROC() (eval_utils.py:217-219,230): the thresholds of sklearn's roc_curve (its
+    defaults, so drop_intermediate=True) at which tpr - (1 - fpr) changes sign; one or two values, the first may be inf.  Empty for a
+    single-class ground truth, where the curve is not defined."""
+    y = np.asarray(y) != 0
+    if y.all() or not y.any():
+        return np.zeros(0, dtype=np.float64)
+    fpr, tpr, tr = roc_curve(y, np.asarray(s, dtype=np.float64))
+    idx = np.argwhere(np.diff(np.sign(tpr - (1 - fpr)))).flatten()
+    return np.asarray(tr[idx], dtype=np.float64)
+
+
+def _auc_or_nan(y: np.ndarray, s: np.ndarray) -> float:
+    """roc_auc_score, NaN where it is undefined: one class or no frame (sklearn raises there or, from 1.6 on, warns and returns NaN;
+    the reference swallows the exception and leaves the clip out of its average)."""
+    if y.size == 0 or y.all() or not y.any():
+        return float("nan")
+    return float(roc_auc_score(y, s))
+
+
+def clip_segments(gts: Dict[Tuple[int, int], np.ndarray], hr_masks: Optional[Dict[Tuple[int, int], np.ndarray]] = None):
+    """-> (sorted clip keys, segments [C, 2]): each clip's [start, end) in `score_dataset`'s concatenated, human-related-compacted
+    vectors."""
+    keys = sorted(gts.keys())
+    hr_masks = hr_masks or {}
+    n = [int(np.asarray(gts[k])[hr_masks[k]].shape[0]) if k in hr_masks else int(np.asarray(gts[k]).shape[0]) for k in keys]
+    ends = np.cumsum(n, dtype=np.int64)
+    return keys, np.stack([ends - n, ends], 1).reshape(-1, 2)
+
+
+def score_report(per_t, gt, segments, clip_keys) -> ScoreReport:
+    """The report as the reference forms it: one roc_auc_score per (transformation, clip), one roc_curve per transformation, in Python
+    loops.  per_t: {t: scores [F]} as `score_dataset` returns it, or an array [nt, F]; gt [F] (non-zero = positive); segments [C, 2]."""
+    rows = np.stack([np.asarray(per_t[t], dtype=np.float64) for t in sorted(per_t)], 0) if isinstance(per_t, dict) \
+        else np.asarray(_host_array(per_t), dtype=np.float64)
+    nt, F = rows.shape
+    y = np.asarray(gt).reshape(-1) != 0
+    seg = check_segments(segments, F)
+    if y.shape[0] != F or seg.shape[0] != len(clip_keys):
+        raise ValueError(f"score_report: {F} frames, gt of {y.shape[0]}, {seg.shape[0]} segments for {len(clip_keys)} clips")
+    pds = np.mean(rows, 0)
+    clip_auc = np.array([[_auc_or_nan(y[a:b], rows[t, a:b]) for a, b in seg.tolist()] for t in range(nt)]).reshape(nt, -1)
+    return ScoreReport(auc=roc_auc_score(y, pds), auc_t=[roc_auc_score(y, rows[t]) for t in range(nt)],
+                       thresholds_t=[roc_crossing_thresholds(y, rows[t]) for t in range(nt)], clip_auc=clip_auc,
+                       clip_auc_final=[_auc_or_nan(y[a:b], pds[a:b]) for a, b in seg.tolist()], clip_keys=clip_keys,
+                       n_pos=[int(y[a:b].sum()) for a, b in seg.tolist()], n_neg=[int((~y[a:b]).sum()) for a, b in seg.tolist()],
+                       segments=seg, frame_scores=pds)
+
+
+def _host_array(t):
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t

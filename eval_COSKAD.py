@@ -7,6 +7,7 @@ import os
 import torch
 import yaml
 
+from coskad_amd import parallel
 from coskad_amd.lit import LitEncoder, Trainer
 from coskad_amd.utils.argparser import init_sub_args
 from coskad_amd.utils.synthetic import batches, make_dataset
@@ -15,7 +16,13 @@ from coskad_amd.utils.synthetic import batches, make_dataset
 def main():
     parser = argparse.ArgumentParser(description='Pose_AD_Experiment')
     parser.add_argument('-c', '--config', type=str, required=True)
-    args = argparse.Namespace(**yaml.load(open(parser.parse_args().config), Loader=yaml.FullLoader))
+    # the reference's per-clip / per-transformation log (eval_COSKAD.py:222-242); the yaml key `eval_report: true` asks for the same
+    parser.add_argument('--report', action='store_true')
+    parser.add_argument('--report-dir', type=str, default=None)      # report.json + <scene>_<clip>.npy (implies --report)
+    cli = parser.parse_args()
+    args = argparse.Namespace(**yaml.load(open(cli.config), Loader=yaml.FullLoader))
+    if cli.report or cli.report_dir:
+        args.eval_report = True
     args, dataset_args, ae_args, res_args, opt_args = init_sub_args(args)
     torch.cuda.set_device(0)
     if args.use_decoder:                             # wrapper selection order: eval_COSKAD.py:55-83
@@ -44,6 +51,12 @@ def main():
         _, loader = get_dataset_and_loader(dataset_args, split=args.split)
         out = trainer.predict(model, lambda: loader, ckpt_path=path)
     auc = model.validation_epoch_end(out)
+    report = getattr(model, 'last_report', None)
+    if report is not None and parallel.rank() == 0:
+        for line in list(report.lines())[:-1]:      # its last line is the one below
+            print(line)
+        if cli.report_dir:
+            report.save(cli.report_dir)
     print('final AUC score: {}'.format(auc))
 
 

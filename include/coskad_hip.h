@@ -521,6 +521,28 @@ int coskad_score_smooth_f64(const double* raw, const int* tiles, const double* t
 int coskad_score_auc_f64(const double* sorted_scores, const int* gt_sorted, const long long* cum_neg, double* out, long long* ws,
                          size_t ws_elems, int F, hipStream_t stream);
 
+/* ---- the evaluation report: per-segment AUCs and ROC thresholds (csrc/score_report.hip) ------------------------------- */
+
+/* The AUC of every segment of every row, and per row the thresholds where its ROC curve crosses tpr = 1 - fpr (eval_COSKAD.py:222-242,
+ * utils/eval_utils.py:216-230).  Rows are [n_rows, F]; fp64 comparisons, integer counts, no floating-point atomics: deterministic.
+ *   auc       : segments: n_seg rows {start, end} that do not overlap, each inside [0, F]; sorted_scores ascending inside every
+ *               segment, gt_sorted the ground truth in that order, cum_neg its inclusive count of negatives along the whole row;
+ *               tile_ptr [n_seg + 1]: the running sum of ceil((end - start) / coskad_score_report_tile()), n_tiles >= tile_ptr[n_seg]
+ *               the launch's tile count (at most F / tile + n_seg); out [n_rows, n_seg, 3] = {AUC, n_pos, n_neg}, the statistic and
+ *               the quotient formed as coskad_score_auc_f64 forms them (AUC NaN for one class or no frame; {NaN, -1, -1} for a
+ *               segment outside [0, F] or a tile_ptr that does not match it); ws: coskad_score_report_auc_ws(n_rows, n_tiles) elements
+ *   thresholds: sorted_scores ascending along each row of F; out [n_rows, 3] = {n, thr0, thr1}: the n = 1 or 2 values
+ *               tr[np.argwhere(np.diff(np.sign(tpr - (1 - fpr))))] of sklearn's roc_curve(drop_intermediate=True), thr0 may be +inf;
+ *               n = 0 for a single-class row; ws: coskad_score_report_thr_ws(n_rows, F) elements */
+int coskad_score_report_tile(void);
+long long coskad_score_report_auc_ws(int n_rows, int n_tiles);
+long long coskad_score_report_thr_ws(int n_rows, int F);
+int coskad_score_report_auc_f64(const double* sorted_scores, const int* gt_sorted, const long long* cum_neg, const int* segments,
+                                const int* tile_ptr, double* out, long long* ws, size_t ws_elems, int n_tiles, int n_rows, int n_seg,
+                                int F, hipStream_t stream);
+int coskad_score_report_thresholds_f64(const double* sorted_scores, const long long* cum_neg, double* out, int* ws, size_t ws_elems,
+                                       int n_rows, int F, hipStream_t stream);
+
 /* ---- one-class heads, centre statistics, regulariser, optimiser ------------------------ */
 
 int coskad_head_slots(void);            /* floats in a stats / acc block (19) at latent <= 16 */
