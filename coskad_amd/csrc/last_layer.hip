@@ -149,6 +149,8 @@ int coskad_narrow_conv_rows(int B, int TV) { return (B > 0 && TV > 0 && TV % 4 =
 int coskad_narrow_conv_fwd_f32(const float* U, const float* in_slope, const float* W, float* out, int B, int Ci, int J, int TV,
                                hipStream_t stream) {
   if (!U || !W || !out) return fail(COSKAD_ERR_ARG, "narrow_conv_fwd: null pointer");
+  if ((size_t)U & 15) return fail(COSKAD_ERR_ARG, "narrow_conv_fwd: `U` (%p) must be 16-byte aligned", (const void*)U);
+  if ((size_t)out & 15) return fail(COSKAD_ERR_ARG, "narrow_conv_fwd: `out` (%p) must be 16-byte aligned", (const void*)out);
   if (B <= 0 || Ci <= 0 || Ci > nl::CMAX || TV <= 0 || TV % 4 || (J != 2 && J != 4 && J != 6 && J != 8))
     return fail(COSKAD_ERR_SHAPE, "narrow_conv_fwd: B=%d Ci=%d J=%d TV=%d (J in {2, 4, 6, 8}, Ci <= 64, TV %% 4 == 0)", B, Ci, J, TV);
   const int R4 = TV / 4, grid = nl::grid_for(B, R4);
@@ -164,6 +166,9 @@ int coskad_narrow_conv_fwd_f32(const float* U, const float* in_slope, const floa
 int coskad_narrow_conv_bwd_f32(const float* U, const float* in_slope, const float* W, const float* dOut, float* dU, float* partials,
                                size_t partials_floats, int B, int Ci, int J, int TV, hipStream_t stream) {
   if (!U || !W || !dOut || !dU || !partials) return fail(COSKAD_ERR_ARG, "narrow_conv_bwd: null pointer");
+  if ((size_t)U & 15) return fail(COSKAD_ERR_ARG, "narrow_conv_bwd: `U` (%p) must be 16-byte aligned", (const void*)U);
+  if ((size_t)dOut & 15) return fail(COSKAD_ERR_ARG, "narrow_conv_bwd: `dOut` (%p) must be 16-byte aligned", (const void*)dOut);
+  if ((size_t)dU & 15) return fail(COSKAD_ERR_ARG, "narrow_conv_bwd: `dU` (%p) must be 16-byte aligned", (const void*)dU);
   if (B <= 0 || Ci <= 0 || Ci > nl::CMAX || TV <= 0 || TV % 4 || (J != 2 && J != 4 && J != 6 && J != 8))
     return fail(COSKAD_ERR_SHAPE, "narrow_conv_bwd: B=%d Ci=%d J=%d TV=%d (J in {2, 4, 6, 8}, Ci <= 64, TV %% 4 == 0)", B, Ci, J, TV);
   const int R4 = TV / 4, grid = nl::grid_for(B, R4);

@@ -336,6 +336,8 @@ int coskad_gcn_f32(const float* in, float* out, const float* A, const float* Tm,
 
 int coskad_prelu_fwd_f32(const float* u, const float* slope, float* out, size_t n, hipStream_t stream) {
   if (!u || !slope || !out || n == 0) return fail(COSKAD_ERR_ARG, "prelu_fwd: bad argument");
+  if ((size_t)u & 15) return fail(COSKAD_ERR_ARG, "prelu_fwd: `u` (%p) must be 16-byte aligned", (const void*)u);
+  if ((size_t)out & 15) return fail(COSKAD_ERR_ARG, "prelu_fwd: `out` (%p) must be 16-byte aligned", (const void*)out);
   const size_t n4 = n / 4;
   const unsigned grid = (unsigned)((n4 + 255) / 256 > 0 ? (n4 + 255) / 256 : 1);
   hipLaunchKernelGGL(k_prelu_fwd, dim3(grid), dim3(256), 0, stream, u, slope, out, n4, n);

@@ -84,7 +84,8 @@ int coskad_layer_tail_f32(const float* in, const float* x, float* out, float* sc
 
 /* nn.PReLU() with one shared weight (stsgcn.py:82,110), elementwise, for API paths that must
  * materialise the post-activation tensor.  bwd: du = dout * PReLU'(u); dslope (+)= sum dout*u [u<0];
- * ws >= 1024 floats. */
+ * ws >= 1024 floats.  fwd moves 16-byte vectors: u and out must be 16-byte aligned (COSKAD_ERR_ARG naming the pointer otherwise,
+ * before anything is launched). */
 int coskad_prelu_fwd_f32(const float* u, const float* slope, float* out, size_t n, hipStream_t stream);
 int coskad_prelu_bwd_f32(const float* u, const float* dout, const float* slope, float* du, float* dslope,
                          float* ws, int accumulate, size_t n, hipStream_t stream);
@@ -602,7 +603,9 @@ int coskad_lowrank_fold_bwd_f32(const float* X, const double* G, const float* dM
  * PReLU see 2 C_out-channel tensors (csrc/last_layer.hip).
  *   fwd : out [B, J, TV] = W [J, Ci] . PReLU(U [B, Ci, TV])   (in_slope NULL: U is activated already); J = 2 C_out in {2, 4, 6, 8}
  *   bwd : dU [B, Ci, TV] = (W^T dOut) * PReLU'(U); partials [coskad_narrow_conv_rows(B, TV)][J Ci + 1]: per-workgroup sums of
- *         dW[j][c] = sum dOut_j PReLU(U)_c and, last column, of the producer's slope gradient -- add the rows with coskad_gemm_sum_f32 */
+ *         dW[j][c] = sum dOut_j PReLU(U)_c and, last column, of the producer's slope gradient -- add the rows with coskad_gemm_sum_f32
+ * Both passes move 16-byte vectors: U, out, dOut and dU must be 16-byte aligned (COSKAD_ERR_ARG naming the pointer otherwise, before
+ * anything is launched). */
 int coskad_narrow_conv_rows(int B, int TV);
 int coskad_narrow_conv_fwd_f32(const float* U, const float* in_slope, const float* W, float* out, int B, int Ci, int J, int TV,
                                hipStream_t stream);

@@ -1,0 +1,186 @@
+"""The float64 references of kernel_refs.py against torch.nn / torch.optim on the CPU, before a device sees them: what the GPU
+kernel tests (test_gpu_wide_kernels.py, test_gpu_narrow_conv.py, test_gpu_flat_kernels.py) compare with is shown right here.  Also
+the Python twin of the dropout hash (its keep rate; the numpy form against the integer form) and the share of elements the
+apply / backward test leaves out at the PReLU kink, from the reference alone.  No kernel runs."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import kernel_refs as R
+import test_gpu_wide_kernels as W
+
+RTOL = 1e-11          # both sides are double: what is left is the order of summation
+
+
+def _close(a, b, name):
+    a, b = a.detach().numpy(), b.detach().numpy()
+    np.testing.assert_allclose(a, b, rtol=RTOL, atol=RTOL * max(1.0, float(np.abs(b).max())), err_msg=name)
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("residual_bn", [True, False])
+def test_bn2_block_is_batchnorm_add_prelu(training, residual_bn):
+    """kernel_refs.bn2_block == nn.BatchNorm2d -> add -> nn.PReLU in double, outputs, every gradient and the running statistics"""
+    g = torch.Generator().manual_seed(3 + int(training) + 2 * int(residual_bn))
+    Nb, C, P, eps, mom = 6, 5, 11, 1e-5, 0.1
+    Ct = (torch.randn(Nb, C, P, generator=g, dtype=torch.float64) * 1.7 + 0.6).requires_grad_(True)
+    Cr = torch.randn(Nb, C, P, generator=g, dtype=torch.float64).requires_grad_(True)
+    dOut = torch.randn(Nb, C, P, generator=g, dtype=torch.float64)
+    bns = []
+    for _ in range(2):
+        bn = torch.nn.BatchNorm2d(C, eps=eps, momentum=mom).double()
+        with torch.no_grad():
+            bn.weight.copy_(torch.randn(C, generator=g)); bn.bias.copy_(torch.randn(C, generator=g))
+            bn.running_mean.copy_(torch.randn(C, generator=g)); bn.running_var.copy_(torch.rand(C, generator=g) + 0.5)
+        bns.append(bn.train(training))
+    act = torch.nn.PReLU(init=0.1).double()
+    rm0 = [bn.running_mean.clone() for bn in bns]
+    rv0 = [bn.running_var.clone() for bn in bns]
+
+    yr = bns[1](Cr[..., None]) if residual_bn else Cr[..., None]
+    want = act(bns[0](Ct[..., None]) + yr)[..., 0]
+    wp = [Ct, Cr, bns[0].weight, bns[0].bias, act.weight] + ([bns[1].weight, bns[1].bias] if residual_bn else [])
+    wgrads = torch.autograd.grad(want, wp, dOut)
+
+    leaf = lambda t: t.detach().clone().requires_grad_(True)
+    t = dict(gamma=leaf(bns[0].weight), beta=leaf(bns[0].bias), running_mean=rm0[0], running_var=rv0[0])
+    r = dict(gamma=leaf(bns[1].weight), beta=leaf(bns[1].bias), running_mean=rm0[1], running_var=rv0[1]) if residual_bn else None
+    Ct2, Cr2, a2 = leaf(Ct), leaf(Cr), leaf(act.weight)
+    got, u, (mean_t, inv_t), sr = R.bn2_block(Ct2, Cr2, t, r, a2, eps, training)
+    gp = [Ct2, Cr2, t["gamma"], t["beta"], a2] + ([r["gamma"], r["beta"]] if residual_bn else [])
+    ggrads = torch.autograd.grad(got, gp, dOut)
+    _close(got, want, "out")
+    assert torch.equal(R.prelu(u, a2), got)
+    for k, (a, b) in enumerate(zip(ggrads, wgrads)):
+        _close(a.reshape(-1), b.reshape(-1), f"grad {k}")
+    for k, (x, bn) in enumerate(((Ct, bns[0]), (Cr, bns[1]))[:2 if residual_bn else 1]):
+        if training:
+            mean, var, inv = R.bn_batch_stats(x.detach(), eps)
+            rm, rv = R.bn_running_update(mean, var, Nb * P, rm0[k], rv0[k], mom)
+            _close(rm, bn.running_mean, "running_mean"); _close(rv, bn.running_var, "running_var")
+            assert int(bn.num_batches_tracked) == 1
+            if k == 0:
+                _close(mean, mean_t, "mean"); _close(inv, inv_t, "invstd")
+        else:
+            assert torch.equal(bn.running_mean, rm0[k]) and torch.equal(bn.running_var, rv0[k]) and int(bn.num_batches_tracked) == 0
+            if k == 0:
+                assert torch.equal(mean_t, rm0[0])
+                _close(inv_t, 1.0 / torch.sqrt(rv0[0] + eps), "invstd")
+
+
+def test_bn2_block_mask_and_single_count():
+    """the mask multiplies the tcn branch's BatchNorm output (nn.Dropout's place, stsgcn.py:66); a count of 1 keeps the biased variance
+    in the running update (the `count > 1` guard)"""
+    g = torch.Generator().manual_seed(11)
+    Nb, C, P, eps = 4, 3, 9, 1e-5
+    Ct, Cr = torch.randn(Nb, C, P, generator=g, dtype=torch.float64), torch.randn(Nb, C, P, generator=g, dtype=torch.float64)
+    mask = (torch.rand(Nb, C, P, generator=g) < 0.75).double() / 0.75
+    t = dict(gamma=torch.randn(C, generator=g, dtype=torch.float64), beta=torch.randn(C, generator=g, dtype=torch.float64))
+    got, _, _, _ = R.bn2_block(Ct, Cr, t, None, 0.1, eps, True, mask)
+    want = F.prelu(mask * F.batch_norm(Ct, None, None, t["gamma"], t["beta"], True, 0.0, eps) + Cr, torch.tensor([0.1], dtype=torch.float64))
+    _close(got, want, "masked")
+    x = torch.tensor([[[2.5]]], dtype=torch.float64)
+    mean, var, inv = R.bn_batch_stats(x, eps)
+    rm, rv = R.bn_running_update(mean, var, 1, torch.tensor([1.0]), torch.tensor([2.0]), 0.1)
+    assert float(var) == 0.0 and float(rm) == pytest.approx(0.9 + 0.25) and float(rv) == pytest.approx(1.8)
+
+
+@pytest.mark.parametrize("pre", [True, False])
+def test_narrow_conv_is_conv2d_of_prelu(pre):
+    """kernel_refs.narrow_conv == F.conv2d(F.prelu(U), W[:, :, None, None]) with its gradients, exact +0.0 / -0.0 in U included (the
+    derivative at zero is the slope's side in both)"""
+    g = torch.Generator().manual_seed(5)
+    B, Ci, J, T, V = 3, 5, 4, 2, 7
+    U = torch.randn(B, Ci, T, V, generator=g, dtype=torch.float64)
+    U.view(-1)[0], U.view(-1)[1], U.view(-1)[17] = 0.0, -0.0, 0.0
+    Wm = torch.randn(J, Ci, generator=g, dtype=torch.float64)
+    dOut = torch.randn(B, J, T, V, generator=g, dtype=torch.float64)
+    res = []
+    for ref in (True, False):
+        u, w, a = U.clone().requires_grad_(True), Wm.clone().requires_grad_(True), torch.tensor([0.2], dtype=torch.float64, requires_grad=True)
+        if ref:
+            out = R.narrow_conv(u.view(B, Ci, T * V), a if pre else None, w).view(B, J, T, V)
+        else:
+            out = F.conv2d(F.prelu(u, a) if pre else u, w[:, :, None, None])
+        res.append((out,) + torch.autograd.grad(out, [u, w] + ([a] if pre else []), dOut))
+    for k, (x, y) in enumerate(zip(*res)):
+        _close(x.reshape(-1), y.reshape(-1), f"narrow {k}")
+    if pre:
+        assert float(res[0][1].view(-1)[0]) == float(res[1][1].view(-1)[0]) != 0.0
+
+
+def test_rec_head_is_mse_of_prelu():
+    g = torch.Generator().manual_seed(6)
+    U, x = torch.randn(50, generator=g, dtype=torch.float64), torch.randn(50, generator=g, dtype=torch.float64)
+    a = torch.tensor([0.15], dtype=torch.float64)
+    assert float(R.rec_head(U, x, a)) == pytest.approx(float(F.mse_loss(F.prelu(U, a), x)), rel=1e-13)
+
+
+def test_adam_step_is_torch_adam():
+    """kernel_refs.adam_step == torch.optim.Adam in double over five steps; with the regulariser folded in, torch gets the folded
+    gradient g gscale + reg_coef mask p"""
+    g = torch.Generator().manual_seed(7)
+    n, lr, b1, b2, eps = 40, 1e-3, 0.9, 0.999, 1e-8
+    for mask, gscale, reg in ((None, 1.0, 0.0), ((torch.rand(n, generator=g) < 0.5).double().numpy(), 0.5, 1e-3)):
+        p_t = torch.randn(n, generator=g, dtype=torch.float64).requires_grad_(True)
+        opt = torch.optim.Adam([p_t], lr=lr, betas=(b1, b2), eps=eps)
+        p, m, v = p_t.detach().numpy().copy(), np.zeros(n), np.zeros(n)
+        for t in range(1, 6):
+            grad = torch.randn(n, generator=g, dtype=torch.float64)
+            folded = grad * gscale + reg * (torch.from_numpy(mask) if mask is not None else 1.0) * p_t.detach()
+            p_t.grad = folded.clone()
+            opt.step()
+            p, m, v = R.adam_step(p, grad.numpy(), m, v, t, lr, b1, b2, eps, mask, gscale, reg)
+            np.testing.assert_allclose(p, p_t.detach().numpy(), rtol=1e-12, atol=1e-14)
+            st = opt.state[p_t]
+            np.testing.assert_allclose(m, st["exp_avg"].numpy(), rtol=1e-12, atol=1e-16)
+            np.testing.assert_allclose(v, st["exp_avg_sq"].numpy(), rtol=1e-12, atol=1e-18)
+
+
+def test_gather_transform_reference_is_the_einsum():
+    """kernel_refs.gather_transform_f32 on valid indices against the reference formula einsum('ktv,ck->ctv', (x, y, 1), M) in double"""
+    rng = np.random.default_rng(0)
+    N, ntrans, TV = 4, 3, 6
+    xy, mats = rng.standard_normal((N, 2, TV)).astype(np.float32), rng.standard_normal((ntrans, 3, 3)).astype(np.float32)
+    idx = [0, 5, N * ntrans - 1, -1, N * ntrans]
+    got = R.gather_transform_f32(xy, mats, idx, N, ntrans)
+    for b, i in enumerate(idx):
+        if i < 0 or i // N >= ntrans:
+            assert not got[b].any()
+            continue
+        h = np.concatenate([xy[i % N].astype(np.float64), np.ones((1, TV))])
+        want = np.einsum("kp,ck->cp", h, mats[i // N].astype(np.float64))[:2]
+        M = np.abs(mats[i // N, :2]).astype(np.float64) @ np.abs(h)          # two products, two adds: k = 4 at most
+        assert np.all(np.abs(got[b] - want) <= 4 * R.U32 * M)
+
+
+@pytest.mark.parametrize("seed", R.DROP_SEEDS)
+@pytest.mark.parametrize("p", [0.25, 0.5])
+def test_dropout_twin_keep_rate(p, seed):
+    """the share of kept elements is within 3 sigma of 1 - p at the size and seeds of the GPU test; kept values are 1 / (1 - p) in
+    float32; p = 0 keeps everything"""
+    n = 70_000
+    m = R.drop_mask_twin(n, p, seed)
+    kept = float((m > 0).mean())
+    assert abs(kept - (1 - p)) <= 3 * np.sqrt(p * (1 - p) / n), kept
+    assert set(np.unique(m)) == {np.float32(0), np.float32(1) / (np.float32(1) - np.float32(p))}
+    assert np.array_equal(R.drop_mask_twin_np(n, p, seed), m)
+    assert np.array_equal(R.drop_mask_twin(100, 0.0, seed), np.ones(100, np.float32))
+
+
+@pytest.mark.parametrize("Nb,C,P", W.APPLY_SHAPES)
+def test_kink_share_of_the_reference_alone(Nb, C, P):
+    """the apply / backward test leaves out the elements whose double u lies within the float32 rounding bound of zero; with the
+    reference's own u their share is far below the test's cap of 1e-3 at every shape and configuration it runs (the dropout cases with
+    the twin's mask at the case's seed, whose keep rate is within 3 sigma of 0.75)"""
+    for residual_bn in (True, False):
+        for training, drop_p in ((True, 0.0), (True, 0.25), (False, 0.0)):
+            def mask_fn(shape, p, seed):
+                m = R.drop_mask_twin_np(int(np.prod(shape)), p, seed)
+                assert abs(float((m > 0).mean()) - (1 - p)) <= 3 * np.sqrt(p * (1 - p) / m.size)
+                return torch.from_numpy(m).view(shape)
+            k = W._apply_case(Nb, C, P, residual_bn, training, drop_p, mask_fn)
+            share = float(k["kink"].double().mean())
+            assert share <= 1e-3, (residual_bn, training, drop_p, share)
+            assert torch.isfinite(k["out_ref"]).all() and all(torch.isfinite(g).all() for g in k["grads"].values())
