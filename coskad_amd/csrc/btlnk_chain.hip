@@ -453,12 +453,8 @@ static int btlnk_bwd_chain_run(const float* U, const float* W, const float* dz, 
   {
   ProbeScope probe(KID_BTLNK_BWD, below_Ci, L, stream);
 #define BC_LAUNCH(CT_, HD_)                                                                                                          \
-  do {                                                                                                                               \
-    auto k = bc::k_btlnk_bwd_stats<CT_, HD_>;                                                                                        \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(bc::kThreads), lds, stream, U, W, dz, slope, dU, dWp, dap, below_in, below_Z,             \
-                       below_in_slope, stats_out, B, TV, L, p.chunk, ride);                                                          \
-  } while (0)
+  rc = launch_lds<bc::k_btlnk_bwd_stats<CT_, HD_>>("btlnk_bwd_stats", dim3(grid), dim3(bc::kThreads), lds, stream, U, W, dz, slope, dU, \
+                                                   dWp, dap, below_in, below_Z, below_in_slope, stats_out, B, TV, L, p.chunk, ride)
   if (below_Ci == 32) {
     if (hr) BC_LAUNCH(2, true); else BC_LAUNCH(2, false);
   } else {
@@ -466,7 +462,7 @@ static int btlnk_bwd_chain_run(const float* U, const float* W, const float* dz, 
   }
 #undef BC_LAUNCH
   }
-  if ((rc = check_launch("btlnk_bwd_stats"))) return rc;
+  if (rc) return rc;
   // one launch sums the dW slabs, the bias / slope gradients and the chain buffer's partial rows (and, behind the riding head's
   // blocks, their partial rows: k_head_finalize's sums)
   *stats_rows = rows;

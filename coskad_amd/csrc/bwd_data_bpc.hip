@@ -534,16 +534,13 @@ int launch_bwd_data_bpc(const float* in, const float* Zg, const float* dU, const
   const size_t lds = (size_t)(16 * bd::window_stride(12 * V) + 32 * (12 * V + 2) + (gpart && Ci == 32 ? V * 12 * 12 : 0)) * sizeof(float);
   const int grid = B < 512 ? B : 512;
   *rows_out = grid;
-#define LAUNCH_BD(CT, OT)                                                                                        \
-  do {                                                                                                           \
-    if (gpart && lds > 64 * 1024)                                                                                \
-      (void)hipFuncSetAttribute((const void*)bd::k_bwd_data_bpc<V, CT, OT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (gpart)                                                                                                   \
-      hipLaunchKernelGGL((bd::k_bwd_data_bpc<V, CT, OT, true>), dim3(grid), dim3(256), lds, st, in, Zg, dU, Aw, Tw, coef, in_slope, \
-                         dIn, dZout, dap, B, gpart);                                                             \
-    else                                                                                                         \
-      hipLaunchKernelGGL((bd::k_bwd_data_bpc<V, CT, OT, false>), dim3(grid), dim3(256), lds, st, in, Zg, dU, Aw, Tw, coef, in_slope, \
-                         dIn, dZout, dap, B, gpart);                                                             \
+#define LAUNCH_BD_G(CT, OT, G)                                                                                                  \
+  return launch_lds<bd::k_bwd_data_bpc<V, CT, OT, G>>("bwd_data_bpc", dim3(grid), dim3(256), lds, st, in, Zg, dU, Aw, Tw, coef, in_slope, \
+                                                      dIn, dZout, dap, B, gpart)
+#define LAUNCH_BD(CT, OT)                         \
+  do {                                            \
+    if (gpart) LAUNCH_BD_G(CT, OT, true);         \
+    else LAUNCH_BD_G(CT, OT, false);              \
   } while (0)
   if (Ci == 16 && Co == 16) LAUNCH_BD(1, 1);
   else if (Ci == 16 && Co == 32) LAUNCH_BD(1, 2);
@@ -552,7 +549,7 @@ int launch_bwd_data_bpc(const float* in, const float* Zg, const float* dU, const
   else if (Ci == 32 && Co == 32) LAUNCH_BD(2, 2);
   else LAUNCH_BD(2, 4);
 #undef LAUNCH_BD
-  return check_launch("bwd_data_bpc");
+#undef LAUNCH_BD_G
 }
 
 }  // namespace coskad

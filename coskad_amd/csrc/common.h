@@ -1,9 +1,11 @@
 // Shared host/device helpers for the COSKAD gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 
 #define COSKAD_ABI_VERSION 1
 
@@ -56,6 +58,37 @@ struct ProbeScope {   // brackets ONE kernel launch with events when the probe i
   hipStream_t st_;
   bool armed_ = false;
 };
+
+// The launch of every kernel whose dynamic LDS can exceed 64 KB: refuses a size above kMaxLdsBytes, raises the kernel's
+// dynamic-LDS limit where it has to, launches, checks the launch.  The limit is a per-device attribute of the kernel and the
+// same kernel is launched with sizes that follow the batch, so each kernel (a template argument: one static per instantiation,
+// no table keyed by pointer) keeps the largest size it was granted per device ordinal and sets the attribute only for a
+// request above it.  Below the mark that is one hipGetDevice and one relaxed load; the rare raise is serialised so that mark
+// and attribute cannot part.  An ordinal beyond the array sets the attribute every time.
+template <auto Kernel>
+int raise_lds_limit(const char* what, size_t lds) {
+  constexpr int kDevices = 16;
+  static std::atomic<size_t> granted[kDevices];
+  static std::mutex raising;
+  int dev = -1;
+  (void)hipGetDevice(&dev);
+  const bool tracked = dev >= 0 && dev < kDevices;
+  if (tracked && granted[dev].load(std::memory_order_relaxed) >= lds) return COSKAD_OK;
+  std::lock_guard<std::mutex> lock(raising);
+  if (tracked && granted[dev].load(std::memory_order_relaxed) >= lds) return COSKAD_OK;
+  if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(COSKAD_ERR_LAUNCH, "%s: %zu B of LDS refused", what, lds);
+  if (tracked) granted[dev].store(lds, std::memory_order_relaxed);
+  return COSKAD_OK;
+}
+template <auto Kernel, class... Args>
+int launch_lds(const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "%s: LDS %zu too large", what, lds);
+  if (lds > 64 * 1024)
+    if (int rc = raise_lds_limit<Kernel>(what, lds)) return rc;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  return check_launch(what);
+}
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }

@@ -726,16 +726,13 @@ int coskad_commute_bwd_f32(const float* u_prev, const float* in_slope, const flo
   hipLaunchKernelGGL(cm::k_commute_bfold, dim3(1), dim3(1024), 0, stream, spart, srow, (double)B * TV, stat, coef, dgamma_t, dbeta_t,
                      dgamma_r, dbeta_r);
   if ((rc = check_launch("commute_bfold"))) return rc;
-#define LAUNCH_CB(V__)                                                                                                          \
-  do {                                                                                                                          \
-    auto k = below_stats ? cm::k_commute_bwd<V__, true> : cm::k_commute_bwd<V__, false>;                                        \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cm::Geo<V__>::bwd_lds);          \
-    hipLaunchKernelGGL(k, dim3(prow), dim3(256), cm::Geo<V__>::bwd_lds, stream, u_prev, YR, Zy, dU, coef, wt, wr, A, Tm, in_slope, d_in, \
-                       gpart, wpart, B, below_z, below_x, below_stats);                                                         \
-  } while (0)
-  if (V == 17) LAUNCH_CB(17); else LAUNCH_CB(25);
+#define LAUNCH_CB(V__, BELOW)                                                                                                    \
+  rc = launch_lds<cm::k_commute_bwd<V__, BELOW>>("commute_bwd", dim3(prow), dim3(256), cm::Geo<V__>::bwd_lds, stream, u_prev, YR, Zy, dU, \
+                                                 coef, wt, wr, A, Tm, in_slope, d_in, gpart, wpart, B, below_z, below_x, below_stats)
+  if (V == 17) { if (below_stats) LAUNCH_CB(17, true); else LAUNCH_CB(17, false); }
+  else { if (below_stats) LAUNCH_CB(25, true); else LAUNCH_CB(25, false); }
 #undef LAUNCH_CB
-  if ((rc = check_launch("commute_bwd"))) return rc;
+  if (rc) return rc;
   const int nblk = ceil_div(nA + nT, cm::kRedCols) + ceil_div(1025, cm::kRedCols) + (below_stats ? ceil_div(cm::kBelowCols, cm::kRedCols) : 0);
   double* bout = below_stats ? reinterpret_cast<double*>(below_stats + ((size_t)prow * cm::kBelowCols + 1) / 2 * 2) : nullptr;
   hipLaunchKernelGGL(cm::k_commute_reduce, dim3(nblk), dim3(1024), 0, stream, gpart, wpart, prow, nA, nT, dA, dT, dWt, dWr, dslope,

@@ -403,12 +403,7 @@ int coskad_conv1x1_f32(const float* A, long long sa_m, long long sa_k, const flo
   const int gx = coskad_conv1x1_stat_rows(M, K, P, batch);
   const size_t lds = ((size_t)2 * wc * cv::BK * ps + (size_t)2 * cv::BK * (mb + 16)) * sizeof(float);
   dim3 grid(gx, M / mb);
-#define LAUNCH_CV(RT, NT, WM, WC)                                                                               \
-  do {                                                                                                          \
-    auto k = cv::k_conv1x1<RT, NT, WM, WC>;                                                                     \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, grid, dim3(64 * WM * WC), lds, stream, a);                                            \
-  } while (0)
+#define LAUNCH_CV(RT, NT, WM, WC) return launch_lds<cv::k_conv1x1<RT, NT, WM, WC>>("conv1x1", grid, dim3(64 * WM * WC), lds, stream, a)
   if (s.nt == 13 && s.wm == 8) LAUNCH_CV(2, 13, 8, 1);
   else if (s.nt == 13 && s.wm == 4) LAUNCH_CV(2, 13, 4, 2);
   else if (s.nt == 13 && s.wm == 2) LAUNCH_CV(2, 13, 2, 4);
@@ -416,7 +411,6 @@ int coskad_conv1x1_f32(const float* A, long long sa_m, long long sa_k, const flo
   else if (s.nt == 19 && s.wm == 2) LAUNCH_CV(2, 19, 2, 2);
   else LAUNCH_CV(2, 19, 1, 4);
 #undef LAUNCH_CV
-  return check_launch("conv1x1");
 }
 
 /* BatchNorm statistics from the [rows][C][2] partials of coskad_conv1x1_f32: stat [2C] = (mean, 1 / sqrt(var + eps)), running
@@ -443,14 +437,10 @@ int coskad_conv1x1_wgrad_f32(const float* G, const float* X, float* partials, in
   const int chunks = ceil_div(batch, chunk);
   if (chunks > 65535) return fail(COSKAD_ERR_SHAPE, "conv1x1_wgrad: %d chunks exceed the grid limit", chunks);
   const bool big = M % 128 == 0 && K % 128 == 0;
-#define LAUNCH_WG(WMR, WKR, TM, TK, PC)                                                                          \
-  do {                                                                                                           \
-    auto k = cv::k_conv1x1_wgrad<WMR, WKR, TM, TK, PC>;                                                          \
-    const size_t lds = (size_t)2 * (16 * TM * WMR + 16 * TK * WKR) * (PC + 2) * sizeof(float);                   \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(K / (16 * TK * WKR), M / (16 * TM * WMR), chunks), dim3(64 * WMR * WKR), lds, stream, G, X,   \
-                       partials, M, K, P, batch, chunk);                                                         \
-  } while (0)
+#define LAUNCH_WG(WMR, WKR, TM, TK, PC)                                                                                     \
+  return launch_lds<cv::k_conv1x1_wgrad<WMR, WKR, TM, TK, PC>>(                                                             \
+      "conv1x1_wgrad", dim3(K / (16 * TK * WKR), M / (16 * TM * WMR), chunks), dim3(64 * WMR * WKR),                        \
+      (size_t)2 * (16 * TM * WMR + 16 * TK * WKR) * (PC + 2) * sizeof(float), stream, G, X, partials, M, K, P, batch, chunk)
   const bool mid = M % 64 == 0;
   if (P == 204) {
     if (big) LAUNCH_WG(4, 2, 2, 4, 68);
@@ -462,7 +452,6 @@ int coskad_conv1x1_wgrad_f32(const float* G, const float* X, float* partials, in
     else LAUNCH_WG(2, 2, 1, 2, 60);
   }
 #undef LAUNCH_WG
-  return check_launch("conv1x1_wgrad");
 }
 
 }  // extern "C"

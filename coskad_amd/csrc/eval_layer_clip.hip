@@ -433,48 +433,47 @@ struct Args {
   int B;
   FirstLayer fl;
   hipStream_t st;
+  const char* what;   // names the launch in an error text
 };
 
 template <int T, int V, int CT, int OT, bool FIRST>
-static void launch_one(const Args& a) {
+static int launch_one(const Args& a) {
   using G = Geo<T, V, CT, OT, FIRST>;
-  auto k = k_eval_layer_clip<T, V, CT, OT, FIRST>;
-  if (G::LDS_BYTES > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
   const int cap = 256 * G::PER_CU;                       // the persistent grid: PER_CU workgroups on each of 256 CUs
   const int grid = a.B < cap ? a.B : cap;
   ProbeScope probe(KID_LAYER_APPLY, FIRST ? 2 : G::Ci, G::Co, a.st);
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), G::LDS_BYTES, a.st, a.in, a.out, a.Aw, a.Tw, a.wfold, a.bias, a.in_slope, a.out_slope,
-                     a.B, a.fl);
+  return launch_lds<k_eval_layer_clip<T, V, CT, OT, FIRST>>(a.what, dim3(grid), dim3(256), G::LDS_BYTES, a.st, a.in, a.out, a.Aw, a.Tw,
+                                                            a.wfold, a.bias, a.in_slope, a.out_slope, a.B, a.fl);
 }
 
 template <int T, int V>
-static void launch_tv(const Args& a, int Ci, int Co, bool first) {
+static int launch_tv(const Args& a, int Ci, int Co, bool first) {
   if (first) {
-    if (Co == 16) launch_one<T, V, 2, 1, true>(a);
-    else if (Co == 32) launch_one<T, V, 2, 2, true>(a);
-    else launch_one<T, V, 2, 4, true>(a);
+    if (Co == 16) return launch_one<T, V, 2, 1, true>(a);
+    else if (Co == 32) return launch_one<T, V, 2, 2, true>(a);
+    else return launch_one<T, V, 2, 4, true>(a);
   } else if (Ci == 16) {
-    if (Co == 16) launch_one<T, V, 1, 1, false>(a);
-    else if (Co == 32) launch_one<T, V, 1, 2, false>(a);
-    else launch_one<T, V, 1, 4, false>(a);
+    if (Co == 16) return launch_one<T, V, 1, 1, false>(a);
+    else if (Co == 32) return launch_one<T, V, 1, 2, false>(a);
+    else return launch_one<T, V, 1, 4, false>(a);
   } else {
-    if (Co == 16) launch_one<T, V, 2, 1, false>(a);
-    else if (Co == 32) launch_one<T, V, 2, 2, false>(a);
-    else launch_one<T, V, 2, 4, false>(a);
+    if (Co == 16) return launch_one<T, V, 2, 1, false>(a);
+    else if (Co == 32) return launch_one<T, V, 2, 2, false>(a);
+    else return launch_one<T, V, 2, 4, false>(a);
   }
 }
 
-static void launch_any(const Args& a, int T, int V, int Ci, int Co, bool first) {
+static int launch_any(const Args& a, int T, int V, int Ci, int Co, bool first) {
   if (V == 17) {
-    if (T == 8) launch_tv<8, 17>(a, Ci, Co, first);
-    else if (T == 12) launch_tv<12, 17>(a, Ci, Co, first);
-    else if (T == 16) launch_tv<16, 17>(a, Ci, Co, first);
-    else launch_tv<24, 17>(a, Ci, Co, first);
+    if (T == 8) return launch_tv<8, 17>(a, Ci, Co, first);
+    else if (T == 12) return launch_tv<12, 17>(a, Ci, Co, first);
+    else if (T == 16) return launch_tv<16, 17>(a, Ci, Co, first);
+    else return launch_tv<24, 17>(a, Ci, Co, first);
   } else {
-    if (T == 8) launch_tv<8, 25>(a, Ci, Co, first);
-    else if (T == 12) launch_tv<12, 25>(a, Ci, Co, first);
-    else if (T == 16) launch_tv<16, 25>(a, Ci, Co, first);
-    else launch_tv<24, 25>(a, Ci, Co, first);
+    if (T == 8) return launch_tv<8, 25>(a, Ci, Co, first);
+    else if (T == 12) return launch_tv<12, 25>(a, Ci, Co, first);
+    else if (T == 16) return launch_tv<16, 25>(a, Ci, Co, first);
+    else return launch_tv<24, 25>(a, Ci, Co, first);
   }
 }
 
@@ -502,8 +501,8 @@ int launch_eval_layer_clip(const float* in, float* out, const float* Aw, const f
     if (!evc::aligned16(in)) return fail(COSKAD_ERR_ARG, "layer_apply: `in` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)in);
     if (!evc::aligned16(out)) return fail(COSKAD_ERR_ARG, "layer_apply: `out` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)out);
   }
-  evc::launch_any(evc::Args{in, out, Aw, Tw, wfold, bias, in_slope, out_slope, B, evc::FirstLayer{}, st}, T_, V_, Ci, Co, false);
-  return check_launch("eval_layer_clip");
+  return evc::launch_any(evc::Args{in, out, Aw, Tw, wfold, bias, in_slope, out_slope, B, evc::FirstLayer{}, st, "eval_layer_clip"}, T_, V_,
+                         Ci, Co, false);
 }
 
 int launch_eval_first_pair_clip(const float* x, float* out, const float* A1, const float* T1, const float* wfold1,
@@ -516,9 +515,8 @@ int launch_eval_first_pair_clip(const float* x, float* out, const float* A1, con
     if (!evc::aligned16(out))
       return fail(COSKAD_ERR_ARG, "layer_first_pair_apply: `out` (%p) must be 16-byte aligned at window lengths 8 / 16 / 24", (const void*)out);
   }
-  evc::launch_any(evc::Args{x, out, A2, T2, wfold2, bias2, mid_slope, out_slope, B, evc::FirstLayer{A1, T1, wfold1, bias1}, st}, T_, V_,
-                  32, Co, true);
-  return check_launch("eval_first_pair_clip");
+  return evc::launch_any(evc::Args{x, out, A2, T2, wfold2, bias2, mid_slope, out_slope, B, evc::FirstLayer{A1, T1, wfold1, bias1}, st,
+                                   "eval_first_pair_clip"}, T_, V_, 32, Co, true);
 }
 
 extern "C" {

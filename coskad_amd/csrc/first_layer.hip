@@ -428,28 +428,22 @@ static int launch_first_bwd_tv(const float* in, const float* Zg, const float* dU
   *rows_out = grid;
   const int rw = ceil_div(Co, NWB);
   const size_t lds = ((size_t)T * V * V + (size_t)V * T * T + (4 + NWB) * (size_t)Ci * T * V) * sizeof(float);
-#define LAUNCH_FB1(CI, RW)                                                                                              \
-  do {                                                                                                                  \
-    auto k = fl::k_first_bwd<T, V, CI, RW>;                                                                             \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NWB), lds, st, in, Zg, dU, Aw, Tw, coef, in_slope, partials, B, Co);             \
-  } while (0)
+#define LAUNCH_FB1(CI, RW)                                                                                                      \
+  return launch_lds<fl::k_first_bwd<T, V, CI, RW>>("first_bwd", dim3(grid), dim3(64 * NWB), lds, st, in, Zg, dU, Aw, Tw, coef, in_slope, \
+                                                   partials, B, Co)
 #define LAUNCH_FB1_C(CI)                        \
   do {                                          \
     if (rw <= 4) LAUNCH_FB1(CI, 4);             \
     else if (rw <= 8) LAUNCH_FB1(CI, 8);        \
     else LAUNCH_FB1(CI, 16);                    \
   } while (0)
-  {
-    ProbeScope probe(KID_BWD_DATA, Ci, Co, st);
-    if (Ci == 1) LAUNCH_FB1_C(1);
-    else if (Ci == 2) LAUNCH_FB1_C(2);
-    else if (Ci == 3) LAUNCH_FB1_C(3);
-    else LAUNCH_FB1_C(4);
-  }
+  ProbeScope probe(KID_BWD_DATA, Ci, Co, st);
+  if (Ci == 1) LAUNCH_FB1_C(1);
+  else if (Ci == 2) LAUNCH_FB1_C(2);
+  else if (Ci == 3) LAUNCH_FB1_C(3);
+  else LAUNCH_FB1_C(4);
 #undef LAUNCH_FB1_C
 #undef LAUNCH_FB1
-  return check_launch("first_bwd");
 }
 
 int launch_first_bwd(const float* in, const float* Zg, const float* dU, const float* Aw, const float* Tw, const float* coef,
@@ -475,21 +469,15 @@ static int launch_first_moments_tv(const float* in, const float* Aw, const float
   }
   const int nmom = grid, ntab = tabs.n * fl::kFtabBlocks;
   const size_t lds = ((size_t)T * V * V + (size_t)V * T * T + 2 * fl::NWM * (size_t)Ci * T * V) * sizeof(float);
-#define LAUNCH_FM(CI)                                                                                                   \
-  do {                                                                                                                  \
-    auto k = fl::k_first_moments<T, V, CI>;                                                                             \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(nmom + ntab), dim3(64 * fl::NWM), lds, st, in, Aw, Tw, in_slope, partials, B, Zout, nmom, tabs); \
-  } while (0)
-  {
-    ProbeScope probe(KID_FWD_MOMENTS, Ci, 0, st);
-    if (Ci == 1) LAUNCH_FM(1);
-    else if (Ci == 2) LAUNCH_FM(2);
-    else if (Ci == 3) LAUNCH_FM(3);
-    else LAUNCH_FM(4);
-  }
+#define LAUNCH_FM(CI)                                                                                                          \
+  return launch_lds<fl::k_first_moments<T, V, CI>>("first_moments", dim3(nmom + ntab), dim3(64 * fl::NWM), lds, st, in, Aw, Tw, in_slope, \
+                                                   partials, B, Zout, nmom, tabs)
+  ProbeScope probe(KID_FWD_MOMENTS, Ci, 0, st);
+  if (Ci == 1) LAUNCH_FM(1);
+  else if (Ci == 2) LAUNCH_FM(2);
+  else if (Ci == 3) LAUNCH_FM(3);
+  else LAUNCH_FM(4);
 #undef LAUNCH_FM
-  return check_launch("first_moments");
 }
 
 int launch_first_moments(const float* in, const float* Aw, const float* Tw, const float* in_slope, float* partials, int B, int Ci,

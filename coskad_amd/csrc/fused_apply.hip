@@ -183,24 +183,18 @@ int launch_layer_apply_ring(const float* Z, const float* in, float* out, const f
   const size_t lds = (size_t)4 * ff::WAVE_LDS_W * sizeof(float);
   const int nblk = (B + 3) / 4;
   const int grid = nblk < 256 ? nblk : 256;
-#define LAUNCH_FA(CT, OTP, NP)                                                                                   \
-  do {                                                                                                           \
-    auto k = fa::k_layer_apply_ring<CT, OTP, NP>;                                                                \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, in, Z, wfold, bias, in_slope, out, B);                 \
-  } while (0)
-  {
-    ProbeScope probe(KID_LAYER_APPLY, Ci, Co, st);
-    if (Ci == 16 && Co == 16) LAUNCH_FA(1, 1, 1);
-    else if (Ci == 16 && Co == 32) LAUNCH_FA(1, 2, 1);
-    else if (Ci == 16 && Co == 64) LAUNCH_FA(1, 4, 1);
-    else if (Ci == 32 && Co == 16) LAUNCH_FA(2, 1, 1);
-    else if (Ci == 32 && Co == 32) LAUNCH_FA(2, 2, 1);
-    else if (Ci == 32 && Co == 64) LAUNCH_FA(2, 4, 1);
-    else return fail(COSKAD_ERR_SHAPE, "apply_ring: unsupported channels (%d, %d)", Ci, Co);
-  }
+#define LAUNCH_FA(CT, OTP, NP)                                                                                                  \
+  return launch_lds<fa::k_layer_apply_ring<CT, OTP, NP>>("layer_apply_ring", dim3(grid), dim3(256), lds, st, in, Z, wfold, bias, in_slope, \
+                                                         out, B)
+  ProbeScope probe(KID_LAYER_APPLY, Ci, Co, st);
+  if (Ci == 16 && Co == 16) LAUNCH_FA(1, 1, 1);
+  else if (Ci == 16 && Co == 32) LAUNCH_FA(1, 2, 1);
+  else if (Ci == 16 && Co == 64) LAUNCH_FA(1, 4, 1);
+  else if (Ci == 32 && Co == 16) LAUNCH_FA(2, 1, 1);
+  else if (Ci == 32 && Co == 32) LAUNCH_FA(2, 2, 1);
+  else if (Ci == 32 && Co == 64) LAUNCH_FA(2, 4, 1);
+  else return fail(COSKAD_ERR_SHAPE, "apply_ring: unsupported channels (%d, %d)", Ci, Co);
 #undef LAUNCH_FA
-  return check_launch("layer_apply_ring");
 }
 
 }  // namespace coskad

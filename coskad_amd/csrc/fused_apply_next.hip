@@ -384,25 +384,18 @@ int launch_layer_apply_next(const float* Z, const float* in, float* out, const f
   *rows_out = grid;
   if (apply_next_bpc_on(Ci, Co))
     return launch_layer_apply_next_bpc(Z, in, out, wfold, bias, in_slope, out_slope, ftab, Znext, partials, B, Ci, Co, st);
-#define LAUNCH_FN(CT, OTP)                                                                                            \
-  do {                                                                                                                \
-    auto k = fn::k_layer_apply_next<CT, OTP>;                                                                         \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, in, Z, wfold, bias, in_slope, out_slope, ftab, out, Znext,  \
-                       partials, B);                                                                                  \
-  } while (0)
-  {
-    ProbeScope probe(KID_LAYER_APPLY, Ci, Co, st);
-    if (Ci == 2 && Co == 16) LAUNCH_FN(0, 1);
-    else if (Ci == 2 && Co == 32) LAUNCH_FN(0, 2);
-    else if (Ci == 16 && Co == 16) LAUNCH_FN(1, 1);
-    else if (Ci == 16 && Co == 32) LAUNCH_FN(1, 2);
-    else if (Ci == 32 && Co == 16) LAUNCH_FN(2, 1);
-    else if (Ci == 32 && Co == 32) LAUNCH_FN(2, 2);
-    else return fail(COSKAD_ERR_SHAPE, "apply_next: unsupported channels (%d, %d)", Ci, Co);
-  }
+#define LAUNCH_FN(CT, OTP)                                                                                                      \
+  return launch_lds<fn::k_layer_apply_next<CT, OTP>>("layer_apply_next", dim3(grid), dim3(256), lds, st, in, Z, wfold, bias, in_slope, \
+                                                     out_slope, ftab, out, Znext, partials, B)
+  ProbeScope probe(KID_LAYER_APPLY, Ci, Co, st);
+  if (Ci == 2 && Co == 16) LAUNCH_FN(0, 1);
+  else if (Ci == 2 && Co == 32) LAUNCH_FN(0, 2);
+  else if (Ci == 16 && Co == 16) LAUNCH_FN(1, 1);
+  else if (Ci == 16 && Co == 32) LAUNCH_FN(1, 2);
+  else if (Ci == 32 && Co == 16) LAUNCH_FN(2, 1);
+  else if (Ci == 32 && Co == 32) LAUNCH_FN(2, 2);
+  else return fail(COSKAD_ERR_SHAPE, "apply_next: unsupported channels (%d, %d)", Ci, Co);
 #undef LAUNCH_FN
-  return check_launch("layer_apply_next");
 }
 
 }  // namespace coskad

@@ -377,15 +377,11 @@ int coskad_fused_encoder_f32(const float* x, float* out, const float* tab, const
   if (T != ff::T || V != ff::V)
     return fail(COSKAD_ERR_SHAPE, "fused_encoder: built for n_frames=12, n_joints=17 and channels 2-32-16-32-64 (got T=%d V=%d)", T, V);
   const size_t lds = (size_t)4 * ff::WAVE_LDS * sizeof(float);
-  auto k = ff::k_fused_encoder;
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int nblk = (B + 3) / 4;
   const int grid = nblk < 256 ? nblk : 256;          // one 4-wave block per CU, persistent over clips
-  {
-    ProbeScope probe(KID_FUSED_FWD, 2, 64, stream);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, stream, x, out, reinterpret_cast<const float4*>(tab), wreg, slopes, B);
-  }
-  return check_launch("fused_encoder");
+  ProbeScope probe(KID_FUSED_FWD, 2, 64, stream);
+  return launch_lds<ff::k_fused_encoder>("fused_encoder", dim3(grid), dim3(256), lds, stream, x, out, reinterpret_cast<const float4*>(tab), wreg,
+                                         slopes, B);
 }
 
 }  // extern "C"

@@ -519,24 +519,17 @@ int launch_bwd_stats_ring(const float* in, const float* Zg, const float* dU, con
   const int nblk = (B + 3) / 4;
   const int grid = nblk < 256 ? nblk : 256;
   *rows_out = grid;
-#define LAUNCH_FS(CT, OT)                                                                                        \
-  do {                                                                                                           \
-    auto k = fs::k_bwd_stats_ring<CT, OT>;                                                                       \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, in, Zg, dU, in_slope, partials, B);                    \
-  } while (0)
-  {
-    ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
-    if (Ci == 16 && Co == 16) LAUNCH_FS(1, 1);
-    else if (Ci == 16 && Co == 32) LAUNCH_FS(1, 2);
-    else if (Ci == 16 && Co == 64) LAUNCH_FS(1, 4);
-    else if (Ci == 32 && Co == 16) LAUNCH_FS(2, 1);
-    else if (Ci == 32 && Co == 32) LAUNCH_FS(2, 2);
-    else if (Ci == 32 && Co == 64) LAUNCH_FS(2, 4);
-    else return fail(COSKAD_ERR_SHAPE, "bwd_stats_ring: unsupported channels (%d, %d)", Ci, Co);
-  }
+#define LAUNCH_FS(CT, OT) \
+  return launch_lds<fs::k_bwd_stats_ring<CT, OT>>("bwd_stats_ring", dim3(grid), dim3(256), lds, st, in, Zg, dU, in_slope, partials, B)
+  ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
+  if (Ci == 16 && Co == 16) LAUNCH_FS(1, 1);
+  else if (Ci == 16 && Co == 32) LAUNCH_FS(1, 2);
+  else if (Ci == 16 && Co == 64) LAUNCH_FS(1, 4);
+  else if (Ci == 32 && Co == 16) LAUNCH_FS(2, 1);
+  else if (Ci == 32 && Co == 32) LAUNCH_FS(2, 2);
+  else if (Ci == 32 && Co == 64) LAUNCH_FS(2, 4);
+  else return fail(COSKAD_ERR_SHAPE, "bwd_stats_ring: unsupported channels (%d, %d)", Ci, Co);
 #undef LAUNCH_FS
-  return check_launch("bwd_stats_ring");
 }
 
 
@@ -549,20 +542,13 @@ int launch_bwd_stats_bpc(const float* in, const float* Zg, const float* dU, cons
   const int per_cu = lds <= (size_t)52 * 1024 ? 3 : 2;
   const int grid = B < 256 * per_cu ? B : 256 * per_cu;
   *rows_out = grid;
-#define LAUNCH_FSB(CT, OT)                                                                                       \
-  do {                                                                                                           \
-    auto k = fs::k_bwd_stats_bpc<CT, OT>;                                                                        \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, in, Zg, dU, in_slope, partials, B);                    \
-  } while (0)
-  {
-    ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
-    if (Ci == 32 && Co == 32) LAUNCH_FSB(2, 2);
-    else if (Ci == 32 && Co == 64) LAUNCH_FSB(2, 4);
-    else return fail(COSKAD_ERR_SHAPE, "bwd_stats_bpc: unsupported channels (%d, %d)", Ci, Co);
-  }
+#define LAUNCH_FSB(CT, OT) \
+  return launch_lds<fs::k_bwd_stats_bpc<CT, OT>>("bwd_stats_bpc", dim3(grid), dim3(256), lds, st, in, Zg, dU, in_slope, partials, B)
+  ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
+  if (Ci == 32 && Co == 32) LAUNCH_FSB(2, 2);
+  else if (Ci == 32 && Co == 64) LAUNCH_FSB(2, 4);
+  else return fail(COSKAD_ERR_SHAPE, "bwd_stats_bpc: unsupported channels (%d, %d)", Ci, Co);
 #undef LAUNCH_FSB
-  return check_launch("bwd_stats_bpc");
 }
 
 
@@ -576,23 +562,16 @@ int launch_bwd_stats_flat(const float* in, const float* Zg, const float* dU, con
   const size_t lds = (size_t)64 * (TVg + 2) * sizeof(float);
   const int grid = B < 512 ? B : 512;
   *rows_out = grid;
-#define LAUNCH_FSF(CT, OT)                                                                                       \
-  do {                                                                                                           \
-    auto k = fs::k_bwd_stats_flat<TVg, CT, OT>;                                                                  \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, in, Zg, dU, in_slope, partials, B);                    \
-  } while (0)
-  {
-    ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
-    if (Ci == 16 && Co == 16) LAUNCH_FSF(1, 1);
-    else if (Ci == 16 && Co == 32) LAUNCH_FSF(1, 2);
-    else if (Ci == 16 && Co == 64) LAUNCH_FSF(1, 4);
-    else if (Ci == 32 && Co == 16) LAUNCH_FSF(2, 1);
-    else if (Ci == 32 && Co == 32) LAUNCH_FSF(2, 2);
-    else LAUNCH_FSF(2, 4);
-  }
+#define LAUNCH_FSF(CT, OT) \
+  return launch_lds<fs::k_bwd_stats_flat<TVg, CT, OT>>("bwd_stats_flat", dim3(grid), dim3(256), lds, st, in, Zg, dU, in_slope, partials, B)
+  ProbeScope probe(KID_BWD_REDUCE, Ci, Co, st);
+  if (Ci == 16 && Co == 16) LAUNCH_FSF(1, 1);
+  else if (Ci == 16 && Co == 32) LAUNCH_FSF(1, 2);
+  else if (Ci == 16 && Co == 64) LAUNCH_FSF(1, 4);
+  else if (Ci == 32 && Co == 16) LAUNCH_FSF(2, 1);
+  else if (Ci == 32 && Co == 32) LAUNCH_FSF(2, 2);
+  else LAUNCH_FSF(2, 4);
 #undef LAUNCH_FSF
-  return check_launch("bwd_stats_flat");
 }
 
 }  // namespace coskad

@@ -230,10 +230,7 @@ int launch_gcn_params_bpc(const float* in, const float* in_slope, const float* d
   const int ntiles = (rows_total + 31) / 32;
   const int grid = ntiles < 512 ? ntiles : 512;
   *rows_out = grid;
-  auto k = gp::k_gcn_params_bpc<V>;
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, in, dz, Aw, Tw, in_slope, partials, rows_total);
-  return check_launch("gcn_params_bpc");
+  return launch_lds<gp::k_gcn_params_bpc<V>>("gcn_params_bpc", dim3(grid), dim3(256), lds, st, in, dz, Aw, Tw, in_slope, partials, rows_total);
 }
 
 }  // namespace coskad

@@ -282,14 +282,6 @@ __global__ __launch_bounds__(1024) void k_win_reduce(const float* __restrict__ p
   }
 }
 
-template <class K>
-int set_lds(K k, size_t lds) {
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(COSKAD_ERR_LAUNCH, "window mixing: %zu B of LDS refused", lds);
-  return COSKAD_OK;
-}
-
 template <int T, int V>
 int launch_win_gcn(const float* in, float* out, const float* Aw, const float* Tw, int rows, int adjoint, hipStream_t st) {
   using G = WinGeo<T, V>;
@@ -298,15 +290,8 @@ int launch_win_gcn(const float* in, float* out, const float* Aw, const float* Tw
   const int ntiles = ceil_div(rows, 16 * G::MixRT);
   const int grid = ntiles < kGridCap ? ntiles : kGridCap;
   const int vec = aligned16(in) && aligned16(out);
-  int rc;
-  if (adjoint) {
-    if ((rc = set_lds(k_win_gcn<T, V, true>, lds))) return rc;
-    hipLaunchKernelGGL((k_win_gcn<T, V, true>), dim3(grid), dim3(kWinBlock), lds, st, in, out, Aw, Tw, rows, vec);
-  } else {
-    if ((rc = set_lds(k_win_gcn<T, V, false>, lds))) return rc;
-    hipLaunchKernelGGL((k_win_gcn<T, V, false>), dim3(grid), dim3(kWinBlock), lds, st, in, out, Aw, Tw, rows, vec);
-  }
-  return check_launch("gcn (window)");
+  if (adjoint) return launch_lds<k_win_gcn<T, V, true>>("gcn (window)", dim3(grid), dim3(kWinBlock), lds, st, in, out, Aw, Tw, rows, vec);
+  return launch_lds<k_win_gcn<T, V, false>>("gcn (window)", dim3(grid), dim3(kWinBlock), lds, st, in, out, Aw, Tw, rows, vec);
 }
 
 // in_slope != NULL: the ACT form (16-byte aligned rows; 17 / 25 joints); dap: its slope-gradient partials, one per workgroup;
@@ -323,28 +308,24 @@ int launch_win_params(const float* x, const float* dZ, const float* Aw, const fl
   const int vec = aligned16(x) && aligned16(dZ) && aligned16(dX) && aligned16(add);   // (NULL counts as aligned)
   int rc;
   if (rows_out) *rows_out = grid;
+#define LAUNCH_WP(DX, ACT, SLOPE, DAP)                                                                                                  \
+  rc = launch_lds<k_win_params<T, V, DX, ACT>>("gcn_bwd_params (window)", dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, \
+                                               add, rows, vec, SLOPE, DAP)
   if (in_slope) {
     if constexpr (V == 17 || V == 25) {
       if (!vec) return fail(COSKAD_ERR_ARG, "gcn_bwd_params (window): the activating form needs 16-byte aligned rows");
-      if (dX) {
-        if ((rc = set_lds(k_win_params<T, V, true, true>, lds))) return rc;
-        hipLaunchKernelGGL((k_win_params<T, V, true, true>), dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, add, rows,
-                           vec, in_slope, dap);
-      } else {
-        if ((rc = set_lds(k_win_params<T, V, false, true>, lds))) return rc;
-        hipLaunchKernelGGL((k_win_params<T, V, false, true>), dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, add, rows,
-                           vec, in_slope, dap);
-      }
+      if (dX) LAUNCH_WP(true, true, in_slope, dap);
+      else LAUNCH_WP(false, true, in_slope, dap);
     } else {
       return fail(COSKAD_ERR_SHAPE, "gcn_bwd_params (window): the activating form is built for 17 / 25 joints");
     }
   } else if (dX) {
-    if ((rc = set_lds(k_win_params<T, V, true>, lds))) return rc;
-    hipLaunchKernelGGL((k_win_params<T, V, true>), dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, add, rows, vec);
+    LAUNCH_WP(true, false, (const float*)nullptr, (float*)nullptr);
   } else {
-    if ((rc = set_lds(k_win_params<T, V, false>, lds))) return rc;
-    hipLaunchKernelGGL((k_win_params<T, V, false>), dim3(grid), dim3(G::ParBlock), lds, st, x, dZ, Aw, Tw, partials, dX, add, rows, vec);
+    LAUNCH_WP(false, false, (const float*)nullptr, (float*)nullptr);
   }
+#undef LAUNCH_WP
+  if (rc) return rc;
   hipLaunchKernelGGL(k_win_reduce, dim3(ceil_div(G::E, 64)), dim3(1024), 0, st, partials, grid, G::E, G::NA, dA, dT, accumulate);
   return check_launch("gcn_bwd_params (window)");
 }

@@ -380,14 +380,6 @@ inline int grid_of(const Shape& s, int grid_cap) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
-template <class K>
-int set_lds(K k, size_t lds) {
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(COSKAD_ERR_LAUNCH, "plain_gcn: %zu B of LDS refused", lds);
-  return COSKAD_OK;
-}
-
 int check_shape(const char* what, int B, int Ci, int Co, int P);
 
 }  // namespace pgcn
@@ -434,15 +426,9 @@ int coskad_plain_gcn_fwd_f32(const float* X, const float* W, const float* Ap, co
   const int grid = pgcn::grid_of(s, grid_cap);
   const bool mixfirst = Ci <= Co;
   const size_t lds = (size_t)(mixfirst ? 2 : 1) * s.R16 * s.LD * sizeof(float);
-  int rc;
-  if (mixfirst) {
-    if ((rc = pgcn::set_lds(pgcn::k_pgcn_fwd<true>, lds))) return rc;
-    hipLaunchKernelGGL((pgcn::k_pgcn_fwd<true>), dim3(grid), dim3(pgcn::kBlock), lds, stream, X, W, Ap, bias, O, save, s);
-  } else {
-    if ((rc = pgcn::set_lds(pgcn::k_pgcn_fwd<false>, lds))) return rc;
-    hipLaunchKernelGGL((pgcn::k_pgcn_fwd<false>), dim3(grid), dim3(pgcn::kBlock), lds, stream, X, W, Ap, bias, O, save, s);
-  }
-  return check_launch("plain_gcn_fwd");
+  if (mixfirst)
+    return launch_lds<pgcn::k_pgcn_fwd<true>>("plain_gcn_fwd", dim3(grid), dim3(pgcn::kBlock), lds, stream, X, W, Ap, bias, O, save, s);
+  return launch_lds<pgcn::k_pgcn_fwd<false>>("plain_gcn_fwd", dim3(grid), dim3(pgcn::kBlock), lds, stream, X, W, Ap, bias, O, save, s);
 }
 
 int coskad_plain_gcn_bwd_f32(const float* X, const float* S, const float* O, const float* dO, const float* W, const float* Ap,
@@ -465,14 +451,11 @@ int coskad_plain_gcn_bwd_f32(const float* X, const float* S, const float* O, con
   float* partials = reinterpret_cast<float*>(ws);
   float* dx = need_dx ? dX : nullptr;
   float* d = need_da ? D : nullptr;
-  int rc;
-  if (mixfirst) {
-    if ((rc = pgcn::set_lds(pgcn::k_pgcn_bwd<true>, lds))) return rc;
-    hipLaunchKernelGGL((pgcn::k_pgcn_bwd<true>), dim3(grid), dim3(pgcn::kBlock), lds, stream, X, S, O, dO, W, Ap, dx, d, partials, s);
-  } else {
-    if ((rc = pgcn::set_lds(pgcn::k_pgcn_bwd<false>, lds))) return rc;
-    hipLaunchKernelGGL((pgcn::k_pgcn_bwd<false>), dim3(grid), dim3(pgcn::kBlock), lds, stream, X, S, O, dO, W, Ap, dx, d, partials, s);
-  }
+  const int rc = mixfirst ? launch_lds<pgcn::k_pgcn_bwd<true>>("plain_gcn_bwd", dim3(grid), dim3(pgcn::kBlock), lds, stream, X, S, O, dO, W, Ap,
+                                                              dx, d, partials, s)
+                          : launch_lds<pgcn::k_pgcn_bwd<false>>("plain_gcn_bwd", dim3(grid), dim3(pgcn::kBlock), lds, stream, X, S, O, dO, W, Ap,
+                                                               dx, d, partials, s);
+  if (rc) return rc;
   const int E = Ci * Co + Co;
   hipLaunchKernelGGL(pgcn::k_pgcn_reduce, dim3(ceil_div(E, 64)), dim3(1024), 0, stream, partials, grid, E, Ci * Co, dW, db, accumulate);
   return check_launch("plain_gcn_bwd");

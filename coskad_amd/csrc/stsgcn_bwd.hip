@@ -1294,22 +1294,19 @@ static int launch_layer_gcn_params(const LayerBwdArgs& a, const float* dz, float
   const int rt = kBlock > 512 ? 32 : 16;       // (16-wave blocks, one per CU: twice the rows per barrier round; 3.20 -> 3.16 ms on the 25-joint step)
   const int RTILE = rows_total < rt ? rows_total : rt;
   const size_t lds = ((size_t)2 * RTILE * LD + (size_t)T * V * V + (size_t)V * T * T) * sizeof(float);
-  if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", lds);
   const int ntiles = ceil_div(rows_total, RTILE);
   const int per_cu = (lds <= (size_t)52 * 1024 && V <= 17) ? 3 : (lds <= (size_t)80 * 1024 ? 2 : 1);
   const int grid = ntiles < 256 * per_cu ? ntiles : 256 * per_cu;
   const int NB = RTILE;
-  auto k = k_bwd_gcn_params<T, V>;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  int rc;
   {
     ProbeScope probe(KID_GCN_PARAMS, a.Ci, a.Co, st);
     static const int ablg = ablate_env("COSKAD_ABLG", 0);
     (void)ablg;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, a.in, dz, a.A, a.Tm, a.in_slope, partials, rows_total, 1, NB, (float*)nullptr,
-                       (const float*)nullptr ABL_ARG(ablg));
+    rc = launch_lds<k_bwd_gcn_params<T, V>>("bwd_gcn_params", dim3(grid), dim3(kBlock), lds, st, a.in, dz, a.A, a.Tm, a.in_slope, partials,
+                                            rows_total, 1, NB, (float*)nullptr, (const float*)nullptr ABL_ARG(ablg));
   }
-  int rc;
-  if ((rc = check_launch("bwd_gcn_params"))) return rc;
+  if (rc) return rc;
   return reduce(grid);
 }
 
@@ -1354,19 +1351,17 @@ static RedPlan plan_reduce(const LayerBwdArgs& a, int kBlock, LdsOf lds_of) {
 template <int T, int V>
 static int stage1_tile_z(const LayerBwdArgs& a, float* partials) {
   const RedPlan p = plan_reduce(a, Geo<T, V>::Block, [&](int nb) { return red_z_lds<T, V>(a, nb); });
-  if (p.lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", p.lds);
+  int rc = 0;
   {
     ProbeScope probe(KID_BWD_REDUCE, a.Ci, a.Co, a.stream);
     with_tiles(ceil_div(a.Co, 16), [&](auto NTO) {
       with_tiles(ceil_div(a.Ci, 16), [&](auto NTC) {
-        auto k = k_bwd_reduce_z<T, V, decltype(NTO)::value, decltype(NTC)::value>;
-        if (p.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        hipLaunchKernelGGL(k, dim3(p.grid), dim3(Geo<T, V>::Block), p.lds, a.stream, a.in, a.Z, a.dU, a.in_slope, partials, a.B, a.Ci,
-                           a.Co, p.NB, (int)(a.Wr != nullptr));
+        rc = launch_lds<k_bwd_reduce_z<T, V, decltype(NTO)::value, decltype(NTC)::value>>(
+            "bwd_reduce_z", dim3(p.grid), dim3(Geo<T, V>::Block), p.lds, a.stream, a.in, a.Z, a.dU, a.in_slope, partials, a.B, a.Ci, a.Co,
+            p.NB, (int)(a.Wr != nullptr));
       });
     });
   }
-  const int rc = check_launch("bwd_reduce_z");
   return rc ? rc : p.grid;
 }
 
@@ -1375,19 +1370,17 @@ static int stage1_tile_z(const LayerBwdArgs& a, float* partials) {
 template <int T, int V>
 static int stage1_tile(const LayerBwdArgs& a, float* partials) {
   const RedPlan p = plan_reduce(a, Geo<T, V>::Block, [&](int nb) { return red_lds<T, V>(a, nb); });
-  if (p.lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", p.lds);
+  int rc = 0;
   {
     ProbeScope probe(KID_BWD_REDUCE, a.Ci, a.Co, a.stream);
     with_tiles(ceil_div(a.Co, 16), [&](auto NTO) {
       with_tiles(ceil_div(a.Ci, 16), [&](auto NTC) {
-        auto k = k_bwd_reduce<T, V, decltype(NTO)::value, decltype(NTC)::value>;
-        if (p.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-        hipLaunchKernelGGL(k, dim3(p.grid), dim3(Geo<T, V>::Block), p.lds, a.stream, a.in, a.dU, a.A, a.Tm, a.in_slope, partials, a.B,
-                           a.Ci, a.Co, p.NB, (int)(a.Wr != nullptr), a.Z);
+        rc = launch_lds<k_bwd_reduce<T, V, decltype(NTO)::value, decltype(NTC)::value>>(
+            "bwd_reduce", dim3(p.grid), dim3(Geo<T, V>::Block), p.lds, a.stream, a.in, a.dU, a.A, a.Tm, a.in_slope, partials, a.B, a.Ci,
+            a.Co, p.NB, (int)(a.Wr != nullptr), a.Z);
       });
     });
   }
-  const int rc = check_launch("bwd_reduce");
   return rc ? rc : p.grid;
 }
 
@@ -1443,14 +1436,12 @@ static int stage2_fold(const LayerBwdArgs& a, const BwdWs& w, int TV, bool fused
   const int Ci = a.Ci, Co = a.Co;
   const LayerGrads& g = a.g;
   const size_t fold_lds = (size_t)(6 * Co + 2 * Co * Ci + Co) * sizeof(double) + (size_t)(4 * Co * Ci + 2 * Ci + 4 * Co) * sizeof(float);
-  if (fold_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_bwd_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds);
   const int tab_blocks = fused ? ceil_div(ff::BTAB_F4 * 4, 1024) : 0;
   const int NF = Co >= 32 ? 8 : (Co >= 16 ? 4 : 1);          // fold blocks (slices of the output channels / K pairs)
   const double* red = a.chain.stats ? reinterpret_cast<const double*>(a.chain.stats + chain_sums_offset(a.chain.rows, 2 * Co * Ci + Co)) : w.red;
-  hipLaunchKernelGGL(k_bwd_fold, dim3(NF + tab_blocks), dim3(1024), fold_lds, a.stream, red, a.stats_count > 0.0 ? a.stats_count : (double)a.B * TV,
-                     a.stat, a.Wt, a.gt, a.Wr, a.gr, g.dWt, g.dbt, g.dgt, g.dbet, g.dWr, g.dbr, g.dgr, g.dber, w.coef, Ci, Co, a.accumulate,
-                     a.A, a.Tm, w.btab, NF);
-  return check_launch("bwd_fold");
+  return launch_lds<k_bwd_fold>("bwd_fold", dim3(NF + tab_blocks), dim3(1024), fold_lds, a.stream, red,
+                                a.stats_count > 0.0 ? a.stats_count : (double)a.B * TV, a.stat, a.Wt, a.gt, a.Wr, a.gr, g.dWt, g.dbt, g.dgt, g.dbet,
+                                g.dWr, g.dbr, g.dgr, g.dber, w.coef, Ci, Co, a.accumulate, a.A, a.Tm, w.btab, NF);
 }
 
 // block partials of the producer's slope gradient go to the workspace where that gradient is asked for
@@ -1514,7 +1505,6 @@ static int stage3_data_tile(const LayerBwdArgs& a, const BwdWs& w) {
   const int CiP = round_up(Ci, 16), KZ = round_up(Ci, 4), K1 = round_up(Co, 4);
   const size_t lds = ((size_t)NB * Ci * LD + (size_t)T * V * V + (size_t)V * T * T + 2 * (size_t)(KZ + K1) * CiP +
                       2 * CiP) * sizeof(float);
-  if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_bwd: LDS %zu too large", lds);
   const int ntl = ceil_div(B, NB);
   const int per_cu = (int)((size_t)kMaxLdsBytes / lds);
   int grid_d = 256 * (per_cu < 1 ? 1 : (per_cu > 2048 / kBlock ? 2048 / kBlock : per_cu));   // (a CU holds 32 waves)
@@ -1526,15 +1516,15 @@ static int stage3_data_tile(const LayerBwdArgs& a, const BwdWs& w) {
   constexpr bool strips_fit = (Geo<T, V>::TV + 31) / 32 <= kBlock / 64;
   // single-read variant: tiles of 32 rows = one clip of >= 32 channels, or two clips of exactly 16
   const bool two_clip = Ci == 16;            // NB was kept at 2 above
+  int rc = 0;
   {
     ProbeScope probe(KID_BWD_DATA, Ci, Co, st);
     if (fused_ok && strips_fit && (NB == 1 || two_clip) && dIn != nullptr && CiP <= 64) {
       if constexpr (strips_fit) {
         auto launch_f = [&](auto OTI, auto NBF) {
-          auto k = k_bwd_data_f<T, V, decltype(OTI)::value, decltype(NBF)::value>;
-          if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          hipLaunchKernelGGL(k, dim3(grid_d), dim3(kBlock), lds, st, a.in, a.dU, a.A, a.Tm, w.coef, a.in_slope, dIn, w.dz, dap, B, Ci, Co,
-                             a.Z ABL_ARG(abl));
+          rc = launch_lds<k_bwd_data_f<T, V, decltype(OTI)::value, decltype(NBF)::value>>(
+              "bwd_data", dim3(grid_d), dim3(kBlock), lds, st, a.in, a.dU, a.A, a.Tm, w.coef, a.in_slope, dIn, w.dz, dap, B, Ci, Co,
+              a.Z ABL_ARG(abl));
         };
         if (two_clip) launch_f(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
         else   // (one clip of < 16 channels: only when the batch is a single clip)
@@ -1542,15 +1532,12 @@ static int stage3_data_tile(const LayerBwdArgs& a, const BwdWs& w) {
       }
     } else {
       with_tiles(CiP / 16, [&](auto OTI) {
-        auto k = k_bwd_data<T, V, decltype(OTI)::value>;
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k, dim3(grid_d), dim3(kBlock), lds, st, a.in, a.dU, a.A, a.Tm, w.coef, a.in_slope, dIn, w.dz, dap, B, Ci, Co, NB,
-                           a.Z);
+        rc = launch_lds<k_bwd_data<T, V, decltype(OTI)::value>>("bwd_data", dim3(grid_d), dim3(kBlock), lds, st, a.in, a.dU, a.A, a.Tm, w.coef,
+                                                                a.in_slope, dIn, w.dz, dap, B, Ci, Co, NB, a.Z);
       });
     }
   }
-  int rc;
-  if ((rc = check_launch("bwd_data"))) return rc;
+  if (rc) return rc;
   if (dap && a.dz_ext) {   // split call: stage 4 is not ours, finish the slope gradient here
     hipLaunchKernelGGL(k_sum_to, dim3(1), dim3(256), 0, st, dap, grid_d, a.g.dslope_in, a.accumulate);
     if ((rc = check_launch("bwd_dslope"))) return rc;
@@ -1643,9 +1630,9 @@ static int launch_gcn_bwd_params(const float* x, const float* dZ, const float* A
   const int ntiles = ceil_div(rows, NB);
   const int grid = ntiles < 512 ? ntiles : 512;
   float* partials = reinterpret_cast<float*>(ws);
-  auto k = k_bwd_gcn_params<T, V>;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, x, dZ, Aw, Tw, (const float*)nullptr, partials, rows, 1, NB, dX, dX_add ABL_ARG(0));
+  if (int rc = launch_lds<k_bwd_gcn_params<T, V>>("gcn_bwd_params", dim3(grid), dim3(kBlock), lds, st, x, dZ, Aw, Tw, (const float*)nullptr,
+                                                  partials, rows, 1, NB, dX, dX_add ABL_ARG(0)))
+    return rc;
   hipLaunchKernelGGL(k_reduce_to_f32, dim3(ceil_div(T * V * V, 64)), dim3(1024), 0, st, partials, grid, E, 0, T * V * V, dA, accumulate);
   hipLaunchKernelGGL(k_reduce_to_f32, dim3(ceil_div(V * T * T, 64)), dim3(1024), 0, st, partials, grid, E, T * V * V, V * T * T, dT, accumulate);
   return check_launch("gcn_bwd_params");

@@ -273,19 +273,14 @@ static int launch_layer_apply(const float* in, float* out, const float* Aw, cons
   if (lds > (size_t)kMaxLdsBytes)
     return fail(COSKAD_ERR_SHAPE, "layer_apply: C_in=%d needs %zu B of LDS (> %d)", Ci, lds, kMaxLdsBytes);
   const int grid = ceil_div(B, NB);
-#define LAUNCH_CB(CB)                                                                             \
-  do {                                                                                            \
-    auto k = k_layer_apply<T, V, CB>;                                                             \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, in, out, Aw, Tw, wfold, bias,         \
-                       in_slope, out_slope, B, Ci, Co, CoP, NB);                                  \
-  } while (0)
+#define LAUNCH_CB(CB)                                                                                        \
+  return launch_lds<k_layer_apply<T, V, CB>>("layer_apply", dim3(grid), dim3(kBlock), lds, st, in, out, Aw, Tw, wfold, bias, \
+                                             in_slope, out_slope, B, Ci, Co, CoP, NB)
   if (Ci % 8 == 0) LAUNCH_CB(8);
   else if (Ci % 4 == 0) LAUNCH_CB(4);
   else if (Ci % 2 == 0) LAUNCH_CB(2);
   else LAUNCH_CB(1);
 #undef LAUNCH_CB
-  return check_launch("layer_apply");
 }
 
 template <int T, int V>

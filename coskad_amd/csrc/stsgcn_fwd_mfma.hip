@@ -175,23 +175,18 @@ int launch_layer_apply_z(const float* Z, const float* in, float* out, const floa
                          const float* in_slope, const float* out_slope, int B, int Ci, int Co, hipStream_t st) {
   const int CoP = round_up(Co, 16), KZ = round_up(Ci, 4);
   const size_t lds = ((size_t)2 * KZ * CoP + CoP) * sizeof(float);
-  if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "layer_apply_z: LDS %zu too large", lds);
   constexpr int PS = (Geo<T, V>::TV + 31) / 32;
   const long long witems = ((long long)B * PS + 3) / 4;
   const int grid = (int)(witems < 256 * 8 ? witems : 256 * 8);   // 8 four-wave blocks per CU (sweep: 4..16 within 5 %)
-#define LAUNCH_Z(OTI)                                                                                 \
-  do {                                                                                                \
-    auto k = k_layer_apply_z<T, V, OTI>;                                                              \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, Z, in, out, wfold, bias, in_slope, out_slope, B, Ci, Co, CoP); \
-  } while (0)
+#define LAUNCH_Z(OTI)                                                                                                  \
+  return launch_lds<k_layer_apply_z<T, V, OTI>>("layer_apply_z", dim3(grid), dim3(256), lds, st, Z, in, out, wfold, bias, in_slope, \
+                                                out_slope, B, Ci, Co, CoP)
   ProbeScope probe(KID_LAYER_APPLY, Ci, Co, st);
   if (CoP == 16) LAUNCH_Z(1);
   else if (CoP == 32) LAUNCH_Z(2);
   else if (CoP == 48) LAUNCH_Z(3);
   else LAUNCH_Z(4);
 #undef LAUNCH_Z
-  return check_launch("layer_apply_z");
 }
 
 size_t layer_apply_m_lds(int T, int V, int Ci, int CoP, int NB) {
@@ -213,13 +208,9 @@ int launch_layer_apply_m(const float* in, float* out, const float* Aw, const flo
   const int per_cu = (int)((size_t)kMaxLdsBytes / lds);
   int grid = 256 * (per_cu < 1 ? 1 : (per_cu > 2048 / kBlock ? 2048 / kBlock : per_cu));   // (a CU holds 32 waves)
   if (grid > ntiles) grid = ntiles;
-#define LAUNCH_OTI(OTI)                                                                             \
-  do {                                                                                              \
-    auto k = k_layer_apply_m<T, V, OTI>;                                                            \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, in, out, Aw, Tw, wfold, bias, in_slope,   \
-                       out_slope, B, Ci, Co, CoP, NB, dbg, Zg);                                     \
-  } while (0)
+#define LAUNCH_OTI(OTI)                                                                                                   \
+  return launch_lds<k_layer_apply_m<T, V, OTI>>("layer_apply_m", dim3(grid), dim3(kBlock), lds, st, in, out, Aw, Tw, wfold, bias, \
+                                                in_slope, out_slope, B, Ci, Co, CoP, NB, dbg, Zg)
   static const int dbg = ablate_env("COSKAD_DBG", 0);   // phase-ablation builds only (tools/ablate_bwd.py)
   ProbeScope probe(KID_LAYER_APPLY, Ci, Co, st);
   if (CoP == 16) LAUNCH_OTI(1);
@@ -227,7 +218,6 @@ int launch_layer_apply_m(const float* in, float* out, const float* Aw, const flo
   else if (CoP == 48) LAUNCH_OTI(3);
   else LAUNCH_OTI(4);
 #undef LAUNCH_OTI
-  return check_launch("layer_apply_m");
 }
 
 // explicit instantiations used by stsgcn_fwd.hip's dispatcher

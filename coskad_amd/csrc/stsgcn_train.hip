@@ -297,12 +297,10 @@ static int launch_reduce_fold(const float* partials, int rows, double* red, doub
   }
   if (!p.Wt) return 0;
   const size_t fold_lds = (2 * (size_t)Ci * Ci + 2 * Ci) * sizeof(double) + (4 * (size_t)Co * Ci + 4 * Co) * sizeof(float);
-  if (fold_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_train_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds);
   const int fold_blocks = Co >= 32 ? 8 : (Co >= 16 ? 4 : 1);
-  hipLaunchKernelGGL(k_train_fold, dim3(fold_blocks), dim3(1024), fold_lds, st, red, npos, p.Wt, p.bt, p.gt, p.bet, p.rm_t,
-                     p.rv_t, p.nbt_t, p.Wr, p.br, p.gr, p.ber, p.rm_r, p.rv_r, p.nbt_r, p.momentum, o.wfold, o.bias, o.stat, Ci,
-                     Co, round_up(Co, 16), self_sum ? partials : (const float*)nullptr, rows);
-  return check_launch("train_fold");
+  return launch_lds<k_train_fold>("train_fold", dim3(fold_blocks), dim3(1024), fold_lds, st, red, npos, p.Wt, p.bt, p.gt, p.bet, p.rm_t,
+                                  p.rv_t, p.nbt_t, p.Wr, p.br, p.gr, p.ber, p.rm_r, p.rv_r, p.nbt_r, p.momentum, o.wfold, o.bias, o.stat, Ci,
+                                  Co, round_up(Co, 16), self_sum ? partials : (const float*)nullptr, rows);
 }
 
 // The statistics pass of one layer: Z = gcn(PReLU(in)) (stored where a.Zout is given), its moments as partial rows, then the fold.
@@ -331,7 +329,7 @@ static int launch_train_stats(const LayerStatsArgs& a) {
   float* partials = reinterpret_cast<float*>(a.ws);
   double* red = reinterpret_cast<double*>(reinterpret_cast<char*>(a.ws) + round_up((int)(kMaxGrid * (size_t)E * sizeof(float)), 256));
   const int need_x = a.sums ? 1 : (a.p.Wr != nullptr);
-  int rows = grid;
+  int rows = grid, rc = 0;
   if (a.ftab && !(a.Zout && Ci <= 4 && T == 12 && V == 17))
     return fail(COSKAD_ERR_SHAPE, "train_stats: operand tables ride only in the first layer's moments launch (stored Z, C_in <= 4, T=12, V=17)");
   if (a.Zout && Ci <= 4 && TV % 4 == 0) {
@@ -346,12 +344,10 @@ static int launch_train_stats(const LayerStatsArgs& a) {
   } else {
     ProbeScope probe(KID_FWD_MOMENTS, Ci, Co, st);
     with_tiles(ceil_div(Ci, 16), [&](auto NTC) {
-      auto k = k_fwd_moments<T, V, decltype(NTC)::value>;
-      if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, st, a.in, a.A, a.Tm, a.in_slope, partials, B, Ci, NB, need_x, a.Zout);
+      rc = launch_lds<k_fwd_moments<T, V, decltype(NTC)::value>>("fwd_moments", dim3(grid), dim3(kBlock), lds, st, a.in, a.A, a.Tm, a.in_slope,
+                                                                 partials, B, Ci, NB, need_x, a.Zout);
     });
   }
-  int rc = check_launch("fwd_moments");
   if (rc) return rc;
   if (a.sums) return launch_reduce_fold(partials, rows, a.sums, 0.0, BnConvParams{}, FoldOut{}, Ci, Co, st);
   return launch_reduce_fold(partials, rows, red, (double)B * TV, a.p, a.out, Ci, Co, st);

@@ -191,14 +191,9 @@ size_t flat_gemm_lds(const FlatGemm& g, int MT, bool dual) {
 template <int MT, bool DUAL>
 int launch_flat_gemm_t(const FlatGemm& g, const char* what, hipStream_t st) {
   const size_t lds = flat_gemm_lds(g, MT, DUAL);
-  if (lds > (size_t)kMaxLdsBytes) return fail(COSKAD_ERR_SHAPE, "%s: LDS %zu too large", what, lds);
-  auto k = k_flat_gemm<MT, DUAL>;
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(COSKAD_ERR_LAUNCH, "%s: %zu B of LDS refused", what, lds);
   const long long ntiles = (long long)g.B * flat_chunks(g.TV);
   const int grid = (int)(ntiles < kFlatGrid ? ntiles : kFlatGrid);
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kFlatThreads), lds, st, g);
-  return check_launch(what);
+  return launch_lds<k_flat_gemm<MT, DUAL>>(what, dim3(grid), dim3(kFlatThreads), lds, st, g);
 }
 
 template <bool DUAL>

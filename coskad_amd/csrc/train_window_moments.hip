@@ -193,23 +193,15 @@ int launch_win_moments(const float* in, const float* Aw, const float* Tw, const 
   const int ntiles = ceil_div(rows, 16 * M::RT);
   const int grid = ntiles < kMomGrid ? ntiles : kMomGrid;
   *rows_out = grid;
-#define LAUNCH_MOM(CI)                                                                                             \
-  do {                                                                                                             \
-    auto k = k_win_moments<T, V, CI>;                                                                              \
-    if (lds > 64 * 1024 &&                                                                                         \
-        hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)   \
-      return fail(COSKAD_ERR_LAUNCH, "train moments (window): %zu B of LDS refused", lds);                         \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kWinBlock), lds, st, in, Aw, Tw, in_slope, partials, Zout, rows, need_x); \
-  } while (0)
-  {
-    ProbeScope probe(KID_FWD_MOMENTS, Ci, Ci, st);
-    if (Ci == 2) LAUNCH_MOM(2);
-    else if (Ci == 4) LAUNCH_MOM(4);
-    else if (Ci == 16) LAUNCH_MOM(16);
-    else LAUNCH_MOM(32);
-  }
+#define LAUNCH_MOM(CI)                                                                                                    \
+  return launch_lds<k_win_moments<T, V, CI>>("fwd_moments (window)", dim3(grid), dim3(kWinBlock), lds, st, in, Aw, Tw, in_slope, \
+                                             partials, Zout, rows, need_x)
+  ProbeScope probe(KID_FWD_MOMENTS, Ci, Ci, st);
+  if (Ci == 2) LAUNCH_MOM(2);
+  else if (Ci == 4) LAUNCH_MOM(4);
+  else if (Ci == 16) LAUNCH_MOM(16);
+  else LAUNCH_MOM(32);
 #undef LAUNCH_MOM
-  return check_launch("fwd_moments (window)");
 }
 
 #define COSKAD_TRAIN_WINDOW_TV(T_, V_, CALL)                              \
