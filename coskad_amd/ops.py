@@ -1566,6 +1566,19 @@ def gather_transform(xy, mats, index, T, V):
     return out
 
 
+def gather_frames(fxy, win_row, mats, index, T, V, step):
+    """The same batch [B, 2, T, V] from the device-resident FRAME table fxy [F, 2, V] (one row per trajectory frame): window s is
+    the rows win_row[s] + t * step, t < T; item i = transform i // N of window i % N with N = win_row.numel().  An index outside
+    [0, N * ntrans) and a window whose rows leave the table give a zero clip."""
+    F, N = fxy.shape[0], win_row.numel()
+    _chk(fxy, "fxy", (F, 2, V)); _chk(win_row, "win_row", (N,), dtype=torch.int32)
+    _chk(mats, "mats", (mats.shape[0], 3, 3)); _chk(index, "index", dtype=torch.int64)
+    B = index.numel()
+    out = torch.empty(B, 2, T, V, device=fxy.device, dtype=torch.float32)
+    call("coskad_gather_frames_f32", fxy, win_row, index, mats, out, B, N, F, mats.shape[0], T, V, step, _stream())
+    return out
+
+
 # ---- frame-level scoring of a validation pass (csrc/score_frames.hip; tables from utils/score_plan.ScorePlan) ----
 
 def score_person_frames(scores, win_ptr, win_idx):

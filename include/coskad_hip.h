@@ -494,6 +494,18 @@ int coskad_btlnk_bwd_chain_head_f32(const float* U, const float* W, const float*
 int coskad_gather_transform_f32(const float* xy, const long long* index, const float* mats, float* out, int B, int N,
                                 int ntrans, int TV, hipStream_t stream);
 
+/* The same items from a FRAME table: one normalised row per trajectory frame instead of one row per window, so a frame is stored
+ * once however many windows overlap it (coskad_amd.utils.dataset.PoseFramesRobust / FrameWindows).  With s = index[b] % N,
+ * tr = index[b] / N and r = win_row[s] + t step:
+ *   out[b, c, t, v] = (M[tr][c][0] x + M[tr][c][1] y) + M[tr][c][2],  (x, y) = fxy[r, 0 / 1, v],  c < 2, t < T, v < V
+ * in the association of coskad_gather_transform_f32: for the same normalised values the two entries give the same bits.
+ * fxy: [F, 2, V], win_row: [N] int32 (row of each window's first frame), index: [B] int64, mats: [ntrans, 3, 3], out: [B, 2, T, V]
+ * (16-byte aligned where T V % 4 == 0).  T, V and step are run-time values.  index[b] < 0, index[b] >= N ntrans and a window whose
+ * rows are not all inside [0, F) give a zero clip and read nothing out of bounds.  NULL pointers, a non-positive B, N, ntrans, T, V or
+ * step and F outside [1, 2^31) fail with COSKAD_ERR_ARG. */
+int coskad_gather_frames_f32(const float* fxy, const int* win_row, const long long* index, const float* mats, float* out, int B,
+                             int N, long long F, int ntrans, int T, int V, int step, hipStream_t stream);
+
 /* ---- frame-level scoring of a validation pass (csrc/score_frames.hip) ------------------------------- */
 
 /* Per-window scores -> frame-level AUC on index tables that coskad_amd.utils.score_plan.ScorePlan derives once from the window table

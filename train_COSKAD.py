@@ -63,7 +63,8 @@ def main():
                     (lambda: batches(val, bs, rank=rank, world=world)) if args.validation else None)
     else:
         # Morais-format trajectories (`dataset_path_to_robust`, train_COSKAD.py:80-85): window table resident in HBM,
-        # batches formed on the device; frame masks are read from args.gt_path by LitEncoder.post_processing
+        # batches formed on the device (`dataset_resident: 'frames'`: one row per trajectory frame resident instead, the same
+        # batches); frame masks are read from args.gt_path by LitEncoder.post_processing
         from coskad_amd.utils.dataset import get_dataset_and_loader
         args.exp_dir_scaler = args.ckpt_dir
         dataset_args.exp_dir = args.ckpt_dir
