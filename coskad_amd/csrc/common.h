@@ -22,6 +22,9 @@ namespace coskad {
 char* err_buf();
 int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
+// hyper[1] *= beta1, hyper[2] *= beta2 in device memory, one thread (heads.hip): the tick in front of every Adam update that reads
+// {lr, beta1^t, beta2^t} from `hyper`
+void launch_adam_tick(float* hyper, float beta1, float beta2, hipStream_t stream);
 
 #ifndef COSKAD_BLOCK
 #define COSKAD_BLOCK 512

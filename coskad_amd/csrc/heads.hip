@@ -338,6 +338,11 @@ __global__ void k_adam_tick(float* __restrict__ hyper, float beta1, float beta2)
     hyper[2] *= beta2;
   }
 }
+// the one launch of it: the Adam entry points that keep beta^t in device memory share this tick (csrc/grad_clip.hip's too), so the
+// eager and the captured pairs multiply up the same way
+void launch_adam_tick(float* hyper, float beta1, float beta2, hipStream_t stream) {
+  hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(64), 0, stream, hyper, beta1, beta2);
+}
 
 __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
@@ -514,7 +519,7 @@ int coskad_adam_pow_f32(float* p, const float* g, float* m, float* v, const floa
 int coskad_adam_dev_f32(float* p, const float* g, float* m, float* v, const float* mask, size_t n, float* hyper,
                         float beta1, float beta2, float eps, float gscale, float reg_coef, hipStream_t stream) {
   if (!p || !g || !m || !v || !hyper || n == 0) return fail(COSKAD_ERR_ARG, "adam_dev: bad argument");
-  hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(64), 0, stream, hyper, beta1, beta2);
+  launch_adam_tick(hyper, beta1, beta2, stream);
   hipLaunchKernelGGL(k_adam_dev, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, g, m, v, mask, n, hyper,
                      beta1, beta2, eps, gscale, reg_coef);
   return check_launch("adam_dev");

@@ -38,8 +38,46 @@ def _joints(args) -> int:
     return 17
 
 
+def step_knobs(args) -> Dict:
+    """Lightning's Trainer arguments that act on the optimisation step, under Lightning's names (the reference hands every yaml
+    key to pl.Trainer.from_argparse_args, train_COSKAD.py:75-78) -> the step classes' keywords"""
+    return {"grad_clip_val": getattr(args, "gradient_clip_val", None) or 0.0,
+            "grad_clip_algorithm": getattr(args, "gradient_clip_algorithm", None) or "norm",
+            "accumulate": int(getattr(args, "accumulate_grad_batches", None) or 1)}
+
+
+# wrapper state that is no buffer of the model and that a resumed run needs (Trainer.fit(ckpt_path=...))
+_RESUME_ATTRS = ("_epoch", "_temp", "n_samples", "_reg_last", "warmup_counter")
+
+
 class LitEncoder(nn.Module):
     _reg_last = None      # the regulariser's value at the last logging step (training_step reuses it in between)
+    n_samples = None
+
+    # ---- what a checkpoint carries beside the model's state_dict, and its way back (Trainer.fit(ckpt_path=...)) ------------
+    def optimizer_state(self) -> Dict:
+        return self._engine.state_dict()
+
+    def load_optimizer_state(self, sd: Dict) -> None:
+        self._engine.load_state_dict(sd)
+
+    def resume_state(self) -> Dict:
+        return {k: (v.detach().cpu().clone() if torch.is_tensor(v) else v)
+                for k, v in ((k, getattr(self, k)) for k in _RESUME_ATTRS if hasattr(self, k))}
+
+    def load_resume_state(self, state: Dict) -> None:
+        dev = next(self.model.parameters()).device
+        for k, v in state.items():
+            setattr(self, k, v.to(dev) if torch.is_tensor(v) else v)
+
+    def flush_gradients(self) -> None:
+        """the update of a pending accumulation group (Lightning steps on the last batch of an epoch whatever its index)"""
+        self._engine.flush()
+
+    def _log_grad_norm(self, step, batch_idx: int) -> None:
+        """`grad_norm`, the unclipped norm of the last update, when clipping by norm -- the only host read of it"""
+        if batch_idx % 20 == 0 and step.clip_val > 0 and step.clip_mode == 'norm':
+            self.log("grad_norm", step.last_grad_norm)
 
     def __init__(self, args: Namespace, hyperbolic: Optional[bool] = None) -> None:
         super().__init__()
@@ -72,13 +110,19 @@ class LitEncoder(nn.Module):
         self.logged[name] = float(value)
 
     # ---- centre initialisation (staticCenter.py:95-130, dynamicCenter.py:76-102, hyperbolic_encoder.py:85-135)
-    def setup(self, stage: str = None, train_loader: Optional[Callable[[], Iterable]] = None) -> None:
+    def setup(self, stage: str = None, train_loader: Optional[Callable[[], Iterable]] = None, resume: bool = False) -> None:
+        """resume: build the step only; the centre, its covariance and the wrapper's own state come from the checkpoint"""
         if stage != "fit":
             return
+        maha = self.distance == 'mahalanobis' and not self.hyperbolic
+        if not resume:
+            self._init_center(train_loader, maha)
+        self._build_step(maha)
+
+    def _init_center(self, train_loader, maha: bool) -> None:
         dev = next(self.model.parameters()).device
         L = self.model.latent_dim
         acc = torch.zeros(ops.head_slots(L), device=dev)
-        maha = self.distance == 'mahalanobis' and not self.hyperbolic
         gram = torch.zeros(L, L, device=dev) if maha else None
         eye = torch.eye(L, device=dev) if maha else None
         self.model.eval()
@@ -108,6 +152,8 @@ class LitEncoder(nn.Module):
             from .trainer import inv_cov_from_moments
             mu = self.model.c if self.static_center else self._temp
             self.model.inv_cov_matrix.copy_(inv_cov_from_moments(gram, acc, mu, L))
+
+    def _build_step(self, maha: bool) -> None:
         self.model.train()
         # `sync_batchnorm` (not a key of the reference's yamls, whose DDP keeps per-rank BatchNorm statistics): optional SyncBN
         extra = {"sync_bn": True} if bool(getattr(self.args, "sync_batchnorm", False)) else {}
@@ -118,7 +164,8 @@ class LitEncoder(nn.Module):
         # kernels where those are built unless the yaml says `fused_window: false` (then: the composed path)
         extra["fused_window"] = bool(getattr(self.args, "fused_window", True))
         self._engine = make_train_step(self.model, lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)),
-                                     head="poincare" if self.hyperbolic else ("mahalanobis" if maha else "euclidean"), **extra)
+                                     head="poincare" if self.hyperbolic else ("mahalanobis" if maha else "euclidean"), **extra,
+                                     **step_knobs(self.args))
         self._epoch = 0
 
     # ---- one optimisation step -----------------------------------------------------------
@@ -134,6 +181,7 @@ class LitEncoder(nn.Module):
             name = "poincare_loss" if self.hyperbolic else "hypersphere_loss"
             self.log(name, stats[0]); self.log("regularization", self._reg_last)
             self.log("loss", float(loss))
+        self._log_grad_norm(self._engine, batch_idx)
         return loss
 
     def on_train_epoch_end(self) -> None:
@@ -279,6 +327,35 @@ class _AutogradLit(LitEncoder):
         object.__setattr__(self, "_engine", self)   # the Trainer's plateau rule calls _engine.set_lr (not a submodule)
         self._opt = None
         self._flat = None
+        self._micro = 0                    # backward passes of the pending accumulation group (autograd route)
+
+    # the step the clip settings and the last gradient norm live on: the flat step, or this wrapper on the autograd route
+    @property
+    def clip_val(self) -> float:
+        return self._knobs["grad_clip_val"]
+
+    @property
+    def clip_mode(self) -> str:
+        return self._knobs["grad_clip_algorithm"]
+
+    def optimizer_state(self) -> Dict:
+        if self._flat is not None:
+            return self._flat.state_dict()
+        return dict(self._opt.state_dict(), coskad={"micro_step": self._micro})
+
+    def load_optimizer_state(self, sd: Dict) -> None:
+        if self._flat is not None:
+            return self._flat.load_state_dict(sd)
+        from .trainer import _load_torch_optimizer
+        _load_torch_optimizer(self._opt, sd)
+
+    def flush_gradients(self) -> None:
+        if self._flat is not None:
+            self._flat.flush()
+        elif self._micro:
+            from .trainer import _clipped_update
+            _clipped_update(list(self.model.parameters()), self._opt, None, self.clip_val, self.clip_mode, self.last_grad_norm)
+            self._micro = 0
 
     def set_lr(self, lr: float) -> None:
         if self._flat is not None:
@@ -287,18 +364,28 @@ class _AutogradLit(LitEncoder):
         for g in self._opt.param_groups:
             g['lr'] = lr
 
+    def _on_device(self) -> bool:
+        """the model sits on the GPU: the flat step is then asked for (a model left on the host takes the autograd route)"""
+        return next(self.model.parameters()).is_cuda
+
     def _make_optimiser(self, mode: str, **weights) -> None:
         """The flat-buffer step with the fused Adam (trainer.STSAETrainStep: no autograd around the encoder / decoder chains)
         where the model is within its kernels; torch autograd + torch.optim.Adam over the module surface otherwise."""
-        from .trainer import make_decoder_step
+        from .trainer import make_decoder_step, _check_accumulate, _check_clip
         self._flat = None
+        self._knobs = step_knobs(self.args)
+        self._knobs["grad_clip_val"], self._knobs["grad_clip_algorithm"] = _check_clip(self._knobs["grad_clip_val"],
+                                                                                       self._knobs["grad_clip_algorithm"])
+        self._knobs["accumulate"] = _check_accumulate(self._knobs["accumulate"])
+        self.last_grad_norm = torch.zeros(1, device=next(self.model.parameters()).device)
         # `flat_wide_latent` (not a key of the reference's yamls; default on): false keeps a model with latent_dim > 16 on the autograd route
         # `flat_gaussian_head` (likewise): false keeps the `distribution: 'normal'` head of the flat step under its local autograd graph
-        if next(self.model.parameters()).is_cuda:
+        if self._on_device():
             self._flat = make_decoder_step(self.model, mode, fused_window=bool(getattr(self.args, "fused_window", True)),
                                            wide_latent=bool(getattr(self.args, "flat_wide_latent", True)),
                                            gaussian_head=bool(getattr(self.args, "flat_gaussian_head", True)),
-                                           lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)), **weights)
+                                           lr=self.learning_rate, alpha=float(getattr(self.args, "alpha", 0.0)), **weights,
+                                           **self._knobs)
         if self._flat is None:
             self._opt = torch.optim.Adam(self.model.parameters(), lr=self.learning_rate)
         if parallel.rank() == 0:           # one line of the training log: which step and which stage forms drive this model
@@ -312,10 +399,15 @@ class _AutogradLit(LitEncoder):
         return 0.5 * sum((p ** 2).sum() for p in ps) / len(ps)
 
     def _optimise(self, loss: torch.Tensor) -> None:
-        self._opt.zero_grad(set_to_none=True)
-        loss.backward()
-        parallel.allreduce_grads_mean_(list(self.model.parameters()))     # one flat bucket per step
-        self._opt.step()
+        """backward of loss / accumulate into .grad (no zero_grad inside a group); the group's last call averages the gradients over
+        ranks (one flat bucket per update), clips them and steps"""
+        k = self._knobs["accumulate"]
+        if self._micro == 0:
+            self._opt.zero_grad(set_to_none=True)
+        (loss if k == 1 else loss / k).backward()
+        self._micro += 1
+        if self._micro == k:
+            self.flush_gradients()
 
     def validation_step(self, batch, batch_idx: int = 0):
         dev = self.model.c.device
@@ -356,18 +448,19 @@ class LitAutoEncoder(_AutogradLit):
         z, x_rec = self.model(x[0])
         return x_rec, z, x[0], x[1], x[2], x[3]
 
-    def setup(self, stage: str = None, train_loader=None) -> None:
+    def setup(self, stage: str = None, train_loader=None, resume: bool = False) -> None:
         if stage != "fit":
             return
         dev = self.model.c.device
         acc = torch.zeros(ops.head_slots(self.model.latent_dim), device=dev)
         self.model.eval()
         with torch.no_grad():
-            for batch in train_loader():
+            for batch in (train_loader() if not resume else ()):        # (resume: the centre comes from the checkpoint)
                 z, _ = self.model(batch[0].to(dev))
                 ops.mse_head(z.contiguous(), self.model.c, need_grad=False, acc=acc)
-        parallel.allreduce_sum_(acc)
-        self.model.c.copy_(ops.center_finalize(acc, self.eps, self.model.latent_dim))
+        if not resume:
+            parallel.allreduce_sum_(acc)
+            self.model.c.copy_(ops.center_finalize(acc, self.eps, self.model.latent_dim))
         self.model.train()
         self._make_optimiser('ae', lambda_=self.lambda_)
 
@@ -382,6 +475,7 @@ class LitAutoEncoder(_AutogradLit):
                 self.log("loss", loss)
                 self.log("reconstruction_loss", out['rec']); self.log("hypersphere_loss", out['head'])
                 self.log("regularization", self._reg_last)
+            self._log_grad_norm(self._flat, batch_idx)
             return loss
         z, x_rec = self.model(x)
         loss_reco = F.mse_loss(x_rec, x)
@@ -392,6 +486,7 @@ class LitAutoEncoder(_AutogradLit):
         if batch_idx % 20 == 0:
             self.log("loss", loss.detach()); self.log("reconstruction_loss", loss_reco.detach())
             self.log("hypersphere_loss", loss_h.detach()); self.log("regularization", loss_reg.detach())
+        self._log_grad_norm(self, batch_idx)
         return loss.detach()
 
     # score type: the wrapper's own validation calls windows_based_loss_rec_and_hy with its default 'rec'
@@ -427,7 +522,7 @@ class LitVAE(_AutogradLit):
         z, x_rec, _ = self.model(x[0])
         return z, x_rec, x[1], x[2], x[3]
 
-    def setup(self, stage: str = None, train_loader=None) -> None:
+    def setup(self, stage: str = None, train_loader=None, resume: bool = False) -> None:
         if stage == "fit":
             self.model.train()
             self._make_optimiser('vae', phi=self.phi, beta=self.beta, gamma=self.gamma)
@@ -448,6 +543,7 @@ class LitVAE(_AutogradLit):
                 self.log("loss", loss)
                 self.log("reconstruction_loss", out['rec']); self.log("kl_loss", out['head'])
                 self.log("exp_dist_loss", out['exp']); self.log("regularization", self._reg_last)
+            self._log_grad_norm(self._flat, batch_idx)
             return loss
         z, x_rec, (q, p, kappa) = self.model(x)
         with torch.no_grad():
@@ -467,6 +563,7 @@ class LitVAE(_AutogradLit):
             self.log("loss", loss.detach()); self.log("reconstruction_loss", loss_rec.detach())
             self.log("kl_loss", loss_kl.detach()); self.log("exp_dist_loss", loss_exp.detach())
             self.log("regularization", loss_reg.detach())
+        self._log_grad_norm(self, batch_idx)
         return loss.detach()
 
     def on_train_epoch_end(self) -> None:                    # update_state (:110-116)
@@ -499,35 +596,82 @@ class Trainer:
         self.max_epochs, self.ckpt_dir, self.save_top_k, self.monitor = max_epochs, ckpt_dir, save_top_k, monitor
         self.history: List[Dict[str, float]] = []
         self._best: List[Tuple[float, str]] = []
+        # the epoch a train_loader() call is for, set before every such call (a loader that reshuffles per epoch keys on it and can
+        # then be resumed); `stage`: 'setup' while the model's setup() runs (its centre pass reads the loader too), then 'fit'
+        self.current_epoch, self.stage = 0, 'setup'
+        self.global_step = 0               # optimiser updates so far
+        self._sched = {"best": -float("inf"), "num_bad_epochs": 0, "lr": None}     # the plateau rule's state
 
-    def fit(self, model: LitEncoder, train_loader, val_loader=None) -> None:
+    def fit(self, model: LitEncoder, train_loader, val_loader=None, ckpt_path: Optional[str] = None) -> None:
+        """ckpt_path (or the yaml key `resume_from_checkpoint`, Lightning 1.6's name): continue the run that wrote that checkpoint,
+        at the epoch after it -- model, optimiser, plateau rule, top-k list, wrapper state and torch's RNG states restored"""
+        ckpt_path = ckpt_path or getattr(getattr(model, "args", None), "resume_from_checkpoint", None)
+        ck = torch.load(ckpt_path, map_location="cpu", weights_only=False) if ckpt_path else None
+        if ck is not None and "optimizer_states" not in ck:
+            raise ValueError(f"{ckpt_path}: no `optimizer_states` (a checkpoint written before training could be resumed holds the "
+                             "model only): it loads through load_checkpoint / Trainer.predict, but a run cannot continue from it")
         # DDP wrap semantics (train_COSKAD.py:75-78): every rank starts from rank 0's parameters and buffers
         parallel.broadcast_module_(model.model)
-        model.setup("fit", train_loader)
+        start = 0 if ck is None else int(ck["epoch"]) + 1
+        self.current_epoch, self.stage = start, 'setup'
+        if ck is None:
+            self._sched = {"best": -float("inf"), "num_bad_epochs": 0, "lr": None}
+            model.setup("fit", train_loader)
+        else:
+            # Lightning restores the module after setup(): the checkpoint's buffers win, so setup skips its centre pass; the
+            # state goes in place into whatever the step re-homed the parameters in
+            model.setup("fit", train_loader, resume=True)
+            self._restore(model, ck)
+        self.stage = 'fit'
         sched = model.configure_optimizers()["lr_scheduler"]
-        best, bad, lr = -float("inf"), 0, model.learning_rate
-        for epoch in range(self.max_epochs):
+        st = self._sched
+        if st["lr"] is None:
+            st["lr"] = model.learning_rate
+        k = int(getattr(getattr(model, "args", None), "accumulate_grad_batches", None) or 1)
+        flush = getattr(model, "flush_gradients", None)
+        for epoch in range(start, self.max_epochs):
             model.model.train()
+            self.current_epoch = epoch
+            n = 0
             for i, batch in enumerate(train_loader()):
                 model.training_step(batch, i)
+                n += 1
+            if flush is not None:          # a pending accumulation group: Lightning steps on the epoch's last batch
+                flush()
+            self.global_step += -(-n // k)
             model.on_train_epoch_end()
             rec = dict(model.logged, epoch=epoch)
             if val_loader is not None:
                 auc = self.validate(model, val_loader)
                 rec["validation_auc"] = auc
-                if auc > best:
-                    best, bad = auc, 0
+                if auc > st["best"]:
+                    st["best"], st["num_bad_epochs"] = auc, 0
                 else:
-                    bad += 1
-                    if bad > sched["patience"]:
-                        lr = max(lr * sched["factor"], sched["min_lr"])
-                        model._engine.set_lr(lr)
-                        bad = 0
+                    st["num_bad_epochs"] += 1
+                    if st["num_bad_epochs"] > sched["patience"]:
+                        st["lr"] = max(st["lr"] * sched["factor"], sched["min_lr"])
+                        model._engine.set_lr(st["lr"])
+                        st["num_bad_epochs"] = 0
                 self._checkpoint(model, epoch, auc)
             elif "loss" in rec:
                 # no validation: ModelCheckpoint(monitor='loss', mode='min') (train_COSKAD.py:70-73)
                 self._checkpoint(model, epoch, rec["loss"], monitor="loss", mode="min")
             self.history.append(rec)
+
+    def _restore(self, model: LitEncoder, ck: Dict) -> None:
+        sd = {k[len("model."):]: v for k, v in ck["state_dict"].items() if k.startswith("model.")}
+        model.model.load_state_dict(sd, strict=True)
+        model.load_optimizer_state(ck["optimizer_states"][0])
+        self._sched = dict(ck["lr_schedulers"][0])
+        self.global_step = int(ck.get("global_step", 0))
+        own = ck.get("coskad", {})
+        self._best = [tuple(b) for b in own.get("best_checkpoints", [])]
+        if hasattr(model, "load_resume_state"):
+            model.load_resume_state(own.get("wrapper", {}))
+        if own.get("rng_cpu") is not None:
+            torch.set_rng_state(own["rng_cpu"])
+        if own.get("rng_device") is not None and torch.cuda.is_available():
+            torch.cuda.set_rng_state(own["rng_device"])
 
     def validate(self, model: LitEncoder, loader) -> float:
         # Lightning's DDP wrap broadcasts rank 0's buffers (BatchNorm running statistics, the centre) before every
@@ -556,19 +700,30 @@ class Trainer:
             return
         os.makedirs(self.ckpt_dir, exist_ok=True)
         path = os.path.join(self.ckpt_dir, f"epoch={epoch}-{monitor or self.monitor}={value:.4f}.ckpt")
-        save_checkpoint(model, path, epoch)
+        # the top-k list first, so that the checkpoint carries the list it belongs to (a resumed run prunes as this one would)
         self._best.append((value, path))
         self._best.sort(key=lambda t: -t[0] if mode == "max" else t[0])
-        for _, p in self._best[self.save_top_k:]:
+        dropped, self._best = self._best[self.save_top_k:], self._best[:self.save_top_k]
+        if all(p != path for _, p in dropped):
+            extra = {"lr_schedulers": [dict(self._sched)], "global_step": self.global_step,
+                     "coskad": {"best_checkpoints": [list(b) for b in self._best],
+                                "wrapper": model.resume_state() if hasattr(model, "resume_state") else {},
+                                "rng_cpu": torch.get_rng_state(),
+                                "rng_device": torch.cuda.get_rng_state() if torch.cuda.is_available() else None}}
+            if hasattr(model, "optimizer_state"):
+                extra["optimizer_states"] = [model.optimizer_state()]
+            save_checkpoint(model, path, epoch, extra)
+        for _, p in dropped:
             if os.path.exists(p):
                 os.remove(p)
-        self._best = self._best[:self.save_top_k]
 
 
-def save_checkpoint(model: LitEncoder, path: str, epoch: int = 0) -> None:
-    """Lightning layout: state_dict keys prefixed `model.`, hyper_parameters = the args Namespace."""
+def save_checkpoint(model: LitEncoder, path: str, epoch: int = 0, extra: Optional[Dict] = None) -> None:
+    """Lightning layout: state_dict keys prefixed `model.`, hyper_parameters = the args Namespace; `extra`: what the Trainer adds
+    for resuming (optimizer_states, lr_schedulers, global_step, and under `coskad` its top-k list, the wrapper's own state and
+    torch's RNG states)."""
     sd = {"model." + k: v.detach().cpu().clone() for k, v in model.model.state_dict().items()}
-    torch.save({"state_dict": sd, "hyper_parameters": {"args": vars(model.args)}, "epoch": epoch}, path)
+    torch.save(dict({"state_dict": sd, "hyper_parameters": {"args": vars(model.args)}, "epoch": epoch}, **(extra or {})), path)
 
 
 def load_checkpoint(model: LitEncoder, path: str) -> None:

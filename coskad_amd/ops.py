@@ -1555,6 +1555,59 @@ def adam_dev(p, g, m, v, mask, hyper, beta1, beta2, eps, gscale=1.0, reg_coef=0.
     call("coskad_adam_dev_f32", p, g, m, v, mask, p.numel(), hyper, beta1, beta2, eps, gscale, reg_coef, _stream())
 
 
+CLIP_PARTIALS = 256            # fp64 entries of grad_sqnorm's partials (csrc/grad_clip.hip: kClipPartials)
+CLIP_MODES = {'norm': 1, 'value': 2}
+
+
+def grad_sqnorm(g, p, mask, gscale=1.0, reg_coef=0.0, partials=None):
+    """partials [256] float64 whose sum is |g * gscale + reg_coef * mask * p|^2, the gradient Adam applies (fixed order: repeated
+    calls agree bit for bit); adam_clip_pow / adam_clip_dev read them."""
+    _chk(g, "g"); _chk(p, "p", g.shape); _chk(mask, "mask", g.shape, optional=True)
+    if partials is None:
+        partials = torch.empty(CLIP_PARTIALS, device=g.device, dtype=torch.float64)
+    _chk(partials, "partials", (CLIP_PARTIALS,), dtype=torch.float64)
+    call("coskad_grad_sqnorm_f32", g, p, mask, g.numel(), gscale, reg_coef, partials, _stream())
+    return partials
+
+
+def _chk_clip(p, g, m, v, mask, partials, mode, norm_out) -> int:
+    for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _chk(t, n, p.shape)
+    _chk(mask, "mask", p.shape, optional=True)
+    if mode not in CLIP_MODES:
+        raise ValueError(f"clip mode {mode!r}: one of {sorted(CLIP_MODES)}")
+    _chk(partials, "partials", (CLIP_PARTIALS,), dtype=torch.float64, optional=mode == 'value')
+    _chk(norm_out, "norm_out", (1,), optional=True)
+    return CLIP_MODES[mode]
+
+
+def adam_clip_pow(p, g, m, v, mask, lr, beta1, beta2, eps, b1pow, b2pow, partials, clip_val, mode='norm', norm_out=None,
+                  gscale=1.0, reg_coef=0.0):
+    """adam_pow with the applied gradient clipped: mode 'norm' by the global norm behind grad_sqnorm's `partials` (the unclipped
+    norm goes to norm_out [1]), mode 'value' by clamping to [-clip_val, clip_val] (no partials)."""
+    k = _chk_clip(p, g, m, v, mask, partials, mode, norm_out)
+    note_raw_write()
+    call("coskad_adam_clip_pow_f32", p, g, m, v, mask, p.numel(), lr, beta1, beta2, eps, b1pow, b2pow, gscale, reg_coef, partials,
+         clip_val, k, norm_out, _stream())
+
+
+def adam_clip_dev(p, g, m, v, mask, hyper, beta1, beta2, eps, partials, clip_val, mode='norm', norm_out=None, gscale=1.0,
+                  reg_coef=0.0):
+    """adam_dev with the same clipping ({lr, beta1^t, beta2^t} in the device tensor `hyper`: replayable in a hipGraph)."""
+    k = _chk_clip(p, g, m, v, mask, partials, mode, norm_out)
+    _chk(hyper, "hyper", (4,))
+    note_raw_write()
+    call("coskad_adam_clip_dev_f32", p, g, m, v, mask, p.numel(), hyper, beta1, beta2, eps, gscale, reg_coef, partials, clip_val, k,
+         norm_out, _stream())
+
+
+def grad_accum(acc, g, first: bool):
+    """acc = g (first) or acc + g: the gradient sum over the micro-batches of one accumulation group"""
+    _chk(acc, "acc"); _chk(g, "g", acc.shape)
+    call("coskad_grad_accum_f32", acc, g, acc.numel(), 1 if first else 0, _stream())
+    return acc
+
+
 def gather_transform(xy, mats, index, T, V):
     """Batch [B, 2, T, V] from the device-resident window table xy [N, 2, T*V]: item i = transform i // N of window
     i % N (utils/dataset.py:65-77; PoseTransform of utils/dataset_utils.py:272-310)."""

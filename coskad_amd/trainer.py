@@ -618,13 +618,39 @@ def _projector(model, fp: "FlatParams", ws: engine.Workspace):
     return _StackedHeads(model, fp, ws)
 
 
+def _check_clip(val, algorithm):
+    """(clip value, 0.0 = off; algorithm) of the keywords grad_clip_val / grad_clip_algorithm, Lightning's gradient_clip_val /
+    gradient_clip_algorithm (None: 'norm')"""
+    import math
+    val = 0.0 if val is None else float(val)
+    algorithm = 'norm' if algorithm is None else str(algorithm)
+    if not math.isfinite(val) or val < 0:
+        raise ValueError(f"grad_clip_val must be finite and >= 0 (0 / None: off), got {val}")
+    if algorithm not in ops.CLIP_MODES:
+        raise ValueError(f"grad_clip_algorithm {algorithm!r}: 'norm' or 'value'")
+    return val, algorithm
+
+
+def _check_accumulate(k) -> int:
+    if k is None:
+        return 1
+    if int(k) != k or int(k) < 1:
+        raise ValueError(f"accumulate must be a whole number >= 1, got {k!r}")
+    return int(k)
+
+
 class _FlatStep:
     """What the autograd-free steps share: the model's parameters re-homed in flat buffers, the bottleneck projector, Adam's moments and
     the fused update, the regulariser, the data-parallel world."""
 
     use_graph = False
 
-    def __init__(self, model, lr: float, alpha: float, betas, eps: float, process_group) -> None:
+    def __init__(self, model, lr: float, alpha: float, betas, eps: float, process_group, grad_clip_val=0.0,
+                 grad_clip_algorithm: str = 'norm', accumulate: int = 1) -> None:
+        """grad_clip_val, grad_clip_algorithm, accumulate: Lightning's gradient_clip_val / gradient_clip_algorithm /
+        accumulate_grad_batches (0 / None: no clipping; 1: an update per step)"""
+        self.accumulate = _check_accumulate(accumulate)
+        self.clip_val, self.clip_mode = _check_clip(grad_clip_val, grad_clip_algorithm)
         self.model, self.alpha, self.lr = model, float(alpha), float(lr)
         self.beta1, self.beta2, self.eps = float(betas[0]), float(betas[1]), float(eps)
         self.pg = process_group
@@ -636,27 +662,158 @@ class _FlatStep:
         self.reg_scale = 0.5 / self.fp.n_reg_tensors          # calc_reg_loss value = reg_scale * sum p^2
         self.reg_coef = self.alpha * 2.0 * self.reg_scale      # its gradient coefficient, times alpha
         self.steps = 0
+        self.updates = 0                   # optimiser updates so far (= steps unless gradients accumulate)
+        # gradient accumulation: the backward kernels overwrite fp.grad, so every micro-step adds it into `acc`; `_micro` counts the
+        # micro-steps of the pending group
+        self.acc = torch.zeros_like(self.fp.grad) if self.accumulate > 1 else None
+        self._micro = 0
+        dev = self.fp.flat.device
+        self.clip_partials = torch.zeros(ops.CLIP_PARTIALS, device=dev, dtype=torch.float64)
+        self.last_grad_norm = torch.zeros(1, device=dev, dtype=torch.float32)       # unclipped norm of the last update (norm mode)
 
     def set_lr(self, lr: float) -> None:
         self.lr = float(lr)
+
+    def set_gradient_clip(self, val, algorithm: Optional[str] = None) -> None:
+        """change the clip value (0 / None: off), and the algorithm when given, between steps"""
+        val, mode = _check_clip(val, self.clip_mode if algorithm is None else algorithm)
+        if self.use_graph and getattr(self, "_graph", None) is not None and (val, mode) != (self.clip_val, self.clip_mode):
+            raise ValueError("use_graph: the captured step holds the clip value as a launch argument; set it before the first step")
+        self.clip_val, self.clip_mode = val, mode
 
     def reg_loss(self) -> Tensor:
         """utils/model_utils.py::calc_reg_loss value of the current parameters (1-element tensor)."""
         return ops.sqnorm(self.fp.flat, self.fp.reg_mask, self.reg_scale)
 
-    def _adam(self) -> None:
+    def _adam(self, grad: Optional[Tensor] = None, gscale: Optional[float] = None, reg_coef: Optional[float] = None) -> None:
         """torch.optim.Adam step on the flat buffers with alpha * calc_reg_loss' gradient and the 1 / world of the gradient
         all-reduce folded in.  Outside hipGraph capture lr and the running products beta^t come from the host (one launch);
-        a captured step keeps them in device memory (`hyper`: a one-thread launch advances beta^t in front of the update)."""
+        a captured step keeps them in device memory (`hyper`: a one-thread launch advances beta^t in front of the update).
+        grad, gscale, reg_coef: another gradient buffer, its scale and the regulariser's coefficient (the accumulated one's).
+        With clipping on, the update runs on the
+        clipping forms of the same two kernels; by norm, one launch in front of them leaves the squared norm's partials."""
+        g = self.fp.grad if grad is None else grad
+        gscale = 1.0 / self.world if gscale is None else gscale
+        reg_coef = self.reg_coef if reg_coef is None else reg_coef
+        fp, clip = self.fp, self.clip_val > 0
+        if clip and self.clip_mode == 'norm':
+            ops.grad_sqnorm(g, fp.flat, fp.reg_mask, gscale, reg_coef, partials=self.clip_partials)
         if self.use_graph:
-            ops.adam_dev(self.fp.flat, self.fp.grad, self.m, self.v, self.fp.reg_mask, self.hyper, self.beta1,
-                         self.beta2, self.eps, gscale=1.0 / self.world, reg_coef=self.reg_coef)
+            if clip:
+                ops.adam_clip_dev(fp.flat, g, self.m, self.v, fp.reg_mask, self.hyper, self.beta1, self.beta2, self.eps,
+                                  self.clip_partials, self.clip_val, self.clip_mode, self.last_grad_norm, gscale=gscale,
+                                  reg_coef=reg_coef)
+            else:
+                ops.adam_dev(fp.flat, g, self.m, self.v, fp.reg_mask, self.hyper, self.beta1,
+                             self.beta2, self.eps, gscale=gscale, reg_coef=reg_coef)
+            return
+        import numpy as np
+        b1p, b2p = getattr(self, "_bpow", (np.float32(1.0), np.float32(1.0)))
+        self._bpow = (np.float32(b1p * np.float32(self.beta1)), np.float32(b2p * np.float32(self.beta2)))   # fp32, as the device tick
+        self.updates += 1
+        if clip:
+            ops.adam_clip_pow(fp.flat, g, self.m, self.v, fp.reg_mask, self.lr, self.beta1, self.beta2, self.eps,
+                              float(self._bpow[0]), float(self._bpow[1]), self.clip_partials, self.clip_val, self.clip_mode,
+                              self.last_grad_norm, gscale=gscale, reg_coef=reg_coef)
         else:
-            import numpy as np
-            b1p, b2p = getattr(self, "_bpow", (np.float32(1.0), np.float32(1.0)))
-            self._bpow = (np.float32(b1p * np.float32(self.beta1)), np.float32(b2p * np.float32(self.beta2)))   # fp32, as the device tick
-            ops.adam_pow(self.fp.flat, self.fp.grad, self.m, self.v, self.fp.reg_mask, self.lr, self.beta1, self.beta2, self.eps,
-                         float(self._bpow[0]), float(self._bpow[1]), gscale=1.0 / self.world, reg_coef=self.reg_coef)
+            ops.adam_pow(fp.flat, g, self.m, self.v, fp.reg_mask, self.lr, self.beta1, self.beta2, self.eps,
+                         float(self._bpow[0]), float(self._bpow[1]), gscale=gscale, reg_coef=reg_coef)
+
+    def _micro_step(self) -> None:
+        """accumulate > 1, after a backward: fp.grad joins the group's sum; the group's last micro-step updates"""
+        ops.grad_accum(self.acc, self.fp.grad, first=self._micro == 0)
+        self._micro += 1
+        if self._micro == self.accumulate:
+            self.flush()
+
+    def flush(self) -> bool:
+        """Apply a pending group of fewer than `accumulate` micro-steps (Lightning steps on the last batch of an epoch whatever its
+        index), each still counting 1 / accumulate -> whether an update was made.  The regulariser is part of every micro-batch's
+        loss, so j micro-steps carry j / accumulate of its gradient: all of it for a whole group (the factor is then exactly 1).
+        One all-reduce of the accumulated buffer per update; none on the micro-steps before it (Lightning's no_sync)."""
+        if self._micro == 0:
+            return False
+        if self.world > 1:
+            dist.all_reduce(self.acc, group=self.pg)
+        self._adam(self.acc, 1.0 / (self.world * self.accumulate), self.reg_coef * (self._micro / self.accumulate))
+        self._micro = 0
+        return True
+
+    def _update(self) -> None:
+        """after a backward that left this rank's gradient in fp.grad, all of it at once"""
+        if self.accumulate > 1:
+            return self._micro_step()
+        if self.world > 1:
+            dist.all_reduce(self.fp.grad, group=self.pg)                          # SUM; the 1 / W is folded into Adam
+        self._adam()
+
+    # -- optimiser state in torch.optim.Adam's layout -------------------------------------------------------------------------
+    def _beta_pows(self):
+        import numpy as np
+        if self.use_graph:
+            h = self.hyper.detach().cpu().numpy()
+            return np.float32(h[1]), np.float32(h[2])
+        return getattr(self, "_bpow", (np.float32(1.0), np.float32(1.0)))
+
+    def state_dict(self) -> dict:
+        """torch.optim.Adam's state_dict of this step (per parameter in named_parameters() order: step, exp_avg, exp_avg_sq as copies
+        of the flat moments' views; one param group), loadable into torch.optim.Adam(model.parameters()); beside it, under 'coskad',
+        what a bit-exact continuation needs and torch does not keep: the fp32 running products beta^t and the micro-step counter."""
+        fp = self.fp
+        updates = self.steps if self.use_graph else self.updates
+        state = {}
+        if updates > 0:
+            for i, n in enumerate(fp.names):
+                off, shape = fp.offsets[n], fp.views[n].shape
+                k = fp.views[n].numel()
+                state[i] = {'step': torch.tensor(float(updates)), 'exp_avg': self.m[off:off + k].view(shape).clone(),
+                            'exp_avg_sq': self.v[off:off + k].view(shape).clone()}
+        group = {'lr': self.lr, 'betas': (self.beta1, self.beta2), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False,
+                 'params': list(range(len(fp.names)))}
+        b1p, b2p = self._beta_pows()
+        return {'state': state, 'param_groups': [group],
+                'coskad': {'beta_pows': (float(b1p), float(b2p)), 'micro_step': self._micro, 'updates': updates,
+                           'last_grad_norm': float(self.last_grad_norm)}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """state_dict()'s inverse, in place into the flat moments; takes torch.optim.Adam's state_dict of the same parameters too (the
+        running products are then multiplied up in fp32, step by step, as this step would have)."""
+        import numpy as np
+        fp = self.fp
+        groups = sd['param_groups']
+        if len(groups) != 1 or len(groups[0]['params']) != len(fp.names):
+            raise ValueError(f"optimizer state: expected one param group of {len(fp.names)} parameters")
+        g = groups[0]
+        if g.get('amsgrad') or g.get('weight_decay') or g.get('maximize'):
+            raise ValueError("optimizer state: the fused Adam has no amsgrad, weight_decay or maximize")
+        own = sd.get('coskad', {})
+        if own.get('micro_step', 0):
+            raise ValueError("optimizer state: saved inside an accumulation group (mid-epoch checkpoints are not supported)")
+        state = sd['state']
+        steps = {int(float(s['step'])) for s in state.values()}
+        if len(steps) > 1 or (state and len(state) != len(fp.names)):
+            raise ValueError("optimizer state: every parameter must carry the same step count")
+        updates = steps.pop() if steps else 0
+        self.m.zero_(); self.v.zero_()
+        for i, n in enumerate(fp.names if state else ()):
+            s = state[g['params'][i]]
+            off, k = fp.offsets[n], fp.views[n].numel()
+            self.m[off:off + k].copy_(s['exp_avg'].reshape(-1))
+            self.v[off:off + k].copy_(s['exp_avg_sq'].reshape(-1))
+        self.beta1, self.beta2, self.eps = float(g['betas'][0]), float(g['betas'][1]), float(g['eps'])
+        self.set_lr(float(g['lr']))
+        if 'beta_pows' in own:
+            b1p, b2p = (np.float32(b) for b in own['beta_pows'])
+        else:
+            b1p = b2p = np.float32(1.0)
+            for _ in range(updates):
+                b1p, b2p = np.float32(b1p * np.float32(self.beta1)), np.float32(b2p * np.float32(self.beta2))
+        self._bpow = (b1p, b2p)
+        if getattr(self, "hyper", None) is not None:
+            self.hyper[1], self.hyper[2] = float(b1p), float(b2p)
+        self.updates = self.steps = updates
+        self._micro = 0
+        self.last_grad_norm.fill_(float(own.get('last_grad_norm', 0.0)))      # (logged before the first update of an epoch)
 
 
 
@@ -669,15 +826,20 @@ class STSETrainStep(_FlatStep, _OneClassHead):
 
     def __init__(self, model, lr: float = 1e-4, alpha: float = 1e-6, head: str = 'euclidean',
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, use_graph: bool = False,
-                 side_stream: bool = False, sync_bn: bool = False, fused_window: bool = False) -> None:
+                 side_stream: bool = False, sync_bn: bool = False, fused_window: bool = False, grad_clip_val=0.0,
+                 grad_clip_algorithm: str = 'norm', accumulate: int = 1) -> None:
         """fused_window: encoder layers of window length 8 / 16 / 24 train on the stored-Z layer kernels where those are built
-        (`window` runs of the stack; off: the composed path, as before)"""
+        (`window` runs of the stack; off: the composed path, as before)
+        grad_clip_val, grad_clip_algorithm, accumulate: gradient clipping ('norm' | 'value'; 0 / None: off) and accumulation over
+        `accumulate` calls of `step` (eager only), as Lightning's Trainer arguments of those meanings"""
         from .models.sts.ae import STSE
         from .models.common.components import MLP
         mlp = isinstance(model.btlnk, MLP)
         if not isinstance(model, STSE) or not (isinstance(model.btlnk, torch.nn.Linear) or (mlp and model.btlnk.hip_ok)):
             raise TypeError("STSETrainStep drives an STSE with projector='linear' or an 'mlp' within the kernels' widths")
-        super().__init__(model, lr, alpha, betas, eps, process_group)
+        if use_graph and _check_accumulate(accumulate) > 1:
+            raise ValueError("use_graph: a captured step makes one update per replay; accumulate > 1 runs eagerly")
+        super().__init__(model, lr, alpha, betas, eps, process_group, grad_clip_val, grad_clip_algorithm, accumulate)
         self.head = head
         dev = self.fp.flat.device
         self.hyper = torch.tensor([lr, 1.0, 1.0, 0.0], device=dev, dtype=torch.float32)
@@ -751,11 +913,14 @@ class STSETrainStep(_FlatStep, _OneClassHead):
             dU, top_stats = self.projector.backward(saved, dz, U, slope, ctx if self.side is None else None, top_layers,
                                                     self.stack.last_slope_grad)
         work = None
-        if self.world > 1 and self.tail_off is not None:
+        if self.world > 1 and self.tail_off is not None and self.accumulate == 1:
             # bucket 1 (87 % of the bytes: the bottleneck weight) is complete now: its all-reduce runs on the collective
             # stream while the encoder backward proceeds (SUM; the 1/W is folded into Adam)
             work = dist.all_reduce(self.fp.grad[self.tail_off:], group=self.pg, async_op=True)
         self.stack.backward(saved_stack, dU, self.ws, need_dx=False, top_stats=top_stats)
+        if self.accumulate > 1:            # no collective inside a group; one all-reduce of the accumulated buffer at its end
+            self._micro_step()
+            return stats
         if self.world > 1:
             head = self.fp.grad if work is None else self.fp.grad[:self.tail_off]
             dist.all_reduce(head, group=self.pg)           # bucket 2: the encoder's gradients (0.12 MB)
@@ -783,6 +948,7 @@ class STSETrainStep(_FlatStep, _OneClassHead):
                 self._stats_static = self._body(self._x_static)
         self._x_static.copy_(x)
         self._graph.replay()
+        self.updates = self.steps
         ops.note_raw_write()                    # the replay runs the captured writers without their wrappers
         return self._stats_static
 
@@ -937,8 +1103,10 @@ class STSAETrainStep(_FlatStep):
 
     def __init__(self, model, mode: str = 'ae', lr: float = 1e-4, alpha: float = 0.0, lambda_: float = 0.01, phi: float = 1.0,
                  beta: float = 1.0, gamma: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, process_group=None,
-                 fused_window: bool = False, gaussian_head: bool = False) -> None:
-        """fused_window: layers of window length 8 / 16 / 24 train on the stored-Z layer kernels where those are built (`window` runs
+                 fused_window: bool = False, gaussian_head: bool = False, grad_clip_val=0.0, grad_clip_algorithm: str = 'norm',
+                 accumulate: int = 1) -> None:
+        """grad_clip_val, grad_clip_algorithm, accumulate: as STSETrainStep's.
+        fused_window: layers of window length 8 / 16 / 24 train on the stored-Z layer kernels where those are built (`window` runs
         of both stacks, the last decoder layer as a `narrow` segment; off: the composed path, as before).  Eager, main stream.
         gaussian_head: a `distribution: 'normal'` VAE runs its latent head on csrc/vae_head_normal.hip (_GaussianLatent) where
         `gaussian_head_ok` admits it; off: under the local autograd graph (_AutogradLatent), as before."""
@@ -957,7 +1125,7 @@ class STSAETrainStep(_FlatStep):
         for kinds, which in zip(self.segment_kinds(model, fused_window), ("an encoder", "a decoder")):
             if kinds[-1] == 'wide':
                 raise NotImplementedError(f"STSAETrainStep: {which} ending in a wide layer")
-        super().__init__(model, lr, alpha, betas, eps, process_group)
+        super().__init__(model, lr, alpha, betas, eps, process_group, grad_clip_val, grad_clip_algorithm, accumulate)
         self.mode = mode
         self.lambda_, self.phi, self.beta, self.gamma = float(lambda_), float(phi), float(beta), float(gamma)
         self.w_rec = self.lambda_ if mode == 'ae' else self.phi
@@ -1040,9 +1208,7 @@ class STSAETrainStep(_FlatStep):
         ctx, top_layers = self.enc.top(enc_saved)
         dU, top_stats = self.projector.backward(proj_saved, dy, U, slope, ctx, top_layers, self.enc.last_slope_grad)
         self.enc.backward(enc_saved, dU, self.ws, need_dx=False, top_stats=top_stats)
-        if self.world > 1:
-            dist.all_reduce(self.fp.grad, group=self.pg)                          # SUM; the 1 / W is folded into Adam
-        self._adam()
+        self._update()
         self.last = out
         return out
 
@@ -1056,8 +1222,12 @@ class AutogradTrainStep(_OneClassHead):
     optimiser is torch's Adam (calc_reg_loss / configure_optimizers of the reference wrappers)."""
 
     def __init__(self, model, lr: float = 1e-4, alpha: float = 1e-6, head: str = 'euclidean', betas=(0.9, 0.999),
-                 eps: float = 1e-8, process_group=None) -> None:
+                 eps: float = 1e-8, process_group=None, grad_clip_val=0.0, grad_clip_algorithm: str = 'norm',
+                 accumulate: int = 1) -> None:
         self.model, self.head, self.alpha, self.pg = model, head, float(alpha), process_group
+        self.accumulate = _check_accumulate(accumulate)
+        self.clip_val, self.clip_mode = _check_clip(grad_clip_val, grad_clip_algorithm)
+        self._micro = 0
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.params = [(n, p) for n, p in model.named_parameters()]
         self.reg_params = [p for n, p in self.params if 'bias' not in n]          # model_utils.py:92
@@ -1068,31 +1238,75 @@ class AutogradTrainStep(_OneClassHead):
         self.center_acc = torch.zeros(ops.head_slots(L), device=dev, dtype=torch.float32)
         self.gram_acc = torch.zeros(L, L, device=dev, dtype=torch.float32) if head == 'mahalanobis' else None
         self.steps = 0
+        self.last_grad_norm = torch.zeros(1, device=dev, dtype=torch.float32)
 
     def set_lr(self, lr: float) -> None:
         for g in self.opt.param_groups:
             g['lr'] = lr
 
+    def set_gradient_clip(self, val, algorithm: Optional[str] = None) -> None:
+        self.clip_val, self.clip_mode = _check_clip(val, self.clip_mode if algorithm is None else algorithm)
+
     def step(self, x: Tensor) -> Tensor:
         self.steps += 1
         m = self.model
-        self.opt.zero_grad(set_to_none=True)
+        if self._micro == 0:               # (no zero_grad inside an accumulation group: autograd sums into .grad)
+            self.opt.zero_grad(set_to_none=True)
         z = m(x)
         zd = z.detach().contiguous()
         stats, dz = self._head(zd)
-        z.backward(dz)
+        z.backward(dz if self.accumulate == 1 else dz / self.accumulate)
         with torch.no_grad():
-            coef = self.alpha * 2.0 * self.reg_scale          # d/dp of alpha * reg_scale * sum p^2
+            coef = self.alpha * 2.0 * self.reg_scale / self.accumulate         # d/dp of alpha * reg_scale * sum p^2
             for p in self.reg_params:
                 if p.grad is not None:
                     p.grad.add_(p, alpha=coef)
-            parallel.allreduce_grads_mean_([p for _, p in self.params], self.pg)   # one flat bucket
-        self.opt.step()
+        self._micro += 1
+        if self._micro == self.accumulate:
+            self.flush()
         return stats
+
+    def flush(self) -> bool:
+        """the update of the pending group (every micro-step counted 1 / accumulate), also of fewer than `accumulate` micro-steps
+        at the end of an epoch -> whether one was made"""
+        if self._micro == 0:
+            return False
+        _clipped_update([p for _, p in self.params], self.opt, self.pg, self.clip_val, self.clip_mode, self.last_grad_norm)
+        self._micro = 0
+        return True
+
+    def state_dict(self) -> dict:
+        """torch.optim.Adam's state_dict, with the micro-step counter beside it"""
+        return dict(self.opt.state_dict(), coskad={'micro_step': self._micro})
+
+    def load_state_dict(self, sd: dict) -> None:
+        _load_torch_optimizer(self.opt, sd)
+        self._micro = 0
 
     def reg_loss(self) -> Tensor:
         with torch.no_grad():
             return self.reg_scale * sum((p.float() ** 2).sum() for p in self.reg_params).reshape(1)
+
+
+def _clipped_update(params, opt, pg, clip_val: float, clip_mode: str, norm_out: Optional[Tensor] = None) -> None:
+    """the autograd routes' update: gradient mean over ranks, torch's clipping (after the mean, as on the flat steps), opt.step()"""
+    with torch.no_grad():
+        parallel.allreduce_grads_mean_(params, pg)   # one flat bucket
+    if clip_val > 0:
+        if clip_mode == 'norm':
+            norm = torch.nn.utils.clip_grad_norm_(params, clip_val)
+            if norm_out is not None:
+                norm_out.copy_(norm.reshape(1))
+        else:
+            torch.nn.utils.clip_grad_value_(params, clip_val)
+    opt.step()
+
+
+def _load_torch_optimizer(opt, sd: dict) -> None:
+    """a step class' state_dict() -- a flat step's or an autograd route's -- into a torch optimiser, the project key left aside"""
+    if sd.get('coskad', {}).get('micro_step', 0):
+        raise ValueError("optimizer state: saved inside an accumulation group (mid-epoch checkpoints are not supported)")
+    opt.load_state_dict({k: v for k, v in sd.items() if k != 'coskad'})
 
 
 def make_train_step(model, flat_plain_gcn: bool = False, fused_window: bool = False, **kw):

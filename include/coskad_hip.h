@@ -740,6 +740,27 @@ int coskad_adam_pow_f32(float* p, const float* g, float* m, float* v, const floa
 int coskad_adam_dev_f32(float* p, const float* g, float* m, float* v, const float* mask, size_t n, float* hyper,
                         float beta1, float beta2, float eps, float gscale, float reg_coef, hipStream_t stream);
 
+/* Gradient clipping and accumulation on the flat buffers (csrc/grad_clip.hip).
+ * partials[0 .. 255] (fp64) = per-workgroup sums of g_eff[i]^2 with g_eff = g*gscale + reg_coef*mask*p formed in fp32 as
+ * coskad_adam_*_f32 forms it; entries no workgroup owns are written 0.  No atomics: repeated calls agree bit for bit. */
+int coskad_grad_sqnorm_f32(const float* g, const float* p, const float* mask, size_t n, float gscale, float reg_coef,
+                           double* partials, hipStream_t stream);
+
+/* coskad_adam_pow_f32 / coskad_adam_dev_f32 with g_eff clipped before the moment updates.  clip_mode 1: by global norm, coef =
+ * min(1, clip_val / (sqrt(sum partials) + 1e-6)) with the norm in fp32 (torch.nn.utils.clip_grad_norm_), every workgroup summing
+ * `partials` (coskad_grad_sqnorm_f32's) in the same fixed order; the unclipped norm goes to norm_out[0] unless norm_out is NULL.
+ * clip_mode 2: by value, clamp to [-clip_val, clip_val]; partials may be NULL and norm_out is not written.  clip_val must be
+ * finite and > 0.  A coefficient of exactly 1 leaves p, m, v bit-identical to the unclipped entry points. */
+int coskad_adam_clip_pow_f32(float* p, const float* g, float* m, float* v, const float* mask, size_t n, float lr, float beta1,
+                             float beta2, float eps, float b1pow, float b2pow, float gscale, float reg_coef,
+                             const double* partials, float clip_val, int clip_mode, float* norm_out, hipStream_t stream);
+int coskad_adam_clip_dev_f32(float* p, const float* g, float* m, float* v, const float* mask, size_t n, float* hyper, float beta1,
+                             float beta2, float eps, float gscale, float reg_coef, const double* partials, float clip_val,
+                             int clip_mode, float* norm_out, hipStream_t stream);
+
+/* acc = first ? g : acc + g over n floats (gradient accumulation over micro-batches). */
+int coskad_grad_accum_f32(float* acc, const float* g, size_t n, int first, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
