@@ -242,6 +242,15 @@ class LitEncoder(nn.Module):
             _, _, score = ops.mse_head(hidden.contiguous(), self.model.c, need_grad=False, need_score=True)
         return score
 
+    def window_attribution(self, x: torch.Tensor):
+        """-> (score [B], grad [B, C, T, V], attr [B, T, V]) of a batch of windows, eval mode: each window's own score (what
+        `window_scores` gives for the same batch), its gradient with respect to the input skeleton and gradient x input summed over
+        the coordinates -- which person-frame-joint carries the score; a missing joint (an exact 0 in x) gets 0.  The adjoint of the
+        folded eval layers on csrc/eval_layer_adj.hip (coskad_amd/attribution.py).  ValueError naming the reason outside
+        the supported set (train mode, mlp projector, plain-GCN encoders, V = 14 / 18, wide layers, dropout)."""
+        from . import attribution
+        return attribution.window_attribution(self, x)
+
     def _load_gts(self) -> Dict[Tuple[int, int], np.ndarray]:
         if self.gts is not None:
             return self.gts
@@ -311,6 +320,10 @@ class _AutogradLit(LitEncoder):
     over ranks.  Validation outputs are per-window scores computed on the device."""
 
     model_cls = None
+
+    def window_attribution(self, x: torch.Tensor):
+        raise ValueError(f"window_attribution: {type(self).__name__} scores windows by reconstruction (autoencoder / VAE wrappers): the "
+                         "per-joint reconstruction error is their natural map, the input gradient of a one-class score is not defined")
 
     def _build(self, args: Namespace, **extra) -> None:
         nn.Module.__init__(self)

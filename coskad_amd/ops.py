@@ -184,6 +184,44 @@ def layer_tail(x_in: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, bias: Tensor,
     return out, score
 
 
+INPUT_GRAD_FRAMES = (8, 12, 16, 24)     # window lengths, joint layouts, input and output widths of the folded layer's adjoint kernel
+INPUT_GRAD_JOINTS = (17, 25)            # (csrc/eval_layer_adj.hip)
+INPUT_GRAD_CIN = (2, 16, 32)
+INPUT_GRAD_COUT = (16, 32, 64)
+
+
+def layer_input_grad_ok(T: int, V: int, Ci: int, Co: int) -> bool:
+    """Host arithmetic of `coskad_layer_input_grad_ok`: layer_input_grad takes the (Ci -> Co) layer at this geometry.  Restated here
+    so that asking needs no native library; tests/test_attribution_host.py holds the two in agreement."""
+    return T in INPUT_GRAD_FRAMES and V in INPUT_GRAD_JOINTS and Ci in INPUT_GRAD_CIN and Co in INPUT_GRAD_COUT
+
+
+def layer_input_grad_max_grid(T: int, V: int, Ci: int, Co: int) -> int:
+    """the persistent grid's cap (workgroups) of layer_input_grad at this shape; 0 where it is not built"""
+    return int(_lib.lib().coskad_layer_input_grad_max_grid(T, V, Ci, Co))
+
+
+def layer_input_grad(dU: Tensor, x_in: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, Co: int,
+                     in_slope: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The adjoint of layer_apply's folded layer with respect to its input `x_in` [B, Ci, T, V] (csrc/eval_layer_adj.hip):
+    dIn [B, Ci, T, V] = PReLU'(x_in) (.) (gcn^T(Wz^T dU) + Wx^T dU) for dU [B, Co, T, V] and the `wfold` layer_apply takes.
+    `in_slope` None (the network input): no mask, `x_in` gives the shape and is not read.
+    One clip per workgroup: a clip's gradient does not depend on the batch it arrives in."""
+    B, Co2, T, V = dU.shape
+    if Co2 != Co:
+        raise ValueError(f"layer_input_grad: dU has {Co2} channels, Co = {Co}")
+    Ci = x_in.shape[1]
+    _chk(dU, "dU"); _chk(x_in, "x_in", (B, Ci, T, V)); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T))
+    _chk(wfold, "wfold", (2 * Ci, cop(Co))); _chk(in_slope, "in_slope", (1,), optional=True)
+    if out is None:
+        out = torch.empty(B, Ci, T, V, device=dU.device, dtype=torch.float32)
+    else:
+        _chk(out, "out", (B, Ci, T, V))
+    call("coskad_layer_input_grad_f32", dU, x_in if in_slope is not None else None, out, A, Tm, wfold, in_slope, B, Ci, Co, T, V,
+         _stream(), tag=(Ci, Co))
+    return out
+
+
 def layer_first_pair_ok(Ci: int, Cm: int, Co: int, T: int, V: int) -> bool:
     """the first layer (2 -> Cm) and the layer behind it (Cm -> Co), folded, in one pass (csrc/eval_layer_clip.hip, FIRST form: 8 / 12 /
     16 / 24 frames)"""
@@ -1644,6 +1682,18 @@ def score_person_frames(scores, win_ptr, win_idx):
     pf = torch.empty(rows, device=scores.device, dtype=torch.float64)
     call("coskad_score_person_frames_f64", scores, int(scores.dtype == torch.float64), win_ptr, win_idx, pf, scores.numel(), rows, _stream())
     return pf
+
+
+def attribution_frames(attr, frames, win_ptr, win_idx, entry_frame):
+    """out [win_ptr.numel() - 1, V] float64: per (person, frame) the mean over the covering windows of the row attr[w, t] with
+    frames[w, t] == entry_frame[row] (attr [N, T, V] float32, frames [N, T] int32); NaN where no window holds the frame."""
+    N, T, V = attr.shape
+    rows = win_ptr.numel() - 1
+    _chk(attr, "attr"); _chk(frames, "frames", (N, T), dtype=torch.int32); _chk(win_ptr, "win_ptr", dtype=torch.int32)
+    _chk(win_idx, "win_idx", dtype=torch.int32); _chk(entry_frame, "entry_frame", (rows,), dtype=torch.int32)
+    out = torch.empty(rows, V, device=attr.device, dtype=torch.float64)
+    call("coskad_attribution_frames_f64", attr, frames, win_ptr, win_idx, entry_frame, out, N, rows, T, V, _stream())
+    return out
 
 
 def score_pad_(pf, row_ptr, pad_size, n_max):

@@ -246,3 +246,79 @@ def score_report(per_t, gt, segments, clip_keys) -> ScoreReport:
 
 def _host_array(t):
     return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t
+
+
+# ---- attribution maps: windows -> person frames -> per-clip files (DESIGN 5.24) ----
+
+def _entry_frames(plan: ScorePlan) -> np.ndarray:
+    """[row_ptr[P]] int64: the frame NUMBER (as the window table's `frames` counts them: from 1) of every row of the person x frame
+    vector"""
+    rp = plan.row_ptr.cpu().numpy().astype(np.int64)
+    return np.arange(int(rp[-1]), dtype=np.int64) - np.repeat(rp[:-1], np.diff(rp)) + 1
+
+
+def attribution_frames(attr, frames, plan: ScorePlan) -> np.ndarray:
+    """The yardstick of `attribution_frames_device`, as numpy loops: attr [N, T, V] per-window maps, frames [N, T] the window table's
+    frame numbers -> [row_ptr[P], V] float64: for every person-frame the mean over its covering windows (the plan's window CSR, in
+    ascending order) of the row attr[w, t] with frames[w, t] == that frame; NaN where no window holds it.  fp64 sums."""
+    a, fr = np.asarray(_host_array(attr)), np.asarray(_host_array(frames)).astype(np.int64)
+    if a.ndim != 3 or fr.shape != a.shape[:2] or a.shape[0] != plan.N:
+        raise ValueError(f"attribution_frames: attr {a.shape}, frames {fr.shape} for a plan of {plan.N} windows")
+    wp, wi = plan.win_ptr.cpu().numpy(), plan.win_idx.cpu().numpy()
+    ef = _entry_frames(plan)
+    out = np.full((ef.shape[0], a.shape[2]), np.nan, dtype=np.float64)
+    for e in range(ef.shape[0]):
+        total, cnt = np.zeros(a.shape[2], dtype=np.float64), 0
+        for w in wi[wp[e]:wp[e + 1]]:
+            hit = np.nonzero(fr[w] == ef[e])[0]
+            if hit.size:
+                total = total + a[w, hit[0]].astype(np.float64)
+                cnt += 1
+        if cnt:
+            out[e] = total / float(cnt)
+    return out
+
+
+def attribution_frames_device(attr: torch.Tensor, frames: torch.Tensor, plan: ScorePlan) -> torch.Tensor:
+    """`attribution_frames` on the device (csrc/attribution_frames.hip: one deterministic launch, fp64 sums in the same order, no
+    atomics): attr [N, T, V] float32 on the GPU -> [row_ptr[P], V] float64 there."""
+    from .. import _lib, ops
+    if not attr.is_cuda:
+        raise _lib.CoskadHipError(f"attribution_frames_device: expected the maps on the GPU, got device {attr.device}; no CPU fallback "
+                                  "(`attribution_frames` is the host route)")
+    if attr.dim() != 3 or tuple(frames.shape) != tuple(attr.shape[:2]) or attr.shape[0] != plan.N:
+        raise ValueError(f"attribution_frames_device: attr {tuple(attr.shape)}, frames {tuple(frames.shape)} for a plan of {plan.N} "
+                         "windows")
+    if attr.device != plan.win_ptr.device:
+        raise ValueError(f"attribution_frames_device: maps on {attr.device}, plan on {plan.win_ptr.device}")
+    if plan.n_persons == 0:
+        return torch.empty(0, attr.shape[2], dtype=torch.float64, device=attr.device)
+    ef = torch.from_numpy(_entry_frames(plan)).to(torch.int32).to(attr.device)
+    return ops.attribution_frames(attr.float().contiguous(), frames.to(attr.device, torch.int32).contiguous(), plan.win_ptr,
+                                  plan.win_idx, ef)
+
+
+def save_attribution(directory: str, maps, plan: ScorePlan) -> None:
+    """Per clip of the plan `<scene>_<clip>_attribution.npy` [persons, frames, V] float32 -- the person-frame maps [row_ptr[P], V] of
+    `attribution_frames(_device)` averaged over the transformations, NaN where the person is absent -- and `<scene>_<clip>_persons.npy`,
+    the person ids of its rows (a clip nobody appears in gets arrays with no person)."""
+    import os
+    os.makedirs(directory, exist_ok=True)
+    m = np.asarray(_host_array(maps), dtype=np.float64)
+    rp = plan.row_ptr.cpu().numpy().astype(np.int64)
+    V = m.shape[1] if m.ndim == 2 else 0
+    for c, (sc, cl) in enumerate(plan.clip_keys):
+        rows = np.nonzero(plan.person_clip == c)[0]
+        ids = np.unique(plan.person_keys[rows, 3]) if rows.size else np.zeros(0, dtype=np.int64)
+        n = int(plan.person_n[rows[0]]) if rows.size else 0
+        total, cnt = np.zeros((ids.shape[0], n, V)), np.zeros((ids.shape[0], n, V))
+        for p in rows:
+            k = int(np.searchsorted(ids, plan.person_keys[p, 3]))
+            blk = m[rp[p]:rp[p + 1]]
+            ok = ~np.isnan(blk)
+            total[k] += np.where(ok, blk, 0.0)
+            cnt[k] += ok
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out = np.where(cnt > 0, total / cnt, np.nan).astype(np.float32)
+        np.save(os.path.join(directory, f"{sc}_{cl}_attribution.npy"), out)
+        np.save(os.path.join(directory, f"{sc}_{cl}_persons.npy"), ids.astype(np.int64))

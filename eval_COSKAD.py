@@ -19,6 +19,9 @@ def main():
     # the reference's per-clip / per-transformation log (eval_COSKAD.py:222-242); the yaml key `eval_report: true` asks for the same
     parser.add_argument('--report', action='store_true')
     parser.add_argument('--report-dir', type=str, default=None)      # report.json + <scene>_<clip>.npy (implies --report)
+    # per clip <scene>_<clip>_attribution.npy [persons, frames, V] (gradient x input of the window scores, mean over the covering windows
+    # and the transformations, NaN where a person is absent) and <scene>_<clip>_persons.npy; one-class encoders only
+    parser.add_argument('--attribution-dir', type=str, default=None)
     cli = parser.parse_args()
     args = argparse.Namespace(**yaml.load(open(cli.config), Loader=yaml.FullLoader))
     if cli.report or cli.report_dir:
@@ -43,13 +46,15 @@ def main():
         test, gts = make_dataset(n_scenes=2, n_clips=3, n_persons=3, clip_len=200, num_transform=args.dataset_num_transform,
                                  anomaly=True, seed=args.seed + 1, T=args.dataset_seg_len)
         model.gts = gts
-        out = trainer.predict(model, lambda: batches(test, args.dataset_batch_size), ckpt_path=path)
+        loader_fn = lambda: batches(test, args.dataset_batch_size)
+        out = trainer.predict(model, loader_fn, ckpt_path=path)
     else:
         # eval_COSKAD.py:107-116: test split of the Morais-format tree, scaler pickled by the training run
         from coskad_amd.utils.dataset import get_dataset_and_loader
         dataset_args.exp_dir = os.path.dirname(path)
         _, loader = get_dataset_and_loader(dataset_args, split=args.split)
-        out = trainer.predict(model, lambda: loader, ckpt_path=path)
+        loader_fn = lambda: loader
+        out = trainer.predict(model, loader_fn, ckpt_path=path)
     auc = model.validation_epoch_end(out)
     report = getattr(model, 'last_report', None)
     if report is not None and parallel.rank() == 0:
@@ -58,6 +63,10 @@ def main():
         if cli.report_dir:
             report.save(cli.report_dir)
     print('final AUC score: {}'.format(auc))
+    if cli.attribution_dir and parallel.rank() == 0:
+        from coskad_amd.attribution import dataset_attribution
+        dataset_attribution(model, loader_fn, out, cli.attribution_dir)
+        print('attribution maps written to {}'.format(cli.attribution_dir))
 
 
 if __name__ == '__main__':

@@ -82,6 +82,23 @@ int coskad_layer_tail_f32(const float* in, const float* x, float* out, float* sc
                           const float* in_slope, const float* out_slope,
                           int B, int Ci, int Co, int T, int V, hipStream_t stream);
 
+/* The ADJOINT of coskad_layer_apply_f32's folded layer (csrc/eval_layer_adj.hip): the gradient with respect to the layer's input of
+ * whatever dU is the gradient of, one clip per workgroup on a persistent grid, no batch coupling:
+ *   dIn [B, Ci, T, V] = PReLU_in'(in) (.) ( gcn^T(Wz^T . dU) + Wx^T . dU ),    dU [B, Co, T, V]
+ * gcn^T: coskad_gcn_f32's adjoint.  wfold [2*Ci][Co]: exactly what coskad_bn_fold_f32 hands coskad_layer_apply_f32 (read transposed).
+ * in_slope NULL (the network input): the mask is 1 and `in` is not read (may be NULL); otherwise PReLU' is 1 where in > 0 and
+ * in_slope[0] elsewhere (an exact 0 gets the slope).
+ * coskad_layer_input_grad_ok: 1 for T in {8, 12, 16, 24} x V in {17, 25} x Ci in {2, 16, 32} x Co in {16, 32, 64}, 0 otherwise (a set
+ * of its own).  coskad_layer_input_grad_max_grid: the persistent grid's cap (workgroups) of that shape, 0 where not ok.
+ * dU, dIn and (with in_slope) `in` non-NULL and 16-byte aligned: COSKAD_ERR_ARG naming the pointer otherwise, BEFORE the shape is
+ * judged; other shapes fail with COSKAD_ERR_SHAPE ("unsupported ...").  Every check runs before the device is touched.  A clip's
+ * result does not depend on B or on the workgroup that forms it. */
+int coskad_layer_input_grad_ok(int T, int V, int Ci, int Co);
+int coskad_layer_input_grad_max_grid(int T, int V, int Ci, int Co);
+int coskad_layer_input_grad_f32(const float* dU, const float* in, float* dIn, const float* A, const float* Tm,
+                                const float* wfold, const float* in_slope, int B, int Ci, int Co, int T, int V,
+                                hipStream_t stream);
+
 /* nn.PReLU() with one shared weight (stsgcn.py:82,110), elementwise, for API paths that must
  * materialise the post-activation tensor.  bwd: du = dout * PReLU'(u); dslope (+)= sum dout*u [u<0];
  * ws >= 1024 floats.  fwd moves 16-byte vectors: u and out must be 16-byte aligned (COSKAD_ERR_ARG naming the pointer otherwise,
@@ -555,6 +572,14 @@ int coskad_score_report_auc_f64(const double* sorted_scores, const int* gt_sorte
                                 int F, hipStream_t stream);
 int coskad_score_report_thresholds_f64(const double* sorted_scores, const long long* cum_neg, double* out, int* ws, size_t ws_elems,
                                        int n_rows, int F, hipStream_t stream);
+
+/* Per-window attribution maps attr [n_windows, T, V] -> per-person frame maps out [n_rows, V] (csrc/attribution_frames.hip), on the
+ * window CSR of coskad_score_person_frames_f64: out[e] = the mean over the windows win_idx[win_ptr[e] .. win_ptr[e + 1]) of
+ * attr[w][t], t the first position with frames[w][t] == entry_frame[e] (frames [n_windows, T], the window table's frame numbers;
+ * entry_frame [n_rows], the frame number of every row); NaN where no window holds the frame.  fp64 sums in ascending window order, no
+ * atomics: bitwise reproducible. */
+int coskad_attribution_frames_f64(const float* attr, const int* frames, const int* win_ptr, const int* win_idx, const int* entry_frame,
+                                  double* out, int n_windows, int n_rows, int T, int V, hipStream_t stream);
 
 /* ---- one-class heads, centre statistics, regulariser, optimiser ------------------------ */
 
