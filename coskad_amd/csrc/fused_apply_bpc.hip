@@ -70,6 +70,17 @@ __global__ __launch_bounds__(256, BPC_OCC) void k_layer_apply_bpc(const float* _
     if (stg) *reinterpret_cast<float4*>(r2 + (4 * q + srow) * LDW + scol) = v;
   };
 
+  // parameter operands: loaded ONCE per workgroup, ahead of every stream load, and held in registers (fused_apply_next_bpc.hip:
+  // a parameter load issued inside the clip loop behind a stream prefetch, and consumed before it, drains the prefetch)
+  const int lq = (L.q * CoP + 16 * wave + L.j) * 4;        // this wave's output tile of the folded weights
+  const float4 b4 = buf_load4(bres, L.q * 16, (16 * wave) * 4);
+  const f32x4 bq = {b4.x, b4.y, b4.z, b4.w};
+  float wc[NG][4];                                         // folded-weight columns: [group][k-step]
+#pragma unroll
+  for (int g = 0; g < NG; ++g)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) wc[g][s] = buf_load1(wres, lq, ((16 * g + 4 * s) * CoP) * 4);
+
   int clip = blockIdx.x;
   {
     const BufRes z0 = clip_res(Zg, clip, Ci), x0 = clip_res(in, clip, Ci);
@@ -99,11 +110,7 @@ __global__ __launch_bounds__(256, BPC_OCC) void k_layer_apply_bpc(const float* _
       qstore(q, gq[0][q], false);
       gq[0][q] = vload(DEPTH, q);
     }
-    const int lq = (L.q * CoP + 16 * wave + L.j) * 4;      // this wave's output tile of the folded weights
-    float wc[2][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) wc[0][s] = buf_load1(wres, lq, (4 * s) * CoP * 4);
-    __syncthreads();                                       // the window holds group 0
+    __syncthreads();                                      // the window holds group 0
 #ifndef BPC_BDBL
 #define BPC_BDBL 0   // operands of k-step s+1 read while step s multiplies (two register sets) / read just in time (one)
 #endif
@@ -112,10 +119,6 @@ __global__ __launch_bounds__(256, BPC_OCC) void k_layer_apply_bpc(const float* _
     for (int t = 0; t < NTILE; ++t) b[0][t] = r2[L.q * LDW + (t < T ? t * V + L.j : jc * V + 16)];
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-      if (g + 1 < NG) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) wc[(g + 1) & 1][s] = buf_load1(wres, lq, ((16 * (g + 1) + 4 * s) * CoP) * 4);
-      }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         if (BPC_BDBL && (s + 1 < 4 || g + 1 < NG)) {       // operands of the next k-step (the next group's first: stored at s = 0)
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(256, BPC_OCC) void k_layer_apply_bpc(const float* _
           if (DEPTH == 2 || g + 2 < NG) gq[(g + 1) % DEPTH][s] = vload(g + 1 + DEPTH, s);   // (beyond this clip: the next clip's first groups)
         }
 #pragma unroll
-        for (int t = 0; t < NTILE; ++t) acc[t] = mfma(wc[g & 1][s], b[BPC_BDBL ? (s & 1) : 0][t], acc[t]);
+        for (int t = 0; t < NTILE; ++t) acc[t] = mfma(wc[g][s], b[BPC_BDBL ? (s & 1) : 0][t], acc[t]);
         if (!BPC_BDBL && (s + 1 < 4 || g + 1 < NG)) {      // single set: the next k-step's operands behind this step's MFMAs
           const int sn = (s + 1) & 3;
 #pragma unroll
@@ -143,8 +146,6 @@ __global__ __launch_bounds__(256, BPC_OCC) void k_layer_apply_bpc(const float* _
       for (int q = 0; q < 4; ++q) gq[0][q] = vload(NG, q);
     }
     L = geo();
-    const float4 b4 = buf_load4(bres, L.q * 16, (16 * wave) * 4);
-    const f32x4 bq = {b4.x, b4.y, b4.z, b4.w};
     const int jf = L.j < T ? L.j : T - 1;
     // ---- flush: 32 channels at a time through the image (waves 0, 1, then 2, 3), full lines to HBM -------------------------
 #pragma unroll

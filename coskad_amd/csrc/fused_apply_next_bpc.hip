@@ -37,6 +37,10 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
   // this wave's share of the 13 position tiles of the GEMM: OTP == 2: output tile wave & 1, tiles [0, 7) or [7, 13);
   // OTP == 1: tiles [0, 4), [4, 7), [7, 10), [10, 13)
   constexpr int MAXT = OTP == 2 ? 7 : 4;
+  // the wave's temporal records live in registers across the clip loop where 128 registers hold them beside the K pass (two input
+  // channels: 123); with them <2,1> spills 28 B and <1,2> 84 B -- the next clip's prefetched rows among them -- so those two load
+  // them once per clip, behind the K pass (below)
+  constexpr bool TREC_HOIST = CT == 0;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* r1 = lds;                 // 32-row image (stride LD)
   float* r2 = lds + 32 * LD;       // 16-row K window (stride LDW)
@@ -138,6 +142,32 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
     }
   };
 
+  // ---- parameter operands: loaded ONCE per workgroup, ahead of every stream load, and held in registers.  gfx950 returns vector
+  // loads in issue order on one counter: a parameter load issued inside the clip loop behind a stream prefetch (the next clip's rows,
+  // the next K group) and consumed before it makes the wave wait for the prefetch at the moment it was meant to start overlapping
+  // (DESIGN 5.2).  The floats and every operation on them are the ones of the in-loop loads.
+  const Lane Lp = geo();
+  const int lq = (Lp.q * CoP + 16 * ot + Lp.j) * 4;      // this wave's output tile of the folded weights
+  const float4 b4 = buf_load4(bres, Lp.q * 16, (16 * ot) * 4);
+  const f32x4 bq = {b4.x, b4.y, b4.z, b4.w};
+  constexpr int NWC = CT ? NG : 1;
+  float wc[NWC][4];                                      // folded-weight columns: [group][k-step] (CT == 0: wc[0][0] only)
+  if constexpr (CT == 0) {
+    wc[0][0] = buf_load1(wres, lq, 0);
+  } else {
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) wc[g][s] = buf_load1(wres, lq, ((16 * g + 4 * s) * CoP) * 4);
+  }
+  constexpr int NTR = (V + 3) / 4;                       // temporal records of the wave's joints wave, wave + 4, .. (5; the last: wave 0 only)
+  float4 trec[NTR];
+  auto load_trec = [&]() {
+#pragma unroll
+    for (int i = 0; i < NTR; ++i) trec[i] = buf_load4(tabres, l16, ((wave + 4 * i < V ? wave + 4 * i : wave) * 64) * 16);
+  };
+  if constexpr (TREC_HOIST) load_trec();
+
   int clip = blockIdx.x;
   {
     const BufRes z0 = clip_res(Zg, clip, Ci), x0 = clip_res(in, clip, Ci);
@@ -162,7 +192,6 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto pos_of = [&](int t) { return t < T ? t * V + L.j : jc * V + 16; };   // t: absolute tile index (T: the joint-16 tile)
-    const int lq = (L.q * CoP + 16 * ot + L.j) * 4;
     if constexpr (CT == 0) {
       // ---- ONE k-step: rows Z0 Z1 X0 X1 of the window against the four rows of the folded weight ----------------------------
       {
@@ -173,13 +202,12 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
           *reinterpret_cast<float4*>(r2 + (2 + frow) * LDW + fcol) = vx;
         }
       }
-      const float wc = buf_load1(wres, lq, 0);
       gq[0][0] = buf_load4(znext, fvoff, 0);             // the next clip's rows take off
       gq[0][1] = buf_load4(xnext, fvoff, 0);
       __syncthreads();                                   // the window holds this clip's four rows
 #pragma unroll
       for (int t = 0; t < MAXT; ++t)
-        if (t < nt) acc[t] = mfma(wc, r2[L.q * LDW + pos_of(t0 + t)], acc[t]);
+        if (t < nt) acc[t] = mfma(wc[0][0], r2[L.q * LDW + pos_of(t0 + t)], acc[t]);
     } else {
       auto vload = [&](int vg, int q) {                  // virtual group: this clip's groups 0 .. NG-1 (Z first), then the next clip's
         const bool nxt = vg >= NG;
@@ -191,19 +219,12 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
         qstore(q, gq[0][q], false);
         gq[0][q] = vload(DEPTH, q);
       }
-      float wc[2][4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) wc[0][s] = buf_load1(wres, lq, (4 * s) * CoP * 4);
       __syncthreads();                                   // the window holds group 0
       float b[MAXT];
 #pragma unroll
       for (int t = 0; t < MAXT; ++t) b[t] = r2[L.q * LDW + pos_of(t0 + (t < nt ? t : 0))];
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
-        if (g + 1 < NG) {
-#pragma unroll
-          for (int s = 0; s < 4; ++s) wc[(g + 1) & 1][s] = buf_load1(wres, lq, ((16 * (g + 1) + 4 * s) * CoP) * 4);
-        }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           // every wave has read rows 4s .. 4s+3 (a k-step ago); in the last group: its fourth quarter (stored a k-step ago) is visible
@@ -214,7 +235,7 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
           }
 #pragma unroll
           for (int t = 0; t < MAXT; ++t)
-            if (t < nt) acc[t] = mfma(wc[g & 1][s], b[t], acc[t]);
+            if (t < nt) acc[t] = mfma(wc[g][s], b[t], acc[t]);
           if (s + 1 < 4 || g + 1 < NG) {                 // the next k-step's operands behind this step's MFMAs
             const int sn = (s + 1) & 3;
 #pragma unroll
@@ -225,8 +246,6 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
     }
     // ---- U = sums + bias -> image (the bias joins the finished sums) ------------------------------------------------------------
     {
-      const float4 b4 = buf_load4(bres, L.q * 16, (16 * ot) * 4);
-      const f32x4 bq = {b4.x, b4.y, b4.z, b4.w};
       __syncthreads();                                   // the image is free: every wave has finished the previous clip's second Gram
 #pragma unroll
       for (int t = 0; t < MAXT; ++t) {
@@ -235,9 +254,11 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
       }
     }
     __syncthreads();                                     // the image holds U
+    // (no registers for the records across the K pass: they take off here, ahead of the rows' stores and half a K pass + the U
+    // phase behind the next clip's rows, and are consumed a whole phase later)
+    if constexpr (!TREC_HOIST) load_trec();
     // ---- U -> HBM while sum x x^T multiplies (X_next = PReLU(U) on the fly); the image keeps U ----------------------------------
     gram_rows(gx, sx, ores, true);
-    float4 rec = buf_load4(tabres, l16, (wave * 64) * 16);   // (the first joint's table record travels across the barrier)
     __syncthreads();                                     // every wave has read U
     // ---- Z_next = gcn_next(X_next) in place.  Temporal: joints v = wave, wave + 4, .. (PReLU on the operand reads) ---------------
     L = geo();
@@ -247,22 +268,24 @@ __global__ __launch_bounds__(256, FNB_OCC) void k_layer_apply_next_bpc(const flo
       int vprev = -1;
 #pragma unroll
       for (int rt = 0; rt < OTP; ++rt) cur[rt] = temporal_read<16, true>(r1, rt, wave, L, a_out);
-      for (int v = wave; v < V; v += 4) {
-        const int vn = v + 4 < V ? v + 4 : v;
-        const float4 recn = buf_load4(tabres, l16, (vn * 64) * 16);
 #pragma unroll
-        for (int rt = 0; rt < OTP; ++rt) nxt[rt] = temporal_read<16, true>(r1, rt, vn, L, a_out);
-        f32x4 d[OTP];
+      for (int i = 0; i < NTR; ++i) {                    // unrolled: trec[i] is a register, not an indexed array
+        const int v = wave + 4 * i;
+        if (v < V) {                                     // (wave-uniform; false only at i == 4 in waves 1 .. 3)
+          const int vn = v + 4 < V ? v + 4 : v;
 #pragma unroll
-        for (int rt = 0; rt < OTP; ++rt) d[rt] = temporal_mm(cur[rt], rec);
-        if (vprev >= 0) {
+          for (int rt = 0; rt < OTP; ++rt) nxt[rt] = temporal_read<16, true>(r1, rt, vn, L, a_out);
+          f32x4 d[OTP];
 #pragma unroll
-          for (int rt = 0; rt < OTP; ++rt) temporal_store<16>(r1, rt, vprev, dprev[rt], L);
+          for (int rt = 0; rt < OTP; ++rt) d[rt] = temporal_mm(cur[rt], trec[i]);
+          if (i > 0) {
+#pragma unroll
+            for (int rt = 0; rt < OTP; ++rt) temporal_store<16>(r1, rt, vprev, dprev[rt], L);
+          }
+#pragma unroll
+          for (int rt = 0; rt < OTP; ++rt) { dprev[rt] = d[rt]; cur[rt] = nxt[rt]; }
+          vprev = v;
         }
-#pragma unroll
-        for (int rt = 0; rt < OTP; ++rt) { dprev[rt] = d[rt]; cur[rt] = nxt[rt]; }
-        vprev = v;
-        rec = recn;
       }
 #pragma unroll
       for (int rt = 0; rt < OTP; ++rt) temporal_store<16>(r1, rt, vprev, dprev[rt], L);

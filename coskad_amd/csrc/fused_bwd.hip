@@ -95,6 +95,27 @@ __global__ __launch_bounds__(1024) void k_reduce_fused(const float* __restrict__
 // waves per SIMD: the one-pass kernel needs up to 256 registers (two); 16 input channels without the chain fit three in 168
 // (B = 4096, 16 -> 32: 163 vs 172 us; WITH the chain's sums three waves spill 30 registers and the step loses 7 us)
 constexpr int bpc_occ(int CT, int NS) { return CT == 1 && NS == 0 ? 3 : 2; }
+// Parameter operands in LDS (the two-per-CU instantiations: 77.6 KB of the 80 KB a workgroup may take there).  gfx950 returns
+// vector loads in issue order on one counter: a table record or coefficient row loaded inside the clip loop behind a stream
+// prefetch (the K ring's next group, dT's X halves) and consumed before it drains the prefetch at the moment it was meant to start
+// overlapping.  The operands that were consumed out of order are staged ONCE per workgroup, from btab / coef as k_bwd_fold wrote
+// them, component-major: lane l's record (v, l) = {x, y, z} becomes tf[v][s][l], so that the 64 lanes of one ds_read_b32 read 64
+// consecutive words (bank = l mod 64: conflict-free, like the LD / LDW reads of fused_ops.h) and the unused components are dropped:
+//   tf [V][3][64]        forward temporal records   rec[v][l][s] = T[v][4s+q][j]                                    13 056 B
+//   as [T][5][64]        adjoint spatial records    rec[t][l][s] = A[t][j][4s+q]                                    15 360 B
+//   et [T][20]           their joint-16 row         A[t][16][4s+q]: one word per k slot, broadcast over j              960 B
+//   kr [CT][4][CT][64]   the Kr rows of the dT phase, [X half][k-step][channel tile][lane]                      <=  4 096 B
+//   kq [2][Ci]           the kt and kr quads
+// The adjoint temporal records stay vector loads: no stream load is in flight when they are issued or consumed.  The coefficient
+// loads of the K pass stay too: they are consumed in ring order.  Measured at B = 4096 (interleaved kernel traces):
+// 16 -> 32 with the chain 158 -> 152 us, 32 -> 16 with the chain 196 -> 190 us; 32 -> 64 (OT == 4: the K pass is 60 % of the kernel)
+// 254 -> 256 us in every combination of the four operand kinds, so that width keeps the vector loads, as do the three-per-CU
+// instantiations, whose workgroups have no LDS to spare.
+constexpr bool bpc_tlds(int CT, int OT, int NS) { return bpc_occ(CT, NS) == 2 && OT < 4; }
+constexpr int TF_F = V * 3 * 64, AS_F = T * 5 * 64, ET_F = 256;
+constexpr int bpc_lds_floats(int CT, int OT, int NS) {
+  return WAVE_LDS_W + 4 * 256 + (bpc_tlds(CT, OT, NS) ? TF_F + AS_F + ET_F + CT * CT * 256 + 2 * 16 * CT : 0);
+}
 #ifndef FBB_BDBL   // K passes: operands of k-step s+1 read in front of step s's MFMAs (two register sets) / behind them (one): same speed
 #define FBB_BDBL 0
 #endif
@@ -117,6 +138,12 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
   float* r1 = lds;                 // 32-row image (stride LD)
   float* r2 = lds + 32 * LD;       // 16-row K window (stride LDW; LD in the statistics phase)
   float* zs = lds + WAVE_LDS_W + 256 * (threadIdx.x >> 6);   // 1 KB per wave: the joint-16 dZ tile, lane-major
+  constexpr bool TLDS = bpc_tlds(CT, OT, NS);               // parameter operands in LDS (above)
+  float* tf = lds + WAVE_LDS_W + 4 * 256;
+  float* as = tf + TF_F;
+  float* et = as + AS_F;
+  float* krl = et + ET_F;
+  float* kql = krl + CT * CT * 256;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   auto geo = [&]() {
@@ -181,17 +208,25 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
   const float a_b = bpre ? below_slope[0] : 0.f;
 
   // mixing phases of the whole image, dealt to the waves: temporal by joint, spatial by frame (fused_apply_next_bpc.hip)
-  auto temporal_rr = [&](int base4) {                    // base4: float4 index of the temporal table's first record
+  auto temporal_rr = [&](int base4, auto from_lds) {     // base4: float4 index of the temporal table's first record (LDS: tf)
     const Lane Lt = geo();
+    auto trec = [&](int v) {
+      if constexpr (decltype(from_lds)::value) {
+        const float* p = tf + v * 192 + 16 * Lt.q + Lt.j;
+        return float4{p[0], p[64], p[128], 0.f};
+      } else {
+        return buf_load4(tabres, l16, (base4 + v * 64) * 16);
+      }
+    };
     TOp cur[CT], nxt[CT];
     f32x4 dprev[CT];
     int vprev = -1;
 #pragma unroll
     for (int rt = 0; rt < CT; ++rt) cur[rt] = temporal_read<16>(r1, rt, wave, Lt);
-    float4 rec = buf_load4(tabres, l16, (base4 + wave * 64) * 16);
+    float4 rec = trec(wave);
     for (int v = wave; v < V; v += 4) {
       const int vn = v + 4 < V ? v + 4 : v;
-      const float4 recn = buf_load4(tabres, l16, (base4 + vn * 64) * 16);
+      const float4 recn = trec(vn);
 #pragma unroll
       for (int rt = 0; rt < CT; ++rt) nxt[rt] = temporal_read<16>(r1, rt, vn, Lt);
       f32x4 d[CT];
@@ -211,14 +246,23 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
   };
   auto spatial_rr = [&]() {                              // the adjoint spatial table: btab section behind the forward temporal one
     const Lane Ls = geo();
-    SpatRec srec = load_spat(tabres, 0, wave, l16);
+    auto spat_rec = [&](int t) {
+      if constexpr (TLDS) {
+        const float* p = as + t * 320 + 16 * Ls.q + Ls.j;
+        const float* e = et + t * 20 + Ls.q;
+        return SpatRec{float4{p[0], p[64], p[128], p[192]}, float4{p[256], e[0], e[4], e[8]}, float4{e[12], e[16], 0.f, 0.f}};
+      } else {
+        return load_spat(tabres, 0, t, l16);
+      }
+    };
+    SpatRec srec = spat_rec(wave);
     SOp op[CT];
 #pragma unroll
     for (int rt = 0; rt < CT; ++rt) op[rt] = spatial_read<16>(r1, rt, wave, Ls);
 #pragma unroll
     for (int k = 0; k < T / 4; ++k) {
       const int t = wave + 4 * k, tn = k + 1 < T / 4 ? t + 4 : t;
-      const SpatRec nrec = load_spat(tabres, 0, tn, l16);
+      const SpatRec nrec = spat_rec(tn);
       SOp opn[CT];
 #pragma unroll
       for (int rt = 0; rt < CT; ++rt) opn[rt] = spatial_read<16>(r1, rt, tn, Ls);
@@ -234,6 +278,29 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
     }
   };
 
+  auto stage_params = [&]() {
+    // ---- the parameter operands -> LDS, once per workgroup (the clip loop's first barriers publish them) ----------------------------
+    for (int e = tid; e < V * 64; e += 256) {            // forward temporal record (v, l) -> tf[v][s][l]
+      const float4 r = buf_load4(tabres, e * 16, 0);
+      float* p = tf + (e >> 6) * 192 + (e & 63);
+      p[0] = r.x; p[64] = r.y; p[128] = r.z;
+    }
+    for (int e = tid; e < T * 64; e += 256) {            // adjoint spatial record (t, l) -> as[t][s][l], et[t][4s + q] (from column j = 0)
+      const int t = e >> 6, l = e & 63, o = (TEMP_F4 + t * 3 * 64 + l) * 16;
+      const float4 c0 = buf_load4(tabres, o, 0), c1 = buf_load4(tabres, o, 1024), c2 = buf_load4(tabres, o, 2048);
+      float* p = as + t * 320 + l;
+      p[0] = c0.x; p[64] = c0.y; p[128] = c0.z; p[192] = c0.w; p[256] = c1.x;
+      if ((l & 15) == 0) {
+        float* q = et + t * 20 + (l >> 4);
+        q[0] = c1.y; q[4] = c1.z; q[8] = c1.w; q[12] = c2.x; q[16] = c2.y;
+      }
+    }
+    for (int e = tid; e < CT * CT * 256; e += 256) {     // Kr row 16h + 4s + q, column 16c + j -> krl[h][s][c][l]
+      const int l = e & 63, c = (e >> 6) % CT, hs = (e >> 6) / CT;
+      krl[e] = buf_load1(cres, ((DX0 / CiP + Co + 4 * hs + (l >> 4)) * CiP + 16 * c + (l & 15)) * 4, 0);
+    }
+    if (tid < 2 * Ci) kql[tid] = buf_load1(cres, ((tid < Ci ? KT0 : KR0 - Ci) + tid) * 4, 0);
+  };
   int clip = blockIdx.x;
   float4 gq[4];                                          // K ring: one group in flight, a quarter per register
   {
@@ -242,6 +309,7 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
 #pragma unroll
     for (int q = 0; q < 4; ++q) gq[q] = qload(du0, 0, q);
   }
+  if constexpr (TLDS) stage_params();                    // (behind the first clip's rows: they fly while the tables are staged)
   for (; clip < B; clip += gridDim.x) {
     const BufRes xres = clip_res(in, clip, Ci), zres = clip_res(Zg, clip, Ci), dures = clip_res(dU, clip, Co);
     const BufRes ores = clip_res(dIn, clip, Ci);
@@ -267,7 +335,7 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
     }
     __syncthreads();                                     // the image holds X, the window group 0
     // ---- Y = temporal mix of X, in place ------------------------------------------------------------------------------------------
-    if (!(FBB_SKIP & 1)) temporal_rr(0);
+    if (!(FBB_SKIP & 1)) temporal_rr(0, std::integral_constant<bool, TLDS>{});
     // ---- K pass:  acc[tile] += coefficient rows [c0 ..) x dU (OT groups) + rows [c1 ..) x the second source (CT groups) --------
     L = geo();
     const int lq = (L.q * CiP + 16 * ct + L.j) * 4;
@@ -327,13 +395,13 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
     };
     f32x4 az[MAXF + 1];
     {
-      const float4 a = buf_load4(cres, L.q * 16, (KT0 + 16 * ct) * 4);
+      const float4 a = TLDS ? *reinterpret_cast<const float4*>(kql + 16 * ct + 4 * L.q) : buf_load4(cres, L.q * 16, (KT0 + 16 * ct) * 4);
 #pragma unroll
       for (int k = 0; k <= MAXF; ++k) az[k] = f32x4{a.x, a.y, a.z, a.w};
     }
     f32x4 xr[MAXF + 1];                                  // Br.dU + Kr.X + kr
     {
-      const float4 kq = buf_load4(cres, L.q * 16, (KR0 + 16 * ct) * 4);
+      const float4 kq = TLDS ? *reinterpret_cast<const float4*>(kql + Ci + 16 * ct + 4 * L.q) : buf_load4(cres, L.q * 16, (KR0 + 16 * ct) * 4);
 #pragma unroll
       for (int k = 0; k <= MAXF; ++k) xr[k] = f32x4{kq.x, kq.y, kq.z, kq.w};
     }
@@ -390,7 +458,8 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
         }
         float wk[4];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) wk[s] = buf_load1(cres, lq, ((DX0 / CiP + Co + 16 * h + 4 * s) * CiP) * 4);   // Kr rows
+        for (int s = 0; s < 4; ++s)                      // Kr rows
+          wk[s] = TLDS ? krl[((4 * h + s) * CT + ct) * 64 + 16 * L.q + L.j] : buf_load1(cres, lq, ((DX0 / CiP + Co + 16 * h + 4 * s) * CiP) * 4);
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -418,7 +487,7 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
     float4 u[XL];
     {
       // ---- gcn^T: temporal adjoint in place, + Br.dU + Kr.X + kr (in the registers since the K pass): dX -------------------------
-      if (!(FBB_SKIP & 1)) temporal_rr(TEMP_F4 + SPAT_F4);
+      if (!(FBB_SKIP & 1)) temporal_rr(TEMP_F4 + SPAT_F4, std::false_type{});
       __syncthreads();                                   // the image holds gcn^T(dZ)
       xload(u, xres);                                    // the pre-activations come back (from L2) for the row pass
       L = geo();
@@ -617,15 +686,16 @@ int bwd_bpc_rows(int B, int Ci, bool chain) {
 int launch_layer_bwd_bpc(const float* in, const float* Zg, const float* dU, const float* coef, const float* in_slope, float* dIn,
                          float* btab, float* partials, float* dap, int B, int Ci, int Co, hipStream_t st, int* rows_out,
                          const float* below_z, const float* below_x, const float* below_slope, int below_Ci, float* below_stats) {
-  const size_t lds = (size_t)(ff::WAVE_LDS_W + 4 * 256) * sizeof(float);
   const int grid = bwd_bpc_rows(B, Ci, below_stats != nullptr);
   *rows_out = grid;
 #define LAUNCH_FBB(CT, OT, NS, CB)                                                                                   \
   do {                                                                                                               \
-    auto k = fb::k_layer_bwd_bpc<CT, OT, NS, CB>;                                                                   \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, in, Zg, dU, coef, btab, in_slope, dIn, partials, dap, B,   \
-                       below_z, below_x, below_slope, below_stats);                                                  \
+    rc = launch_lds<fb::k_layer_bwd_bpc<CT, OT, NS, CB>>("bwd_bpc", dim3(grid), dim3(256),                          \
+                                                         fb::bpc_lds_floats(CT, OT, NS) * sizeof(float), st, in, Zg, dU, coef,  \
+                                                         (const float*)btab, in_slope, dIn, partials, dap, B, below_z,      \
+                                                         below_x, below_slope, below_stats);                                \
   } while (0)
+  int rc = COSKAD_OK;
   {
     ProbeScope probe(KID_BWD_DATA, Ci, Co, st);
     if (below_stats) {
@@ -642,7 +712,7 @@ int launch_layer_bwd_bpc(const float* in, const float* Zg, const float* dU, cons
     else return fail(COSKAD_ERR_SHAPE, "bwd_bpc: unsupported channels (%d, %d)", Ci, Co);
   }
 #undef LAUNCH_FBB
-  return check_launch("bwd_bpc");
+  return rc;
 }
 
 int launch_reduce_fused(const float* partials, int rows, float* dA, float* dT, const float* dap, float* dslope, int accumulate,
