@@ -1,8 +1,10 @@
 """Float64 restatements of the stand-alone kernels the kernel-level tests compare with (test_gpu_wide_kernels.py,
-test_gpu_narrow_conv.py, test_gpu_flat_kernels.py), in plain torch / numpy on the CPU.  Every function takes the float32 inputs
-converted to double, composes the forward only -- gradients come from torch autograd on that forward, never from a hand-written
-backward -- and never calls the library.  test_kernel_refs_host.py holds them against torch.nn / torch.optim before a device sees
-them.  Not a conftest: a plain module the tests import by name."""
+test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py), in plain torch / numpy on the CPU.  Every function takes
+the float32 inputs converted to double, composes the forward only -- gradients come from torch autograd on that forward, never from a
+hand-written backward -- and never calls the library.  test_kernel_refs_host.py holds them against torch.nn / torch.optim before a
+device sees them.  The one-class heads' section also restates the kernels' Poincare sequences, backward included, over a running-error
+arithmetic: that restatement supplies BOUNDS only, the values compared with stay the oracle's.  Not a conftest: a plain module the
+tests import by name."""
 import math
 
 import numpy as np
@@ -162,3 +164,441 @@ def gather_transform_f32(xy, mats, index, N, ntrans):
         out[b, 0] = (x * m[0, 0] + y * m[0, 1]) + m[0, 2]
         out[b, 1] = (x * m[1, 0] + y * m[1, 1]) + m[1, 2]
     return out
+
+
+# ---- the one-class heads (csrc/heads.hip: L <= 16, one thread per clip; csrc/heads_wide.hip: 16 < L <= 512, one wave per clip) ---------
+
+HEAD_LMAX = 16            # heads_common.h LMAX: latents up to here run one thread per clip
+HEAD_ROWS = 512           # kFlatBlock: clips per block of the narrow heads; one block writes stats / acc itself
+WIDE_TILE = 16            # hw::kTileRows: clips per block of the wide heads (4 waves)
+WIDE_MAX_BLOCKS = 1024    # hw::kMaxBlocks
+
+# Largest error of the device's tanhf / log1pf in ulps of the float32 result.  Neither can be derived from the kernels' text; both were
+# measured once on an MI355X (torch's float32 tanh / log1p on the device against float64 over the argument ranges of
+# head_inputs: 1.39 and 0.57 ulp) and set to the ceiling of the largest error seen plus 1 ulp.
+TANH_ULP = 3
+LOG1P_ULP = 2
+
+HEAD_RADII = (0.0, 1e-7, 9e-6, 1.1e-5, 1e-3, 0.3, 1.0, 2.5, 3.7, 3.9, 6.0, 14.9, 15.1, 20.0, 100.0)
+HEAD_CENTRES = (0.0, 0.4, 0.93, 0.995)
+
+
+def head_inputs(B, L, cnorm, seed=0):
+    """Latent rows and a centre for the head tests: row n is a random unit direction times HEAD_RADII[(n + seed) % 15] -- the radii
+    straddle the min-norm clamp (1e-5), the projection threshold artanh(0.999) = 3.8002 and the tanh clamp (15) -- and, for a centre off
+    the origin, row 0 is antipodal to it at radius 6 and row 1 lies along it at radius 1 (B == 1: one of the two, by the seed).
+    -> (z [B, L] float32, c [L] float32 with |c| = cnorm)"""
+    g = torch.Generator().manual_seed(1000 * L + 7 * B + seed)
+    unit = lambda t: t / t.norm(dim=-1, keepdim=True)
+    cdir = unit(torch.randn(L, generator=g, dtype=torch.float64))
+    dirs = unit(torch.randn(B, L, generator=g, dtype=torch.float64))
+    radii = torch.tensor(HEAD_RADII, dtype=torch.float64)[(torch.arange(B) + seed) % len(HEAD_RADII)]
+    z = dirs * radii[:, None]
+    if cnorm > 0:
+        special = [-6.0 * cdir, 1.0 * cdir]
+        if B == 1:
+            z[0] = special[seed % 2]
+        else:
+            z[0], z[1] = special
+    return z.float(), (cnorm * cdir).float()
+
+
+def dot_roundings(L):
+    """roundings of one latent dot product: the fmaf chain of the L non-zero products (narrow), or the lane's ceil(L / 64) fmaf and the
+    six xor-butterfly levels of wave_sum (wide)"""
+    return L if L <= HEAD_LMAX else -(-L // 64) + 6
+
+
+def head_blocks(B, L):
+    """partial rows (= blocks) of a head launch"""
+    if L <= HEAD_LMAX:
+        return 1 if B <= HEAD_ROWS else -(-B // HEAD_ROWS)
+    return min(-(-B // WIDE_TILE), WIDE_MAX_BLOCKS)
+
+
+def head_sum_roundings(B, L):
+    """float32 roundings on the way from a clip's term to its slot of `stats`, the final conversion included (the partial rows are
+    summed in double).  Narrow: the thread's clips in turn, wave_sum (6), the block's eight waves in turn (7; the first add is to 0),
+    the conversion (1).  Wide (Euclidean / Poincare): the wave's clips in turn, the four waves (3), the conversion (1)."""
+    P = head_blocks(B, L)
+    if L <= HEAD_LMAX:
+        return -(-B // (P * HEAD_ROWS)) + 6 + 7 + 1
+    return -(-B // (P * 4)) + 3 + 1
+
+
+def poincare_slot_sums(zh):
+    """the Poincare head's slots from the points on the ball: (sum gamma zh [L], sum (gamma - 1), sum |zh|), gamma = 2 / (1 - |zh|^2)"""
+    gamma = 2.0 / (1.0 - (zh * zh).sum(-1, keepdim=True))
+    return (gamma * zh).sum(0), (gamma - 1.0).sum(), torch.sqrt((zh * zh).sum(-1)).sum()
+
+
+def euclid_slot_sums(z):
+    """the Euclidean / Mahalanobis heads' slots: (sum z [L], the clip count, sum |z|) and the Gram matrix sum z z^T"""
+    return z.sum(0), float(z.shape[0]), torch.sqrt((z * z).sum(-1)).sum(), z.T @ z
+
+
+def midpoint_from_sums(S, s):
+    """oracle.ref_cpu.weighted_midpoint from its two sums S = sum gamma x, s = sum (gamma - 1) (curvature 1), line for line"""
+    m = S / s.clamp_min(1e-10)
+    mn = torch.sqrt((m * m).sum()).clamp_min(1e-15)
+    at = 0.5 * torch.log((1 + mn.clamp(max=1 - 1e-7)) / (1 - mn.clamp(max=1 - 1e-7)))
+    return torch.tanh(0.5 * at) * m / mn
+
+
+# Running-error arithmetic: the kernels' Poincare chain (expmap0 -> project -> Mobius add -> artanh, and its backward) is too long and
+# too ill-conditioned for a hand constant, so its BOUND comes from restating the kernels' operation sequence once (the functions
+# below) over a value / error pair: EV.v is the operation on the exact operands in double, EV.e bounds how far the kernel's float32
+# value can be from it -- every operation propagates its operands' errors (sum |df/dx_i| e_i, with the denominators taken at their
+# near end) and adds one float32 rounding of its result, U32 (|v| + e).  The VALUE the tests compare with stays the oracle's; the
+# restatement in double is held to the oracle at 1e-12 and, evaluated over F32 (numpy float32, every operation rounded), to its own
+# bound by test_kernel_refs_host.py.
+
+def _pow2(x):
+    return x == 0.0 or math.frexp(abs(x))[0] == 0.5
+
+
+class EV:
+    __slots__ = ("v", "e")
+
+    def __init__(self, v, e=None):
+        self.v = torch.as_tensor(v, dtype=torch.float64)
+        self.e = torch.zeros_like(self.v) if e is None else torch.as_tensor(e, dtype=torch.float64) + torch.zeros_like(self.v)
+
+    @staticmethod
+    def lift(x):
+        if isinstance(x, EV):
+            return x
+        assert f32(x) == x, "a literal must be a float32"
+        return EV(x)
+
+    @staticmethod
+    def rounded(v, ep):
+        return EV(v, ep + U32 * (v.abs() + ep))
+
+    def __neg__(self):
+        return EV(-self.v, self.e)
+
+    def __add__(self, o):
+        o = EV.lift(o)
+        return EV.rounded(self.v + o.v, self.e + o.e)
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        return self + (-EV.lift(o))
+
+    def __rsub__(self, o):
+        return EV.lift(o) + (-self)
+
+    def __mul__(self, o):
+        if not isinstance(o, EV) and _pow2(o):
+            return EV(self.v * o, self.e * abs(o))          # exact
+        o = EV.lift(o)
+        return EV.rounded(self.v * o.v, self.v.abs() * o.e + o.v.abs() * self.e + self.e * o.e)
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        o = EV.lift(o)
+        v = self.v / o.v
+        return EV.rounded(v, (self.e + v.abs() * o.e) / (o.v.abs() - o.e).clamp_min(1e-300))
+
+    def __rtruediv__(self, o):
+        return EV.lift(o) / self
+
+    def sqrt(self):
+        v = torch.sqrt(self.v)
+        lo = torch.sqrt((self.v - self.e).clamp_min(0.0))
+        ep = torch.where(self.e > 0, torch.minimum(self.e / (v + lo).clamp_min(1e-300), torch.sqrt(self.e)), torch.zeros_like(v))
+        return EV.rounded(v, ep)
+
+    def tanh(self):
+        v = torch.tanh(self.v)
+        near = torch.tanh((self.v.abs() - self.e).clamp_min(0.0))
+        return EV(v, (1.0 - near * near) * self.e + TANH_ULP * 2 * U32 * v.abs())
+
+    def log1p(self):
+        v = torch.log1p(self.v)
+        return EV(v, self.e / (1.0 + self.v - self.e).clamp_min(1e-300) + LOG1P_ULP * 2 * U32 * v.abs())
+
+    def _pick(self, o, v):
+        """min / max are 1-Lipschitz: the larger of the two errors, and the winner's own where the two cannot change places"""
+        o = EV.lift(o)
+        z = torch.zeros_like(self.v)
+        ov, oe = o.v + z, o.e + z
+        apart = (self.v - ov).abs() > self.e + oe
+        return EV(v(self.v, ov), torch.where(apart, torch.where(v(self.v, ov) == self.v, self.e, oe), torch.maximum(self.e, oe)))
+
+    def maximum(self, o):
+        return self._pick(o, torch.maximum)
+
+    def minimum(self, o):
+        return self._pick(o, torch.minimum)
+
+
+class EVMath:
+    """the arithmetic the chains are written over: constants, selects, the latent dot product and the record of every select's margin"""
+
+    def __init__(self):
+        self.margins = []          # (name, |x - threshold| [rows], err(x) + err(threshold) [rows])
+
+    def inp(self, x):
+        return EV(torch.as_tensor(np.asarray(x), dtype=torch.float64) if not torch.is_tensor(x) else x.double())
+
+    def const(self, x, x32=None):
+        """a constant the kernel holds as float32: x32 (default: x rounded) where the exact chain has x"""
+        return EV(x, abs((f32(x) if x32 is None else float(x32)) - x))
+
+    def exact(self, x):
+        """x taken as an exact operand: for a result that does not depend on x's value"""
+        return EV(x.v)
+
+    def rel(self, x):
+        return x.e / (x.v.abs() - x.e).clamp_min(1e-300)
+
+    def widen(self, x, rel):
+        return EV(x.v, x.e + rel * (x.v.abs() + x.e))
+
+    def gt(self, name, x, thr):
+        thr = EV.lift(thr)
+        self.margins.append((name, (x.v - thr.v).abs(), x.e + thr.e))
+        return x.v > thr.v
+
+    def positive(self, x):
+        return x.v > 0
+
+    def where(self, cond, a, b):
+        a, b = EV.lift(a), EV.lift(b)
+        return EV(torch.where(cond, a.v, b.v + torch.zeros_like(a.v)), torch.where(cond, a.e, b.e + torch.zeros_like(a.e)))
+
+    def dot(self, a, b, wide):
+        """[.., L] x [.., L] -> [.., 1] in the kernel's order: dot() of heads_common.h (one fmaf chain) or wdot() of heads_wide.hip
+        (lane l: a chain over j = l + 64 v, then wave_sum).  Every partial sum is rounded once."""
+        t = a.v * b.v
+        prop = (a.v.abs() * b.e + b.v.abs() * a.e + a.e * b.e).sum(-1, keepdim=True)
+        L = t.shape[-1]
+        if not wide:
+            run = t.cumsum(-1).abs().sum(-1, keepdim=True)
+            n = L
+        else:
+            pad = torch.zeros(t.shape[:-1] + (512 - L,), dtype=t.dtype)
+            lanes = torch.cat([t, pad], -1).view(t.shape[:-1] + (8, 64))
+            nv = -(-L // 64)
+            run = lanes.cumsum(-2)[..., :nv, :].abs().sum((-2, -1)).unsqueeze(-1) + 6 * t.abs().sum(-1, keepdim=True)
+            n = nv + 6
+        return EV(t.sum(-1, keepdim=True), prop + U32 * (run + n * prop))
+
+    def value(self, x):
+        return x.v
+
+    def bound(self, x):
+        return x.e
+
+
+class F32:
+    """numpy float32 with the same interface: every operation rounds to float32 (an fmaf is formed in double and rounded once)"""
+    __slots__ = ("x",)
+
+    def __init__(self, x):
+        self.x = np.asarray(x, dtype=np.float32)
+
+    @staticmethod
+    def lift(o):
+        return o if isinstance(o, F32) else F32(np.float32(o))
+
+    def __neg__(self):
+        return F32(-self.x)
+
+    def __add__(self, o):
+        return F32(self.x + F32.lift(o).x)
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        return F32(self.x - F32.lift(o).x)
+
+    def __rsub__(self, o):
+        return F32(F32.lift(o).x - self.x)
+
+    def __mul__(self, o):
+        return F32(self.x * F32.lift(o).x)
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return F32(self.x / F32.lift(o).x)
+
+    def __rtruediv__(self, o):
+        return F32.lift(o) / self
+
+    def sqrt(self):
+        return F32(np.sqrt(self.x))
+
+    def tanh(self):
+        return F32(np.tanh(self.x.astype(np.float64)))
+
+    def log1p(self):
+        return F32(np.log1p(self.x.astype(np.float64)))
+
+    def maximum(self, o):
+        return F32(np.maximum(self.x, F32.lift(o).x))
+
+    def minimum(self, o):
+        return F32(np.minimum(self.x, F32.lift(o).x))
+
+
+class F32Math:
+    def __init__(self):
+        self.margins = []
+
+    def inp(self, x):
+        return F32(x.numpy() if torch.is_tensor(x) else x)
+
+    def const(self, x, x32=None):
+        return F32(np.float32(x if x32 is None else x32))
+
+    def exact(self, x):
+        return x
+
+    def rel(self, x):
+        return None
+
+    def widen(self, x, rel):
+        return x
+
+    def gt(self, name, x, thr):
+        return x.x > F32.lift(thr).x
+
+    def positive(self, x):
+        return x.x > 0
+
+    def where(self, cond, a, b):
+        return F32(np.where(cond, F32.lift(a).x, F32.lift(b).x))
+
+    @staticmethod
+    def _fma(a, b, c):
+        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+    def dot(self, a, b, wide):
+        a, b = np.broadcast_arrays(a.x, b.x)
+        L = a.shape[-1]
+        if not wide:
+            s = np.zeros(a.shape[:-1], np.float32)
+            for j in range(L):
+                s = self._fma(a[..., j], b[..., j], s)
+            return F32(s[..., None])
+        pad = [(0, 0)] * (a.ndim - 1) + [(0, 512 - L)]
+        a, b = (np.pad(t, pad).reshape(t.shape[:-1] + (8, 64)) for t in (a, b))
+        s = np.zeros(a.shape[:-2] + (64,), np.float32)
+        for v in range(8):
+            s = self._fma(a[..., v, :], b[..., v, :], s)
+        lane = np.arange(64)
+        for off in (32, 16, 8, 4, 2, 1):
+            s = s + s[..., lane ^ off]
+        return F32(s[..., :1])
+
+    def value(self, x):
+        return torch.from_numpy(x.x.astype(np.float64))
+
+
+def _f32sub(a, b):
+    return float(np.float32(a) - np.float32(b))
+
+
+def hyp_embed(A, u, wide):
+    """heads.hip hyp_embed / heads_wide.hip hw::hyp_embed: p = project(expmap0(u)) and what the backward keeps"""
+    kmin = A.const(1e-5)
+    un_raw = A.dot(u, u, wide).sqrt()
+    un = un_raw.maximum(kmin)
+    tn = un.minimum(15.0).tanh()                                  # the lower clamp at -15 never binds
+    f = tn / un
+    e = f * u
+    en_raw = A.dot(e, e, wide).sqrt()
+    en = en_raw.maximum(kmin)
+    maxnorm = A.const(1 - 1e-3, _f32sub(1, 1e-3))
+    clamped = A.gt("projection", en, maxnorm)
+    # x / |x| does not change when x is scaled, so the projected point carries none of f's error: only the roundings from e on
+    e0 = A.exact(f) * u
+    p = A.where(clamped, e0 / A.dot(e0, e0, wide).sqrt().maximum(kmin) * maxnorm, e)
+    return dict(p=p, un_raw=un_raw, un=un, tn=tn, f=f, en_raw=en_raw, clamped=clamped, maxnorm=maxnorm, kmin=kmin)
+
+
+def poincare_dist(A, c, p, wide, need_grad=True):
+    """poincare_dist of both files: d = 2 artanh(|(-c) (+) p|) [.., 1] and dd/dp.  The artanh clamp is a minimum, continuous, and the
+    backward takes the clamped value on both sides of it (Artanh.backward): its error propagates without a select."""
+    x2, y2, xy = A.dot(c, c, wide), A.dot(p, p, wide), -A.dot(c, p, wide)
+    alpha = 1.0 + 2.0 * xy + y2
+    beta = 1.0 - x2
+    den = 1.0 + 2.0 * xy + x2 * y2
+    D = den + A.const(1e-5)
+    x = -c
+    m = (alpha * x + beta * p) / D
+    mn = A.dot(m, m, wide).sqrt()
+    mc = mn.minimum(A.const(1 - 1e-5, _f32sub(1, 1e-5)))          # the lower clamp never binds: mn >= 0
+    d = mc.log1p() - (-mc).log1p()
+    if not need_grad:
+        return d, None, None
+    # everything from here to dz is linear in gmn = 2 / (1 - mc^2), the one badly conditioned scalar (1 / (1 - mc^2) reaches 5e4): its
+    # relative error goes to dz as a relative error (hyp_embed_bwd's caller widens by it), not through the cancellations on the way
+    gmn = 2.0 / (1.0 - mc * mc)
+    rel = A.rel(gmn)
+    gmn = A.exact(gmn)
+    inv = A.where(A.positive(mn), gmn / mn, 0.0)
+    gm = inv * m
+    gD = -A.dot(gm, m, wide) / D
+    galpha = A.dot(gm / D, x, wide)
+    gp = beta * gm / D + galpha * (2.0 * x + 2.0 * p) + gD * (2.0 * x + 2.0 * x2 * p)
+    return d, gp, rel
+
+
+def hyp_embed_bwd(A, u, em, gp, wide):
+    """hyp_embed_bwd of both files: dL/dp -> dL/du through project and expmap0"""
+    f, un, tn = em["f"], em["un"], em["tn"]
+    en = em["en_raw"]
+    egp = A.dot(f * u, gp, wide)
+    ge = A.where(em["clamped"], em["maxnorm"] * (gp / en - f * u * egp / (en * en * en)), gp)
+    gf = A.dot(ge, u, wide)
+    sech2 = A.where(A.gt("tanh clamp", A.const(15.0), un), 1.0 - tn * tn, 0.0)
+    df = (sech2 * un - tn) / (un * un)
+    coef = A.where(A.gt("min-norm", em["un_raw"], em["kmin"]), gf * df / em["un_raw"], 0.0)
+    return f * ge + coef * u
+
+
+def poincare_head_chain(A, z, c, wide, gscale=None):
+    """one clip of k_poincare_head / hw::k_poincare_wide on float32 z [B, L], c [L] or None: zh, the slot terms gamma zh, gamma - 1,
+    |zh|, and with a centre the distance and dz = hyp_embed_bwd(gscale dd/dp) (gscale: (exact, as the kernel's float32 holds it))"""
+    u = A.inp(z)
+    em = hyp_embed(A, u, wide)
+    p = em["p"]
+    y2 = A.dot(p, p, wide)
+    gamma = 2.0 / (1.0 - y2)
+    out = dict(zh=p, gzh=gamma * p, gm1=gamma - 1.0, norm=y2.sqrt())
+    if c is not None:
+        d, gp, rel = poincare_dist(A, _row(A, c), p, wide, gscale is not None)
+        out["d"] = d
+        if gscale is not None:
+            out["dz"] = A.widen(hyp_embed_bwd(A, u, em, gp * A.const(*gscale), wide), rel)
+    return out
+
+
+def _row(A, c):
+    x = A.inp(c)
+    if isinstance(x, EV):
+        return EV(x.v[None, :], x.e[None, :])
+    return F32(x.x[None, :])
+
+
+def logmap0_chain(A, y, wide):
+    """k_poincare_logmap0 of both files"""
+    p = A.inp(y)
+    yn = A.dot(p, p, wide).sqrt().maximum(A.const(1e-5))
+    yc = yn.minimum(A.const(1 - 1e-5, _f32sub(1, 1e-5)))
+    at = 0.5 * (yc.log1p() - (-yc).log1p())
+    return p / yn * at
+
+
+def gscale_pair(upstream, B):
+    """the Poincare / Mahalanobis heads' gscale = upstream / (float)B: (exact on the float32 upstream, the kernel's float32)"""
+    up = np.float32(upstream)
+    return float(up) / B, float(up / np.float32(B))

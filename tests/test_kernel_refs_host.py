@@ -1,5 +1,6 @@
 """The float64 references of kernel_refs.py against torch.nn / torch.optim on the CPU, before a device sees them: what the GPU
-kernel tests (test_gpu_wide_kernels.py, test_gpu_narrow_conv.py, test_gpu_flat_kernels.py) compare with is shown right here.  Also
+kernel tests (test_gpu_wide_kernels.py, test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py) compare with is
+shown right here; the running-error arithmetic behind the Poincare head's bounds against the oracle and numpy float32.  Also
 the Python twin of the dropout hash (its keep rate; the numpy form against the integer form) and the share of elements the
 apply / backward test leaves out at the PReLU kink, from the reference alone.  No kernel runs."""
 import numpy as np
@@ -167,6 +168,84 @@ def test_dropout_twin_keep_rate(p, seed):
     assert set(np.unique(m)) == {np.float32(0), np.float32(1) / (np.float32(1) - np.float32(p))}
     assert np.array_equal(R.drop_mask_twin_np(n, p, seed), m)
     assert np.array_equal(R.drop_mask_twin(100, 0.0, seed), np.ones(100, np.float32))
+
+
+# ---- the one-class heads: the restated Poincare chain and its running-error arithmetic ---------------------------------------------------
+
+HEAD_LS = [1, 2, 5, 16, 17, 65, 512]
+
+
+def _head_case(L, cnorm, B=67):
+    """float32 inputs of kernel_refs.head_inputs with the oracle's double forward and autograd gradient on them"""
+    from oracle import ref_cpu as O
+    z, c = R.head_inputs(B, L, cnorm if cnorm is not None else 0.4, seed=3)
+    zd = z.double().requires_grad_(True)
+    loss, zh = O.poincare_loss(zd, c.double())
+    (gz,) = torch.autograd.grad(loss, zd)
+    return z, c, zh.detach(), O.dist(c.double()[None], zh.detach()), gz, O
+
+
+@pytest.mark.parametrize("cnorm", R.HEAD_CENTRES)
+@pytest.mark.parametrize("L", HEAD_LS)
+def test_head_chain_in_double_is_the_oracle(L, cnorm):
+    """the restated kernel sequences (kernel_refs.poincare_head_chain, logmap0_chain), evaluated in double, equal oracle/ref_cpu.py's
+    project(expmap0(z)), dist and logmap0 to 1e-12, their hand-written backward equals autograd on the oracle's forward, the slot sums
+    give the oracle's gyromidpoint, and the oracle's gradients are finite on every row -- at both dot-product orders"""
+    z, c, zh, d, gz, O = _head_case(L, cnorm)
+    B = z.shape[0]
+    assert torch.isfinite(gz).all() and torch.isfinite(d).all()
+    for wide in (False, True):
+        A = R.EVMath()
+        out = R.poincare_head_chain(A, z, c, wide, R.gscale_pair(1.0, B))
+        tol = lambda ref: 1e-12 * max(1.0, float(ref.abs().max()))
+        assert float((out["zh"].v - zh).abs().max()) <= tol(zh)
+        # two double evaluations of |m| differ by a few roundings, which artanh amplifies by 2 / (1 - mc^2) (up to 1e5 at the clamp):
+        # eight of them on top of the 1e-12
+        amp = 2.0 / (1.0 - torch.tanh(d / 2) ** 2)
+        assert bool(((out["d"].v[:, 0] - d).abs() <= 1e-12 * d.abs().clamp_min(1.0) + 8 * R.U64 * amp).all())
+        # the backward is a restatement too (it only supplies the bound): rows at the ball's edge amplify double rounding by 1 / (1 - mn^2)
+        assert float((out["dz"].v - gz).abs().max()) <= 1e-9 * float(gz.abs().max())
+        S, s, nb = R.poincare_slot_sums(zh)
+        assert float((out["gzh"].v.sum(0) - S).abs().max()) <= 1e-12 * float(S.abs().max())
+        assert float((out["gm1"].v.sum() - s).abs()) <= 1e-12 * float(s) and float((out["norm"].v.sum() - nb).abs()) <= 1e-12 * float(nb)
+        mid = O.weighted_midpoint(zh)
+        assert float((R.midpoint_from_sums(S, s) - mid).abs().max()) <= 1e-12
+        lm = R.logmap0_chain(A, zh.float(), wide)
+        want = O.logmap0(zh.float().double())
+        assert float((lm.v - want).abs().max()) <= tol(want)
+
+
+@pytest.mark.parametrize("cnorm", R.HEAD_CENTRES)
+@pytest.mark.parametrize("L", HEAD_LS)
+def test_head_chain_in_float32_lies_within_the_running_error_bound(L, cnorm):
+    """the same sequences in numpy float32 (every operation rounded, fmaf rounded once, the kernels' summation orders) lie within the
+    arithmetic's bound of the double value, for every output of the head; and no row lies nearer to a select's threshold (projection,
+    min-norm, tanh clamp) than the compared quantity's bound: the cap on rows left out is 0.  (The artanh clamp is no select: a
+    minimum is continuous and Artanh.backward takes the clamped value on both sides, so its error passes through EV.minimum.)"""
+    z, c, zh, d, gz, O = _head_case(L, cnorm)
+    B = z.shape[0]
+    for wide in ((False, True) if L <= R.HEAD_LMAX else (True,)):         # the one-thread chain of L fmaf exists up to L = 16 only
+        A, F = R.EVMath(), R.F32Math()
+        gs = R.gscale_pair(0.37, B)
+        ev = R.poincare_head_chain(A, z, c, wide, gs)
+        fl = R.poincare_head_chain(F, z, c, wide, gs)
+        for name, margin, bound in A.margins:
+            assert bool((margin > bound).all()), (name, float((margin - bound).min()))
+        for k in ("zh", "d", "dz", "gzh", "gm1", "norm"):
+            err = (F.value(fl[k]) - ev[k].v).abs()
+            ratio = float((err / ev[k].e.clamp_min(1e-300)).max())
+            assert torch.isfinite(ev[k].e).all() and ratio <= 1.0, (k, wide, ratio)
+        y = zh.float()
+        le, lf = R.logmap0_chain(A, y, wide), R.logmap0_chain(F, y, wide)
+        assert float(((F.value(lf) - le.v).abs() / le.e.clamp_min(1e-300)).max()) <= 1.0
+
+
+def test_euclid_slot_sums_give_the_oracle_centre():
+    from oracle import ref_cpu as O
+    z = torch.randn(37, 5, generator=torch.Generator().manual_seed(2), dtype=torch.float64) * 1e-2
+    S, n, nb, G = R.euclid_slot_sums(z)
+    assert n == 37 and torch.allclose(G, torch.einsum("ni,nj->ij", z, z), rtol=1e-13, atol=1e-16)
+    assert torch.equal(O.clamp_center(S / n, 1e-3), O.clamp_center(z.sum(0) / 37, 1e-3)) and float(nb) == pytest.approx(float(z.norm(dim=1).sum()))
 
 
 @pytest.mark.parametrize("Nb,C,P", W.APPLY_SHAPES)
