@@ -12,6 +12,10 @@ chain of `window_attribution`:
   4. ops.btlnk_bwd for dU_n (its dW / db outputs go to scratch);
   5. one ops.layer_input_grad per layer, last to first.
 Everything outside the supported set raises ValueError naming the reason; nothing falls back.
+
+The decoder models' counterpart: `window_latent_attribution` runs the same chain on the autoencoder's encoder for the
+latent term of its score, and `dataset_error_maps` writes the per-joint reconstruction-error maps of `lit.window_error_map` -- no
+gradient: the map is the decomposition of the reconstruction term that the decoder-tail kernel forms beside the score.
 """
 from __future__ import annotations
 
@@ -27,10 +31,16 @@ Tensor = torch.Tensor
 
 def unsupported_reason(lit) -> Optional[str]:
     """Why `lit.window_attribution` does not take this wrapper in its current mode (host arithmetic, no device), or None."""
-    from .models.common.components import Encoder
     model = getattr(lit, "model", None)
     if model is None or hasattr(model, "decoder") or hasattr(model, "rev_btlnk") or not hasattr(model, "btlnk"):
         return "autoencoder / VAE wrappers have a decoder: their natural map is the per-joint reconstruction error, not an input gradient"
+    return encoder_unsupported_reason(model)
+
+
+def encoder_unsupported_reason(model) -> Optional[str]:
+    """Why the adjoint chain does not run through this model's encoder and bottleneck in its current mode (host arithmetic), or None:
+    the encoder-side half of `unsupported_reason`, which LitAutoEncoder.window_latent_attribution asks on its own."""
+    from .models.common.components import Encoder
     if model.training:
         return "train mode: BatchNorm couples the batch; call .eval() (the adjoint is that of the layers with folded running statistics)"
     if not isinstance(model.encoder, Encoder):
@@ -119,15 +129,59 @@ def dataset_attribution(lit, loader, outputs, directory: str) -> None:
 
 def window_attribution(lit, x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """-> (score [B], grad [B, C, T, V] = d score_n / d x_n, attr [B, T, V] = sum_c x * grad) for a LitEncoder in eval mode."""
-    from .models.graph_layers.stsgcn import layer_tensors
     why = unsupported_reason(lit)
     if why is not None:
         raise ValueError(f"window_attribution: {why}")
-    model = lit.model
+    return _input_gradient(lit.model, x, lambda z: head_score_grad(lit, z), "window_attribution")
+
+
+def window_latent_attribution(lit, x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (hyp [B], grad [B, C, T, V] = d hyp_n / d x_n, attr [B, T, V] = sum_c x * grad) for a LitAutoEncoder in eval mode: the chain
+    of `window_attribution` on the autoencoder's encoder and bottleneck with the Euclidean head on its centre, hyp = mean_j (z - c)^2
+    -- the latent term of the autoencoder's score.  The decoder does not run."""
+    model = getattr(lit, "model", None)
+    if model is None or not hasattr(model, "decoder") or not hasattr(model, "btlnk") or hasattr(model, "mean_vector"):
+        raise ValueError("window_latent_attribution: the autoencoder wrapper only (a one-class encoder has `window_attribution`; the "
+                         "VAE's score is the cosine of a sampled latent)")
+    why = encoder_unsupported_reason(model)
+    if why is not None:
+        raise ValueError(f"window_latent_attribution: {why}")
+
+    def head(z):
+        _, dz, score = ops.mse_head(z, model.c, need_grad=True, need_score=True, upstream=float(z.shape[0]))
+        return score, dz
+    return _input_gradient(model, x, head, "window_latent_attribution")
+
+
+def dataset_error_maps(lit, loader, outputs, directory: str) -> None:
+    """The reconstruction-error maps of a whole test pass as per-clip files (eval_COSKAD.py --error-map-dir): `dataset_attribution`'s
+    flow with `lit.window_error_map` -- every window's map [T, V] is held on the device (N T V floats for N windows), turned into
+    person-frame maps by eval_utils.attribution_frames_device on the scoring plan's window table (the mean over the covering windows)
+    and written by eval_utils.save_attribution as `<scene>_<clip>_error_map.npy` (mean over the transformations, NaN where the person
+    is absent) and `<scene>_<clip>_persons.npy`.  The wrapper's ValueError for a wrapper without a decoder or without a reconstruction
+    term in its score."""
+    from .utils import eval_utils
+    maps = [lit.window_error_map(b[0])[1] for b in loader()]
+    if not maps:
+        raise ValueError("dataset_error_maps: the loader yields no batch")
+    emap = torch.cat(maps, 0)
+    trans, meta, frames = (torch.cat([o[i] for o in outputs], 0) for i in (1, 2, 3))
+    if emap.shape[0] != frames.shape[0]:
+        raise ValueError(f"dataset_error_maps: {emap.shape[0]} maps for a window table of {frames.shape[0]} rows")
+    num_transform = max(1, int(getattr(lit.args, "dataset_num_transform", 1)))
+    plan = getattr(lit, "_score_plan", None)
+    if plan is None or plan.win_ptr.device != emap.device or plan.num_transform != num_transform or not plan.matches(trans, meta, frames):
+        plan = eval_utils.ScorePlan(trans, meta, frames, lit._load_gts(), num_transform, device=emap.device)
+    eval_utils.save_attribution(directory, eval_utils.attribution_frames_device(emap, frames, plan), plan, suffix="error_map")
+
+
+def _input_gradient(model, x: Tensor, head, what: str) -> Tuple[Tensor, Tensor, Tensor]:
+    """the chain of the module's docstring through `model`'s encoder and bottleneck; `head`: z -> (score [B], dz [B, L])"""
+    from .models.graph_layers.stsgcn import layer_tensors
     if x.dim() != 4 or tuple(x.shape[1:]) != (model.input_dim, model.n_frames, model.n_joints):
-        raise ValueError(f"window_attribution: expected x [B, {model.input_dim}, {model.n_frames}, {model.n_joints}], got {tuple(x.shape)}")
+        raise ValueError(f"{what}: expected x [B, {model.input_dim}, {model.n_frames}, {model.n_joints}], got {tuple(x.shape)}")
     if x.shape[0] < 1:
-        raise ValueError("window_attribution: empty batch")
+        raise ValueError(f"{what}: empty batch")
     with torch.no_grad():
         x = x.to(model.c.device, torch.float32).contiguous()
         B = x.shape[0]
@@ -135,7 +189,7 @@ def window_attribution(lit, x: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         us, folds = eval_preactivations(x, layers)
         W, top = model.btlnk.weight.contiguous(), layers[-1].slope
         z = ops.btlnk_fwd(us[-1], W, model.btlnk.bias, top, ws=model._ws)
-        score, dz = head_score_grad(lit, z)
+        score, dz = head(z)
         K, Lz = W.shape[1], W.shape[0]
         # the parameter gradients the bottleneck backward also forms are scratch here
         dW = torch.empty_like(W)

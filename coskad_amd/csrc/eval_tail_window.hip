@@ -18,7 +18,8 @@
 //   * a thread's table values (T + V per position) are read per clip through L1 / L2 (held for the launch they would cost up to 147
 //     registers, and the stream wants workgroups per CU more than it wants them);
 //   * epilogue: thread <-> four positions again: x_rec = PReLU_out(Z + R), stored as 16-byte vectors when `out` is given; the squared
-//     difference to `x` is summed lanes -> waves -> one value in a fixed order and ONE thread stores score[n].
+//     difference to `x` is summed lanes -> waves -> one value in a fixed order and ONE thread stores score[n];
+//   * (coskad_layer_tail_map_f32) the same differences also leave as the per-position error map emap[n, t, v], whose sum is score[n].
 // No atomics; a clip's results do not depend on B, on the workgroup that forms them or on the loop round.  Threads beyond a clip's
 // vectors / positions walk every barrier and store nothing.
 #include "layer_launch.h"
@@ -53,11 +54,19 @@ __device__ __forceinline__ void fma4(float4& acc, float w, const float4& x) {
 }
 __device__ __forceinline__ float4 add4(const float4& a, const float4& b) { return float4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
 
-template <int T, int V, int Ci>
+// kMap: also the clip's per-position error map, emap[n, t, v] = ((x_rec_0 - x_0)^2 + (x_rec_1 - x_1)^2) / (2 T V), from the differences the
+// score is summed from -- one 16-byte store per `own` thread, behind no barrier of its own; the score's arithmetic is untouched.  The
+// switch is the parameter pack `Map`: empty (the score / out kernel: its argument segment, and with it every instruction, is what it
+// was without the switch) or one `float` (the map kernel, whose last argument is `emap`).
+__device__ __forceinline__ float* map_base(float* p) { return p; }
+
+template <int T, int V, int Ci, typename... Map>
 __global__ __launch_bounds__(kThreads, (Geo<T, V, Ci>::PER_CU)) void k_eval_tail(
     const float* __restrict__ in, const float* __restrict__ x, float* __restrict__ out, float* __restrict__ score,
     const float* __restrict__ Aw, const float* __restrict__ Tw, const float* __restrict__ wfold, const float* __restrict__ bias,
-    const float* __restrict__ in_slope, const float* __restrict__ out_slope, int B) {
+    const float* __restrict__ in_slope, const float* __restrict__ out_slope, int B, Map* __restrict__... emap) {
+  constexpr bool kMap = sizeof...(Map) == 1;
+  static_assert(sizeof...(Map) <= 1, "at most the map's base");
   using G = Geo<T, V, Ci>;
   constexpr int TV = G::TV, R4 = G::R4, NG = G::NG, CG = G::CG;
   constexpr int CoP = 16;                                  // coskad_bn_fold_f32's column count for two output channels
@@ -181,6 +190,12 @@ __global__ __launch_bounds__(kThreads, (Geo<T, V, Ci>::PER_CU)) void k_eval_tail
                           u1.x - xt[1].x, u1.y - xt[1].y, u1.z - xt[1].z, u1.w - xt[1].w};
 #pragma unroll
       for (int k = 0; k < 8; ++k) sq = fmaf(d[k], d[k], sq);
+      if constexpr (kMap) {                                // positions idx = t V + v = 4 e4 .. 4 e4 + 3: TV % 4 == 0, a 16-byte address
+        constexpr float kScale = 1.f / (2 * TV);
+        *reinterpret_cast<float4*>(map_base(emap...) + (size_t)clip * TV + 4 * e4) =
+            float4{(d[0] * d[0] + d[4] * d[4]) * kScale, (d[1] * d[1] + d[5] * d[5]) * kScale,
+                   (d[2] * d[2] + d[6] * d[6]) * kScale, (d[3] * d[3] + d[7] * d[7]) * kScale};
+      }
     }
     if (score != nullptr) {                                // (uniform over the workgroup)
       sq = wave_sum(sq);
@@ -208,30 +223,35 @@ struct Args {
   const float* out_slope;
   int B;
   hipStream_t st;
+  float* emap;   // the map entry only
 };
 
-template <int T, int V, int Ci>
+template <int T, int V, int Ci, bool kMap>
 static void launch_one(const Args& a) {
   using G = Geo<T, V, Ci>;
   const int cap = kCUs * G::PER_CU;                        // the persistent grid: PER_CU workgroups on each CU
   const int grid = a.B < cap ? a.B : cap;
   ProbeScope probe(KID_LAYER_APPLY, Ci, 2, a.st);
-  hipLaunchKernelGGL((k_eval_tail<T, V, Ci>), dim3(grid), dim3(kThreads), 0, a.st, a.in, a.x, a.out, a.score, a.Aw, a.Tw, a.wfold,
-                     a.bias, a.in_slope, a.out_slope, a.B);
+  if constexpr (kMap)
+    hipLaunchKernelGGL((k_eval_tail<T, V, Ci, float>), dim3(grid), dim3(kThreads), 0, a.st, a.in, a.x, a.out, a.score, a.Aw, a.Tw,
+                       a.wfold, a.bias, a.in_slope, a.out_slope, a.B, a.emap);
+  else
+    hipLaunchKernelGGL((k_eval_tail<T, V, Ci>), dim3(grid), dim3(kThreads), 0, a.st, a.in, a.x, a.out, a.score, a.Aw, a.Tw, a.wfold,
+                       a.bias, a.in_slope, a.out_slope, a.B);
 }
 
-template <int T, int V>
+template <int T, int V, bool kMap>
 static void launch_tv(const Args& a, int Ci) {
-  if (Ci == 16) launch_one<T, V, 16>(a);
-  else launch_one<T, V, 32>(a);
+  if (Ci == 16) launch_one<T, V, 16, kMap>(a);
+  else launch_one<T, V, 32, kMap>(a);
 }
 
-template <int V>
+template <int V, bool kMap>
 static void launch_v(const Args& a, int T, int Ci) {
-  if (T == 8) launch_tv<8, V>(a, Ci);
-  else if (T == 12) launch_tv<12, V>(a, Ci);
-  else if (T == 16) launch_tv<16, V>(a, Ci);
-  else launch_tv<24, V>(a, Ci);
+  if (T == 8) launch_tv<8, V, kMap>(a, Ci);
+  else if (T == 12) launch_tv<12, V, kMap>(a, Ci);
+  else if (T == 16) launch_tv<16, V, kMap>(a, Ci);
+  else launch_tv<24, V, kMap>(a, Ci);
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -269,10 +289,33 @@ int coskad_layer_tail_f32(const float* in, const float* x, float* out, float* sc
   if (!evt::tail_ok(T, V, Ci, Co))
     return fail(COSKAD_ERR_SHAPE, "unsupported layer_tail shape (n_frames=%d, n_joints=%d, C_in=%d, C_out=%d): built for T in "
                 "{8,12,16,24}, V in {17,25}, C_in in {16,32}, C_out = 2", T, V, Ci, Co);
-  const evt::Args a{in, x, out, score, A, Tm, wfold, bias, in_slope, out_slope, B, stream};
-  if (V == 17) evt::launch_v<17>(a, T, Ci);
-  else evt::launch_v<25>(a, T, Ci);
+  const evt::Args a{in, x, out, score, A, Tm, wfold, bias, in_slope, out_slope, B, stream, nullptr};
+  if (V == 17) evt::launch_v<17, false>(a, T, Ci);
+  else evt::launch_v<25, false>(a, T, Ci);
   return check_launch("layer_tail");
+}
+
+int coskad_layer_tail_map_f32(const float* in, const float* x, float* out, float* score, float* emap, const float* A, const float* Tm,
+                              const float* wfold, const float* bias, const float* in_slope, const float* out_slope, int B, int Ci,
+                              int Co, int T, int V, hipStream_t stream) {
+  if (!in || !A || !Tm || !wfold || !bias) return fail(COSKAD_ERR_ARG, "layer_tail_map: null pointer");
+  if (B <= 0 || Ci <= 0 || Co <= 0) return fail(COSKAD_ERR_ARG, "layer_tail_map: B=%d Ci=%d Co=%d", B, Ci, Co);
+  if (!x) return fail(COSKAD_ERR_ARG, "layer_tail_map: the target `x` is NULL");
+  if (!score) return fail(COSKAD_ERR_ARG, "layer_tail_map: `score` is NULL");
+  if (!emap) return fail(COSKAD_ERR_ARG, "layer_tail_map: `emap` is NULL");
+  if (!evt::aligned16(in)) return fail(COSKAD_ERR_ARG, "layer_tail_map: `in` (%p) must be 16-byte aligned", (const void*)in);
+  if (!evt::aligned16(x)) return fail(COSKAD_ERR_ARG, "layer_tail_map: `x` (%p) must be 16-byte aligned", (const void*)x);
+  if (!evt::aligned16(out)) return fail(COSKAD_ERR_ARG, "layer_tail_map: `out` (%p) must be 16-byte aligned", (const void*)out);
+  if (!evt::aligned16(emap)) return fail(COSKAD_ERR_ARG, "layer_tail_map: `emap` (%p) must be 16-byte aligned", (const void*)emap);
+  if ((reinterpret_cast<uintptr_t>(score) & 3) != 0)
+    return fail(COSKAD_ERR_ARG, "layer_tail_map: `score` (%p) must be 4-byte aligned", (const void*)score);
+  if (!evt::tail_ok(T, V, Ci, Co))
+    return fail(COSKAD_ERR_SHAPE, "unsupported layer_tail_map shape (n_frames=%d, n_joints=%d, C_in=%d, C_out=%d): built for T in "
+                "{8,12,16,24}, V in {17,25}, C_in in {16,32}, C_out = 2", T, V, Ci, Co);
+  const evt::Args a{in, x, out, score, A, Tm, wfold, bias, in_slope, out_slope, B, stream, emap};
+  if (V == 17) evt::launch_v<17, true>(a, T, Ci);
+  else evt::launch_v<25, true>(a, T, Ci);
+  return check_launch("layer_tail_map");
 }
 
 }  // extern "C"

@@ -251,6 +251,10 @@ class LitEncoder(nn.Module):
         from . import attribution
         return attribution.window_attribution(self, x)
 
+    def window_error_map(self, x: torch.Tensor):
+        raise ValueError(f"window_error_map: {type(self).__name__} has no decoder, so there is no reconstruction to take the error of; "
+                         "`window_attribution` is the map of a one-class encoder")
+
     def _load_gts(self) -> Dict[Tuple[int, int], np.ndarray]:
         if self.gts is not None:
             return self.gts
@@ -324,6 +328,35 @@ class _AutogradLit(LitEncoder):
     def window_attribution(self, x: torch.Tensor):
         raise ValueError(f"window_attribution: {type(self).__name__} scores windows by reconstruction (autoencoder / VAE wrappers): the "
                          "per-joint reconstruction error is their natural map, the input gradient of a one-class score is not defined")
+
+    def window_error_map(self, x: torch.Tensor):
+        """-> (rec [B], emap [B, T, V]) of a batch of windows, eval mode: the window's mean squared reconstruction error and its exact
+        decomposition over (frame, joint), emap = ((x_rec - x)^2).sum(coordinates) / (C T V), so that emap[n].sum() == rec[n] -- where
+        the skeleton was reconstructed badly.  Where the model's decoder tail is on csrc/eval_tail_window.hip the map leaves the launch
+        that forms rec; otherwise it is the formula on the model's reconstruction.
+        The map is of the reconstruction term, UNSCALED: under LitAutoEncoder's 'rec+hyp' the score's reconstruction part is rec /
+        rec_loss_weight (plus the latent term, whose map is `window_latent_attribution`).  For LitVAE it is the map of the sampled
+        latent's reconstruction (under the same torch seed: forward's) and NOT a decomposition of its score, the cosine distance of
+        that latent.  Missing joints (exact zeros in x) are not masked: the reference's score counts them, and masking would break
+        emap.sum() == rec.  ValueError in train mode (BatchNorm would couple the batch)."""
+        why = self._error_map_refusal()
+        if why is not None:
+            raise ValueError(f"window_error_map: {why}")
+        model = self.model
+        if x.dim() != 4 or tuple(x.shape[1:]) != (model.input_dim, model.n_frames, model.n_joints):
+            raise ValueError(f"window_error_map: expected x [B, {model.input_dim}, {model.n_frames}, {model.n_joints}], got {tuple(x.shape)}")
+        if x.shape[0] < 1:
+            raise ValueError("window_error_map: empty batch")
+        with torch.no_grad():
+            _, rec, emap = model.reconstruction_map(x.to(model.c.device, torch.float32).contiguous())
+        return rec, emap
+
+    def _error_map_refusal(self) -> Optional[str]:
+        """why `window_error_map` does not take this wrapper in its current mode (host arithmetic), or None"""
+        if self.model.training:
+            return ("train mode: BatchNorm couples the batch and the reconstruction is not the scored one; call .eval() "
+                    "(Trainer.predict / validate do)")
+        return None
 
     def _build(self, args: Namespace, **extra) -> None:
         nn.Module.__init__(self)
@@ -513,6 +546,20 @@ class LitAutoEncoder(_AutogradLit):
         else:                                   # the last decoder layer and the error in one launch where the kernel is built
             z, rec = self.model.reconstruction_scores(x)
         return eval_utils.rec_and_hy_from_rec(rec, z, self.model.c, self.rec_loss_weight, self.score_type)
+
+    def _error_map_refusal(self) -> Optional[str]:
+        if self.score_type == 'hyp':
+            return ("score type 'hyp' has no reconstruction term (the score is the latent's distance to the centre): "
+                    "`window_latent_attribution` is its map")
+        return super()._error_map_refusal()
+
+    def window_latent_attribution(self, x: torch.Tensor):
+        """-> (hyp [B], grad [B, C, T, V], attr [B, T, V]) of a batch of windows, eval mode: the score's latent term hyp = mean_j (z - c)^2
+        (the whole score under 'hyp', the second term under 'rec+hyp'), its gradient with respect to the input skeleton and gradient x
+        input summed over the coordinates -- LitEncoder.window_attribution's adjoint chain on this model's encoder, bottleneck and
+        Euclidean head (coskad_amd/attribution.py).  ValueError naming the reason outside that chain's set."""
+        from . import attribution
+        return attribution.window_latent_attribution(self, x)
 
 
 class LitVAE(_AutogradLit):

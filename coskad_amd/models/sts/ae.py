@@ -278,6 +278,24 @@ class STSAE(STSE):
         Z, x_rec = out[0], out[1]
         return Z, ((x_rec - X) ** 2).reshape(X.shape[0], -1).mean(-1)
 
+    def reconstruction_map(self, X: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+        """-> (Z, rec [B], emap [B, T, V]): reconstruction_scores with the per-joint map of the error, emap = ((x_rec - X)^2).sum(1) /
+        (C T V), whose sum over (T, V) is rec.  Where `_tail_layer` holds it leaves the tail launch that forms rec (ops.layer_tail_map:
+        rec is bit for bit reconstruction_scores'); everywhere else the formula on forward's output."""
+        if len(X.shape) == 4 and self._tail_layer(X) is not None:
+            from ..graph_layers.stsgcn import layer_tensors
+            Z, (B, C, T, V, M) = self._latent(X)
+            h, slope = self._decode_head(Z, B * M, C, T, V)
+            L = layer_tensors(self.decoder.model[-1])
+            wfold, bias = engine.eval_fold(L)
+            _, rec, emap = ops.layer_tail_map(h.contiguous(), L.A, L.T, wfold, bias, L.Co, X.contiguous(), in_slope=slope,
+                                              out_slope=L.slope)
+            return Z, rec, emap
+        out = self(X)
+        Z, x_rec = out[0], out[1]
+        sq = (x_rec - X) ** 2
+        return Z, sq.reshape(X.shape[0], -1).mean(-1), sq.sum(1) / (X.shape[1] * X.shape[2] * X.shape[3])
+
     def _latent(self, X: Tensor):
         """-> (Z, input_shape): the latent forward hands to decode"""
         return self.encode(X, return_shape=True)

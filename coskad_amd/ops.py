@@ -184,6 +184,39 @@ def layer_tail(x_in: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, bias: Tensor,
     return out, score
 
 
+def layer_tail_map(x_in: Tensor, A: Tensor, Tm: Tensor, wfold: Tensor, bias: Tensor, Co: int, x: Tensor,
+                   in_slope: Optional[Tensor] = None, out_slope: Optional[Tensor] = None, want_out: bool = False,
+                   out: Optional[Tensor] = None, score: Optional[Tensor] = None, emap: Optional[Tensor] = None):
+    """layer_tail's launch against the target `x` [B, Co, T, V] with the per-position map of the error beside the score:
+    -> (out [B, Co, T, V] or None, score [B], emap [B, T, V] = ((out - x)^2).sum(1) / (Co T V)); emap[n].sum() is score[n], and score is
+    bit for bit layer_tail's.  A clip's results do not depend on the batch."""
+    B, Ci, T, V = x_in.shape
+    _chk(x_in, "x_in"); _chk(A, "A", (T, V, V)); _chk(Tm, "T", (V, T, T))
+    _chk(wfold, "wfold", (2 * Ci, cop(Co))); _chk(bias, "bias", (cop(Co),))
+    _chk(in_slope, "in_slope", (1,), optional=True); _chk(out_slope, "out_slope", (1,), optional=True)
+    if not layer_tail_ok(T, V, Ci, Co):
+        raise _lib.CoskadHipError(f"layer_tail_map: unsupported shape (n_frames={T}, n_joints={V}, C_in={Ci}, C_out={Co}): "
+                                  "layer_tail_ok is False there, and nothing falls back")
+    _chk(x, "x", (B, Co, T, V))
+    if score is None:
+        score = torch.empty(B, device=x_in.device, dtype=torch.float32)
+    else:
+        _chk(score, "score", (B,))
+    if emap is None:
+        emap = torch.empty(B, T, V, device=x_in.device, dtype=torch.float32)
+    else:
+        _chk(emap, "emap", (B, T, V))
+    if want_out:
+        if out is None:
+            out = torch.empty(B, Co, T, V, device=x_in.device, dtype=torch.float32)
+        else:
+            _chk(out, "out", (B, Co, T, V))
+    out = out if want_out else None
+    call("coskad_layer_tail_map_f32", x_in, x, out, score, emap, A, Tm, wfold, bias, in_slope, out_slope, B, Ci, Co, T, V, _stream(),
+         tag=(Ci, Co))
+    return out, score, emap
+
+
 INPUT_GRAD_FRAMES = (8, 12, 16, 24)     # window lengths, joint layouts, input and output widths of the folded layer's adjoint kernel
 INPUT_GRAD_JOINTS = (17, 25)            # (csrc/eval_layer_adj.hip)
 INPUT_GRAD_CIN = (2, 16, 32)

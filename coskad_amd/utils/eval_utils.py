@@ -298,10 +298,13 @@ def attribution_frames_device(attr: torch.Tensor, frames: torch.Tensor, plan: Sc
                                   plan.win_idx, ef)
 
 
-def save_attribution(directory: str, maps, plan: ScorePlan) -> None:
+def save_attribution(directory: str, maps, plan: ScorePlan, suffix: str = "attribution") -> None:
     """Per clip of the plan `<scene>_<clip>_attribution.npy` [persons, frames, V] float32 -- the person-frame maps [row_ptr[P], V] of
     `attribution_frames(_device)` averaged over the transformations, NaN where the person is absent -- and `<scene>_<clip>_persons.npy`,
-    the person ids of its rows (a clip nobody appears in gets arrays with no person)."""
+    the person ids of its rows (a clip nobody appears in gets arrays with no person).  `suffix`: the map file's name behind
+    `<scene>_<clip>_` (attribution.dataset_error_maps writes `error_map`)."""
+    if suffix == "persons":
+        raise ValueError("save_attribution: the suffix `persons` is the name of the person-id file")
     import os
     os.makedirs(directory, exist_ok=True)
     m = np.asarray(_host_array(maps), dtype=np.float64)
@@ -320,5 +323,5 @@ def save_attribution(directory: str, maps, plan: ScorePlan) -> None:
             cnt[k] += ok
         with np.errstate(invalid="ignore", divide="ignore"):
             out = np.where(cnt > 0, total / cnt, np.nan).astype(np.float32)
-        np.save(os.path.join(directory, f"{sc}_{cl}_attribution.npy"), out)
+        np.save(os.path.join(directory, f"{sc}_{cl}_{suffix}.npy"), out)
         np.save(os.path.join(directory, f"{sc}_{cl}_persons.npy"), ids.astype(np.int64))

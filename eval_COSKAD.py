@@ -22,6 +22,10 @@ def main():
     # per clip <scene>_<clip>_attribution.npy [persons, frames, V] (gradient x input of the window scores, mean over the covering windows
     # and the transformations, NaN where a person is absent) and <scene>_<clip>_persons.npy; one-class encoders only
     parser.add_argument('--attribution-dir', type=str, default=None)
+    # per clip <scene>_<clip>_error_map.npy [persons, frames, V] (the per-joint reconstruction error of the windows, mean over the covering
+    # windows and the transformations, NaN where a person is absent) and <scene>_<clip>_persons.npy; autoencoder / VAE configs whose
+    # score has a reconstruction term
+    parser.add_argument('--error-map-dir', type=str, default=None)
     cli = parser.parse_args()
     args = argparse.Namespace(**yaml.load(open(cli.config), Loader=yaml.FullLoader))
     if cli.report or cli.report_dir:
@@ -32,7 +36,9 @@ def main():
         from coskad_amd.lit import LitAutoEncoder
         model = LitAutoEncoder(args).cuda()
         from coskad_amd.utils.eval_utils import eval_loss_type
-        model.rec_loss_weight = 0                      # eval_COSKAD.py:58-66: the script's constant selects 'hyp'
+        # eval_COSKAD.py:58-66: the script's constant, 0, selects 'hyp'.  `eval_rec_loss_weight` (no key of the reference's yamls; 0
+        # unless set) stands for that constant: > 100 selects 'rec', any other non-zero value 'rec+hyp'
+        model.rec_loss_weight = getattr(args, 'eval_rec_loss_weight', 0)
         model.score_type = eval_loss_type(model.rec_loss_weight)
     elif args.use_vae:
         from coskad_amd.lit import LitVAE
@@ -67,6 +73,10 @@ def main():
         from coskad_amd.attribution import dataset_attribution
         dataset_attribution(model, loader_fn, out, cli.attribution_dir)
         print('attribution maps written to {}'.format(cli.attribution_dir))
+    if cli.error_map_dir and parallel.rank() == 0:
+        from coskad_amd.attribution import dataset_error_maps
+        dataset_error_maps(model, loader_fn, out, cli.error_map_dir)
+        print('error maps written to {}'.format(cli.error_map_dir))
 
 
 if __name__ == '__main__':

@@ -82,6 +82,18 @@ int coskad_layer_tail_f32(const float* in, const float* x, float* out, float* sc
                           const float* in_slope, const float* out_slope,
                           int B, int Ci, int Co, int T, int V, hipStream_t stream);
 
+/* coskad_layer_tail_f32 with, from the same launch, the per-position map of the reconstruction error (one 16-byte store per thread,
+ * no atomics, no further barrier):
+ *   emap [B, T, V] = ((out_0 - x_0)^2 + (out_1 - x_1)^2) / (2 T V),     sum over (t, v) of emap[n] = score[n]
+ * `score` is formed from the same differences by the same reduction: bit for bit what coskad_layer_tail_f32 stores.  The shape set
+ * is coskad_layer_tail_ok's and the checks are coskad_layer_tail_f32's; beyond them x, score and emap are required and emap must be
+ * 16-byte aligned (COSKAD_ERR_ARG naming the operand).  `out` stays optional.  A clip's map does not depend on B or on the workgroup
+ * that forms it. */
+int coskad_layer_tail_map_f32(const float* in, const float* x, float* out, float* score, float* emap,
+                              const float* A, const float* Tm, const float* wfold, const float* bias,
+                              const float* in_slope, const float* out_slope,
+                              int B, int Ci, int Co, int T, int V, hipStream_t stream);
+
 /* The ADJOINT of coskad_layer_apply_f32's folded layer (csrc/eval_layer_adj.hip): the gradient with respect to the layer's input of
  * whatever dU is the gradient of, one clip per workgroup on a persistent grid, no batch coupling:
  *   dIn [B, Ci, T, V] = PReLU_in'(in) (.) ( gcn^T(Wz^T . dU) + Wx^T . dU ),    dU [B, Co, T, V]
