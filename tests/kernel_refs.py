@@ -1,5 +1,6 @@
 """Float64 restatements of the stand-alone kernels the kernel-level tests compare with (test_gpu_wide_kernels.py,
-test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py), in plain torch / numpy on the CPU.  Every function takes
+test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py, test_gpu_btlnk_kernels.py), in plain torch / numpy on the
+CPU.  Every function takes
 the float32 inputs converted to double, composes the forward only -- gradients come from torch autograd on that forward, never from a
 hand-written backward -- and never calls the library.  test_kernel_refs_host.py holds them against torch.nn / torch.optim before a
 device sees them.  The one-class heads' section also restates the kernels' Poincare sequences, backward included, over a running-error
@@ -602,3 +603,128 @@ def gscale_pair(upstream, B):
     """the Poincare / Mahalanobis heads' gscale = upstream / (float)B: (exact on the float32 upstream, the kernel's float32)"""
     up = np.float32(upstream)
     return float(up) / B, float(up / np.float32(B))
+
+
+# ---- the bottleneck projection (csrc/bottleneck.hip: L <= 16; csrc/btlnk_chain.hip; csrc/btlnk_wide.hip: 16 < L <= 512) ------------------
+
+def btlnk(U, slope, W, b):
+    """z = W . PReLU(U) + b on U [B, K], W [L, K], b [L] or None (slope None: U is activated already)"""
+    X = U if slope is None else prelu(U, slope)
+    z = X @ W.T
+    return z if b is None else z + b
+
+
+def top_layer_sums(dU, Z, x_in, in_slope):
+    """the batch reductions the top layer's BatchNorm backward starts from (coskad_hip.h, coskad_btlnk_bwd_chain_f32):
+    P[o][c] = sum dU[n][o][p] Z[n][c][p], Q[o][c] = sum dU[n][o][p] PReLU(x_in)[n][c][p], s[o] = sum dU[n][o][p];
+    dU [B, Co, TV], Z / x_in [B, Ci, TV] -> (P [Co, Ci], Q [Co, Ci], s [Co])"""
+    X = x_in if in_slope is None else prelu(x_in, in_slope)
+    return torch.einsum("nop,ncp->oc", dU, Z), torch.einsum("nop,ncp->oc", dU, X), dU.sum((0, 2))
+
+
+BTLNK_MAGS = (1e-3, 1.0, 30.0)
+F32_TINY = 2.0 ** -126
+
+
+def btlnk_zero_plants(B, K, TV=None):
+    """(clip, column) of the exact zeros btlnk_inputs plants, signs alternating +0.0, -0.0 in this order: the first, second, middle
+    and last element of U; and in the last clip of every 16-clip tile one element at column (5 + 7 tile) % K and one inside the last
+    position tile (K = channels x TV positions, position innermost; TV None: one channel of K positions).  At most a quarter of U
+    (one element of a U below eight) is planted, the head of this order."""
+    TV = K if TV is None else TV
+    n = B * K
+    flat = [0, 1, n // 2, n - 1] if n > 1 else [0]
+    spots = [(e // K, e % K) for e in flat]
+    p_last = 16 * ((TV - 1) // 16)
+    for t in range(-(-B // 16)):
+        row = min(16 * t + 15, B - 1)
+        spots.append((row, (5 + 7 * t) % K))
+        ch = t % (K // TV)
+        spots.append((row, ch * TV + p_last + t % (TV - p_last)))
+    seen, out = set(), []
+    for s in spots:
+        if s not in seen:
+            seen.add(s)
+            out.append(s)
+    return out[:max(1, n // 4)]          # (a U of three or four elements keeps the others: at most a quarter is zero)
+
+
+def btlnk_inputs(B, K, L, seed, TV=None):
+    """float32 inputs of the bottleneck tests: U [B, K] a normal draw times a per-element magnitude from BTLNK_MAGS with exact +0.0 /
+    -0.0 at btlnk_zero_plants; W ~ N(0, 1 / K) [L, K]; b, dz ~ N(0, 1).  No value is subnormal (how the f32 MFMA treats subnormals is
+    not documented)."""
+    g = torch.Generator().manual_seed(seed)
+    mags = torch.tensor(BTLNK_MAGS)[torch.randint(0, len(BTLNK_MAGS), (B, K), generator=g)]
+    U = (torch.randn(B, K, generator=g) * mags).contiguous()
+    for i, (n, k) in enumerate(btlnk_zero_plants(B, K, TV)):
+        U[n, k] = -0.0 if i % 2 else 0.0
+    d = dict(U=U, W=torch.randn(L, K, generator=g) * K ** -0.5, b=torch.randn(L, generator=g), dz=torch.randn(B, L, generator=g))
+    for k, v in d.items():
+        assert not bool(((v != 0) & (v.abs() < F32_TINY)).any()), f"subnormal in {k}"
+    return d
+
+
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def round_up(a, b):
+    return ceil_div(a, b) * b
+
+
+# Restatements of the launch plans: they size the bounds (chain lengths) and prove that a test shape meets the edge it is listed for;
+# test_kernel_refs_host.py holds each against what the library reports through its workspace / row queries.
+
+def btl_chunks(B, K):
+    """csrc/bottleneck.hip btl_chunks with coskad_btlnk_bwd_f32's chunk length -> (S clip chunks, clips per chunk)"""
+    gx = ceil_div(K, 256)
+    s = max(1, min((1024 + gx // 2) // gx, ceil_div(B, 16), 64))
+    return s, round_up(ceil_div(B, s), 16)
+
+
+def btl_bwd_ws_floats(B, K, L):
+    S, _ = btl_chunks(B, K)
+    return S * L * K + S * ceil_div(K, 256) + 64
+
+
+def chain_plan(B, TV):
+    """csrc/btlnk_chain.hip bc::plan -> (position tiles, S clip chunks, clips per chunk); rows = position tiles x S"""
+    npt = ceil_div(TV, 16)
+    s = max(1, min(256 // npt, ceil_div(B, 16)))
+    chunk = round_up(ceil_div(B, s), 16)
+    return npt, ceil_div(B, chunk), chunk
+
+
+def chain_floats(B, TV, Ci, Co=64):
+    npt, S, _ = chain_plan(B, TV)
+    E = 2 * Co * Ci + Co
+    return (npt * S * E + 1) // 2 * 2 + 2 * E
+
+
+def wide_tile(L):
+    """bw::fwd_tn / bw::dw_tm: 16-wide MFMA tiles per wave along the latent axis"""
+    return 1 if L <= 32 else (2 if L <= 64 else 4)
+
+
+def wide_fwd_rchunk(K, L):
+    ks = max(2, 16 // ceil_div(L, 32 * wide_tile(L)))
+    ks = max(1, min(ks, ceil_div(K, 8 * 16)))
+    return round_up(ceil_div(K, ks), 16)
+
+
+def wide_fwd_slices(K, L):
+    return ceil_div(K, wide_fwd_rchunk(K, L))
+
+
+def wide_dw_chunk(B, K, L):
+    tiles = ceil_div(K, 128) * ceil_div(L, 32 * wide_tile(L))
+    s = max(1, min((1024 + tiles // 2) // tiles, 64))
+    return round_up(ceil_div(B, s), 16)
+
+
+def wide_dw_chunks(B, K, L):
+    return ceil_div(B, wide_dw_chunk(B, K, L))
+
+
+def wide_dx_blocks(B, K):
+    return ceil_div(K, 128) * ceil_div(B, 128)

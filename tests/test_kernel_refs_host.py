@@ -263,3 +263,166 @@ def test_kink_share_of_the_reference_alone(Nb, C, P):
             share = float(k["kink"].double().mean())
             assert share <= 1e-3, (residual_bn, training, drop_p, share)
             assert torch.isfinite(k["out_ref"]).all() and all(torch.isfinite(g).all() for g in k["grads"].values())
+
+
+# ---- the bottleneck: references, input builder, launch-plan restatements, and the edge every test shape is listed for -------------------
+
+@pytest.mark.parametrize("a", [None, 0.25, 0.0, -0.5, 1.0])
+def test_btlnk_is_linear_of_prelu(a):
+    """kernel_refs.btlnk == nn.Linear(nn.PReLU(U)) in double, z and every gradient, on kernel_refs.btlnk_inputs (exact +0.0 / -0.0 in U:
+    the derivative at zero is the slope's side in both); slope None: the Linear alone; without a bias too"""
+    B, K, L = 19, 36, 5
+    d = R.btlnk_inputs(B, K, L, seed=4)
+    dz = d["dz"].double()
+    res = []
+    for ref in (True, False):
+        U, Wm, b = (d[k].double().clone().requires_grad_(True) for k in ("U", "W", "b"))
+        s = None if a is None else torch.tensor([a], dtype=torch.float64, requires_grad=True)
+        if ref:
+            z = R.btlnk(U, s, Wm, b)
+        else:
+            z = F.linear(U if a is None else F.prelu(U, s), Wm, b)
+        res.append((z,) + torch.autograd.grad(z, [U, Wm, b] + ([] if a is None else [s]), dz))
+    for k, (x, y) in enumerate(zip(*res)):
+        _close(x.reshape(-1), y.reshape(-1), f"btlnk {k}")
+    n0, k0 = R.btlnk_zero_plants(B, K)[0]
+    if a is not None:
+        assert float(res[0][1][n0, k0]) == float(res[1][1][n0, k0]) == a * float((dz @ d["W"].double())[n0, k0])
+    U, Wm = d["U"].double(), d["W"].double()
+    _close(R.btlnk(U, None, Wm, None), F.linear(U, Wm), "no bias")
+
+
+@pytest.mark.parametrize("a_in", [None, 0.2])
+def test_top_layer_sums_are_the_weight_gradients(a_in):
+    """kernel_refs.top_layer_sums == autograd of sum dU (Wz Z + Wx PReLU(x) + bias) with respect to Wz, Wx and the bias"""
+    g = torch.Generator().manual_seed(12)
+    B, Co, Ci, TV = 5, 6, 3, 11
+    dU, Z, x = (torch.randn(B, c, TV, generator=g, dtype=torch.float64) for c in (Co, Ci, Ci))
+    Wz, Wx = (torch.randn(Co, Ci, generator=g, dtype=torch.float64).requires_grad_(True) for _ in range(2))
+    bias = torch.zeros(Co, dtype=torch.float64, requires_grad=True)
+    X = x if a_in is None else F.prelu(x, torch.tensor([a_in], dtype=torch.float64))
+    out = torch.einsum("oc,ncp->nop", Wz, Z) + torch.einsum("oc,ncp->nop", Wx, X) + bias[None, :, None]
+    want = torch.autograd.grad((dU * out).sum(), [Wz, Wx, bias])
+    for k, (x_, y_) in enumerate(zip(R.top_layer_sums(dU, Z, x, a_in), want)):
+        _close(x_.reshape(-1), y_.reshape(-1), f"sums {k}")
+
+
+@pytest.mark.parametrize("B,K,TV", [(1, 4, None), (1, 3, None), (17, 260, None), (100, 64 * 600, 600), (33, 64 * 20, 20)])
+def test_btlnk_inputs_plants_and_magnitudes(B, K, TV):
+    """the planted elements are exact zeros of alternating sign; first, second, middle and last element, one element of the last clip
+    of every 16-clip tile and one in the last position tile are among them; nothing else is zero, nothing is subnormal; the three
+    magnitudes all occur"""
+    d = R.btlnk_inputs(B, K, 5, seed=1, TV=TV)
+    U = d["U"]
+    spots = R.btlnk_zero_plants(B, K, TV)
+    assert int((U == 0).sum()) == len(spots) <= max(1, B * K // 4)
+    for i, (n, k) in enumerate(spots):
+        assert float(U[n, k]) == 0.0 and bool(torch.signbit(U[n, k])) == bool(i % 2)
+    if B * K >= 64:
+        flat = {n * K + k for n, k in spots}
+        assert {0, 1, B * K // 2, B * K - 1} <= flat
+        tv = K if TV is None else TV
+        for t in range(R.ceil_div(B, 16)):
+            row = min(16 * t + 15, B - 1)
+            cols = [k for n, k in spots if n == row]
+            assert cols and any(k % tv >= 16 * ((tv - 1) // 16) for k in cols), t
+        a = U.abs()
+        assert bool((a[a > 0] >= R.F32_TINY).all()) and float(a.max()) > 30.0 and 0 < float(a[a > 0].min()) < 1e-3
+    assert tuple(d["W"].shape) == (5, K) and tuple(d["dz"].shape) == (B, 5) and tuple(d["b"].shape) == (5,)
+
+
+def _library():
+    from coskad_amd import _lib
+    return _lib.lib()
+
+
+def test_btlnk_plan_restatements_match_the_library():
+    """kernel_refs.btl_chunks, chain_plan, wide_fwd_slices, wide_dw_chunks, wide_dx_blocks against the library's pure-host size queries
+    (no device is touched), at every shape of test_gpu_btlnk_kernels.py and over a grid of others"""
+    import test_gpu_btlnk_kernels as BK
+    lib = _library()
+    KS = lib.coskad_btlnk_fwd_ks()
+    assert 1 <= KS <= 8
+    narrow = list(BK.BWD_SHAPES) + [(B, K, L) for B in (1, 16, 17, 300, 1024, 1025, 4096) for K in (4, 252, 256, 260, 816, 13056, 26112)
+                                    for L in (1, 9, 16)]
+    for B, K, L in narrow:
+        assert lib.coskad_btlnk_bwd_ws_bytes(B, K, L) == 4 * R.btl_bwd_ws_floats(B, K, L), (B, K, L)
+        assert lib.coskad_btlnk_fwd_ws_bytes_l(B, K, L) == 4 * KS * B * 16
+        S, chunk = R.btl_chunks(B, K)
+        assert 1 <= S <= 64 and chunk % 16 == 0 and S * chunk >= B
+    chain = [(B, TV, Ci, L) for B, TV, Ci, L in BK.CHAIN_SHAPES + BK.RIDE_SHAPES]
+    chain += [(B, TV, Ci, 16) for B in (1, 16, 17, 255, 256, 257, 4096) for TV in (4, 16, 136, 204, 272, 300, 408, 600) for Ci in (16, 32)]
+    for B, TV, Ci, L in chain:
+        npt, S, chunk = R.chain_plan(B, TV)
+        K = 64 * TV
+        assert lib.coskad_btlnk_bwd_chain_ok(K, TV, Ci) == 1
+        assert lib.coskad_btlnk_bwd_chain_rows(B, TV) == npt * S, (B, TV)
+        assert lib.coskad_btlnk_bwd_chain_ws_bytes(B, K, L, TV) == 4 * (S * L * K + S * npt + 64)
+        assert lib.coskad_btlnk_bwd_chain_floats(B, TV, Ci) == R.chain_floats(B, TV, Ci)
+        assert chunk % 16 == 0 and (S - 1) * chunk < B <= S * chunk             # the chain kernel has no empty chunk
+    wide = list(BK.WIDE_SHAPES) + [(B, K, L) for B in (1, 128, 129, 1025, 4096) for K in (3, 128, 129, 1030, 13056) for L in (17, 32, 33, 64,
+                                                                                                                         65, 128, 129, 512)]
+    for B, K, L in wide:
+        assert lib.coskad_btlnk_fwd_ws_bytes_l(B, K, L) == 4 * R.wide_fwd_slices(K, L) * B * L, (B, K, L)
+        assert lib.coskad_btlnk_bwd_ws_bytes(B, K, L) == 4 * (R.wide_dw_chunks(B, K, L) * L * K + R.wide_dx_blocks(B, K) + 64), (B, K, L)
+        assert R.wide_fwd_rchunk(K, L) % 16 == 0 and R.wide_dw_chunk(B, K, L) % 16 == 0
+
+
+def test_btlnk_shapes_meet_the_edges_they_are_listed_for():
+    """every shape of test_gpu_btlnk_kernels.py, from the plan restatements alone (held to the library above): a later change of a
+    launcher that moves a case off its edge fails here"""
+    import test_gpu_btlnk_kernels as BK
+    cd = R.ceil_div
+    # (a) direct forward: k-steps over eight waves
+    steps = [cd(K, 16) for K in BK.FWD_K_DIRECT]
+    assert steps == [1, 2, 3, 17, 52]
+    assert [K % 16 for K in BK.FWD_K_DIRECT] == [4, 4, 0, 0, 4]                          # the k < K tail, and K = 4: one lane group
+    per = [cd(s, 8) for s in steps]
+    assert [sum(1 for w in range(8) if w * p >= s) for p, s in zip(per, steps)] == [7, 6, 5, 2, 0]       # empty waves
+    assert per[3] % 4 and per[4] % 4                                                      # a partly filled batch of UB = 4 k-steps
+    assert set(BK.FWD_BS) >= {1, 15, 16, 17, 63, 64, 65, 130}
+    # split-K forward: 16 wave groups, empty and odd-length slices
+    G = 4 * _library().coskad_btlnk_fwd_ks()
+    lens = {K: [K // 16 * (g + 1) // G - K // 16 * g // G for g in range(G)] for K in BK.FWD_K_SPLIT}
+    assert [K // 16 for K in BK.FWD_K_SPLIT] == [1, 5, 17, 81] and all(K % 16 == 0 for K in BK.FWD_K_SPLIT)
+    assert 0 in lens[16] and 0 in lens[80] and any(l % 2 for l in lens[272]) and any(l % 2 for l in lens[1296]) and min(lens[1296]) >= 5
+    assert all(K < 256 for K in BK.FWD_K_SPLIT[:2])
+    # (b) narrow backward
+    plan = {s: R.btl_chunks(s[0], s[1]) for s in BK.BWD_SHAPES}
+    assert plan[(1, 4, 1)] == (1, 16) and plan[(15, 20, 5)] == (1, 16)
+    assert 260 % 256 == 4 and plan[(17, 260, 16)] == (2, 16)                            # a second column block of one lane
+    assert plan[(100, 272, 15)] == (7, 16)                                              # fewer slabs than the unroll of eight
+    S, chunk = plan[(330, 13056, 16)]
+    assert S * chunk - 330 >= chunk                                                      # wholly empty chunks at the production K
+    assert plan[(1041, 272, 16)] == (64, 32) and sum(1 for y in range(64) if y * 32 >= 1041) == 31
+    S, chunk = plan[(1041, 1280, 5)]
+    assert cd(1280, 256) * S == 320 > 256 and 1041 > 4 * 256                            # slope partials and clips per db thread column
+    S, chunk = plan[(145, 272, 8)]
+    assert S == 10 and S > 8 and S % 8                                                   # the dW slab loop's remainder behind one round
+    # (c) chain backward
+    cp = {s: R.chain_plan(s[0], s[1]) for s in BK.CHAIN_SHAPES}
+    assert all(s[1] % 4 == 0 and s[2] in (16, 32) for s in BK.CHAIN_SHAPES)
+    assert cp[(1, 4, 16, 1)] == (1, 1, 16)
+    npt, S, chunk = cp[(17, 20, 32, 8)]
+    assert npt * S == 4 < 8 and 20 - 16 * (npt - 1) == 4                                # nwg < 8; a last position tile of 4
+    assert 136 - 16 * (cp[(37, 136, 16, 16)][0] - 1) == 8                               # a last position tile of 8
+    assert 204 - 16 * (cp[(40, 204, 32, 16)][0] - 1) == 12
+    npt, S, chunk = cp[(100, 600, 32, 16)]
+    assert chunk == 32 and 100 - (S - 1) * chunk == 4 and npt * S > 128                 # two tiles per workgroup, a last chunk of 4
+    assert cp[(700, 204, 32, 9)][2] == 48                                               # three tiles per workgroup
+    npt, S, chunk = cp[(1120, 20, 16, 16)]
+    assert npt * S == 140 and S == 70                                                    # the unrolled row sum (rows > 7 * 16) and slab sum
+    npt, S, chunk = cp[(33, 272, 32, 5)]
+    assert 272 % 16 == 0 and 33 - (S - 1) * chunk == 1
+    assert {s[2] for s in BK.CHAIN_SHAPES} == {16, 32} and {s[3] for s in BK.CHAIN_SHAPES} >= {1, 5, 8, 9, 16}
+    # (d) riding head: two head blocks behind the backward's workgroups
+    assert R.head_blocks(600, 16) == 2 and R.head_blocks(100, 16) == 1
+    # (e) wide
+    assert {R.wide_tile(s[2]) for s in BK.WIDE_SHAPES} == {1, 2, 4}
+    sl = {s: R.wide_fwd_slices(s[1], s[2]) for s in BK.WIDE_SHAPES}
+    assert sl[(1, 3, 17)] == 1 and sl[(127, 100, 32)] == 1 and sl[(260, 100, 200)] == 1
+    assert sl[(300, 272, 64)] == 3 and 272 - 2 * R.wide_fwd_rchunk(272, 64) == 80 < R.wide_fwd_rchunk(272, 64)       # the last slice ragged
+    assert sl[(129, 1030, 65)] == 9 and 1030 % 4 == 2 and sl[(40, 129, 129)] == 2 and sl[(20, 272, 512)] == 3
+    assert {s[0] for s in BK.WIDE_SHAPES} >= {127, 129} and {s[1] for s in BK.WIDE_SHAPES} >= {100, 129, 272}       # both sides of 128
+    assert R.wide_dw_chunk(1040, 36, 40) == 32 and all(R.wide_dw_chunk(*s) == 16 for s in BK.WIDE_SHAPES[:-1])
+    assert R.wide_dw_chunks(300, 272, 64) == 19 > 8 and R.wide_dx_blocks(300, 272) == 9
