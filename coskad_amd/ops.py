@@ -1813,3 +1813,83 @@ def score_report_thresholds(sorted_scores, cum_neg, out=None):
     ws = torch.empty(max(1, 2 * R * ((F + REPORT_TILE - 1) // REPORT_TILE)), device=sorted_scores.device, dtype=torch.int32)
     call("coskad_score_report_thresholds_f64", sorted_scores, cum_neg, out, ws, ws.numel(), R, F, _stream())
     return out
+
+
+# ---- online scoring of live pose tracks (csrc/stream.hip; bookkeeping and the public class in coskad_amd/stream.py) ----
+
+STREAM_WINDOWS = (8, 12, 16, 24)    # window lengths of the stream kernels
+STREAM_JOINTS = (14, 17, 18)        # headless, plain, kp18_format
+STREAM_KP18, STREAM_HEADLESS, STREAM_NORMALISED = 1, 2, 4       # layout flags of coskad_stream_push_f32
+
+
+def stream_ok(T: int, V: int) -> bool:
+    """Host arithmetic of `coskad_stream_ok`: the stream kernels take windows of T frames and V joints.  Restated here so that the
+    bookkeeping of coskad_amd/stream.py needs no native library; tests/test_stream_host.py holds the two in agreement."""
+    return T in STREAM_WINDOWS and V in STREAM_JOINTS
+
+
+def stream_rows(T: int, step: int) -> int:
+    """R = (T - 1) step + 1: the rows from a window's first to its last, the length of a track's rings"""
+    return (T - 1) * step + 1
+
+
+def _chk_host_i32(t: Tensor, name: str, n: int) -> None:
+    if t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
+        raise ValueError(f"{name}: expected {n} contiguous int32 values on the host")
+
+
+def stream_push(raw, slot, slot_host, reset, out_index, center, scale, vid_res, flags, mats, ring, count, m, T, V, step):
+    """One frame of detections into the tracks' rings, and the K transformed copies of every window that became full
+    (`coskad_stream_push_f32`): raw [n, 34] f32 pixel rows, slot / reset / out_index [n] int32 on the device, slot_host the host's copy
+    of `slot`, center / scale [34] f64 or None, vid_res (width, height) or None with STREAM_NORMALISED, mats [K, 3, 3], ring
+    [M, R, 2, V], count [M].  -> x_out [K m, 2, T, V] (None at m = 0)."""
+    n, M, K = raw.shape[0], count.numel(), mats.shape[0]
+    R = stream_rows(T, step)
+    _chk(raw, "raw", (n, 34)); _chk(mats, "mats", (K, 3, 3)); _chk(ring, "ring", (M, R, 2, V)); _chk(count, "count", (M,), dtype=torch.int32)
+    for name, t in (("slot", slot), ("reset", reset), ("out_index", out_index)):
+        _chk(t, name, (n,), dtype=torch.int32)
+    _chk_host_i32(slot_host, "slot_host", n)
+    _chk(center, "center", (34,), dtype=torch.float64, optional=True); _chk(scale, "scale", (34,), dtype=torch.float64, optional=True)
+    width, height = (0.0, 0.0) if vid_res is None else (float(vid_res[0]), float(vid_res[1]))
+    x_out = torch.empty(K * m, 2, T, V, device=raw.device, dtype=torch.float32) if m > 0 else None
+    call("coskad_stream_push_f32", raw, slot, slot_host, reset, out_index, center, scale, width, height, flags, mats, ring, count, x_out,
+         n, m, M, K, T, V, step, _stream())
+    return x_out
+
+
+def stream_frames(scores, slot, slot_host, clip_index, count, wscore, clip, T, step):
+    """The scores [K m] of a push's windows into the tracks' score rings; -> frame_mean [K, m] f64, the row of every ready track that
+    became final (`coskad_stream_frames_f64`).  clip [K, clip_frames] f64 or None: folded at clip_index [m] by a 64-bit atomic max."""
+    if scores.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"scores: expected float32 or float64, got {scores.dtype}")
+    M, K, R = wscore.shape
+    m = slot.numel()
+    _chk(scores, "scores", dtype=scores.dtype); _chk(slot, "slot", (m,), dtype=torch.int32); _chk(count, "count", (M,), dtype=torch.int32)
+    _chk(wscore, "wscore", (M, K, stream_rows(T, step)), dtype=torch.float64)
+    _chk_host_i32(slot_host, "slot_host", m)
+    if scores.numel() != K * m:
+        raise ValueError(f"scores: expected {K} x {m} values, got {scores.numel()}")
+    _chk(clip, "clip", dtype=torch.float64, optional=True)
+    if clip is not None:
+        _chk(clip_index, "clip_index", (m,), dtype=torch.int32)
+    out = torch.empty(K, m, device=scores.device, dtype=torch.float64)
+    call("coskad_stream_frames_f64", scores, int(scores.dtype == torch.float64), slot, slot_host, clip_index if clip is not None else None,
+         count, wscore, out, clip, clip.shape[1] if clip is not None else 0, m, M, K, T, step, _stream())
+    return out
+
+
+def stream_close(row_slot, row_slot_host, row_index, clip_index, count, wscore, clip, T, step):
+    """The trailing rows of closed tracks, final with the windows that exist (`coskad_stream_close_f64`): row_slot / row_index [rows]
+    int32 -> frame_mean [K, rows] f64, folded into clip like `stream_frames`."""
+    M, K, R = wscore.shape
+    rows = row_slot.numel()
+    _chk(row_slot, "row_slot", (rows,), dtype=torch.int32); _chk(row_index, "row_index", (rows,), dtype=torch.int32)
+    _chk(count, "count", (M,), dtype=torch.int32); _chk(wscore, "wscore", (M, K, stream_rows(T, step)), dtype=torch.float64)
+    _chk_host_i32(row_slot_host, "row_slot_host", rows)
+    _chk(clip, "clip", dtype=torch.float64, optional=True)
+    if clip is not None:
+        _chk(clip_index, "clip_index", (rows,), dtype=torch.int32)
+    out = torch.empty(K, rows, device=wscore.device, dtype=torch.float64)
+    call("coskad_stream_close_f64", row_slot, row_slot_host, row_index, clip_index if clip is not None else None, count, wscore, out, clip,
+         clip.shape[1] if clip is not None else 0, rows, M, K, T, step, _stream())
+    return out

@@ -593,6 +593,39 @@ int coskad_score_report_thresholds_f64(const double* sorted_scores, const long l
 int coskad_attribution_frames_f64(const float* attr, const int* frames, const int* win_ptr, const int* win_idx, const int* entry_frame,
                                   double* out, int n_windows, int n_rows, int T, int V, hipStream_t stream);
 
+/* ---- online scoring: live pose tracks, one frame at a time (csrc/stream.hip; coskad_amd/stream.py) ------------------------------- */
+
+/* The offline route's arithmetic per frame.  State of M tracks, R = (T - 1) step + 1: ring [M, R, 2, V] f32 (row r of a track at slot
+ * r % R), count [M] int32 (rows pushed per track), wscore [M, K, R] f64 (the score of the window ENDING at row e at slot e % R).
+ *   push  : one wave per detection.  raw [n, 34] pixel rows (x1, y1, ...; zeros = missing joint) -> bounding-box-centred coordinates
+ *           (utils/data.py:9-43,159-181, fp32) -> RobustScaler (center / scale [34] f64, both NULL = normalize_pose off; f32(f64(x) -
+ *           center), then f32(f64(.) / scale); a centred 0 stays 0) -> layout (flags: 1 kp18_format, 2 headless; V = 17 / 18 / 14) ->
+ *           ring row count[slot] (count <- 0 first where reset[i] != 0), count + 1.  flags & 4: the rows are normalised already and only
+ *           the layout applies.  Where out_index[i] = j >= 0 the window that ends at this row (rows e - (R - 1) + t step) is written K
+ *           times: x_out[k m + j] = (M[k][c][0] x + M[k][c][1] y) + M[k][c][2], bit for bit coskad_gather_frames_f32's items;
+ *           x_out [K m, 2, T, V] (may be NULL at m = 0), mats [K, 3, 3].  A ready row whose count is below R gives a zero window.
+ *   frames: scores [K m] of x_out (floats, or doubles with scores_f64) -> wscore; frame_mean [K, m] = for each ready track the row
+ *           e - (R - 1), final now: the mean over the windows that end at e - t step (t < T, end >= R - 1) by ascending window start,
+ *           exact zeros missing, 0 when none is left (the rules of coskad_score_person_frames_f64).  clip [K, clip_frames] (or NULL):
+ *           clip[k][clip_index[j]] = max(., mean), an unsigned 64-bit atomic max on the bit pattern (scores are non-negative; the max
+ *           is order-free, so the result is reproducible); clip_index[j] outside [0, clip_frames) is skipped.
+ *   close : row_slot / row_index [rows]: trailing rows of closed tracks (at most min(count, R - 1) per track) -> frame_mean [K, rows]
+ *           from the windows that exist (0 for a track that never filled one), folded into clip likewise.
+ * slot_host / row_slot_host: the host's copy of the slots, which the launcher checks before the launch.  NULL pointers, non-positive
+ * sizes, m > n, a slot outside [0, M) or twice in one push / frames launch, V that does not match the flags: COSKAD_ERR_ARG;
+ * T outside {8, 12, 16, 24} or V outside {14, 17, 18}: COSKAD_ERR_SHAPE; all before the device is touched. */
+int coskad_stream_ok(int T, int V);
+int coskad_stream_push_f32(const float* raw, const int* slot, const int* slot_host, const int* reset, const int* out_index,
+                           const double* center, const double* scale, float width, float height, int flags, const float* mats,
+                           float* ring, int* count, float* x_out, int n, int m, int M, int K, int T, int V, int step,
+                           hipStream_t stream);
+int coskad_stream_frames_f64(const void* scores, int scores_f64, const int* slot, const int* slot_host, const int* clip_index,
+                             const int* count, double* wscore, double* frame_mean, double* clip, int clip_frames, int m, int M, int K,
+                             int T, int step, hipStream_t stream);
+int coskad_stream_close_f64(const int* row_slot, const int* row_slot_host, const int* row_index, const int* clip_index, const int* count,
+                            const double* wscore, double* frame_mean, double* clip, int clip_frames, int rows, int M, int K, int T,
+                            int step, hipStream_t stream);
+
 /* ---- one-class heads, centre statistics, regulariser, optimiser ------------------------ */
 
 int coskad_head_slots(void);            /* floats in a stats / acc block (19) at latent <= 16 */
