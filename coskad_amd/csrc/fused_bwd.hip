@@ -113,12 +113,23 @@ constexpr int bpc_occ(int CT, int NS) { return CT == 1 && NS == 0 ? 3 : 2; }
 // instantiations, whose workgroups have no LDS to spare.
 constexpr bool bpc_tlds(int CT, int OT, int NS) { return bpc_occ(CT, NS) == 2 && OT < 4; }
 constexpr int TF_F = V * 3 * 64, AS_F = T * 5 * 64, ET_F = 256;
-constexpr int bpc_lds_floats(int CT, int OT, int NS) {
-  return WAVE_LDS_W + 4 * 256 + (bpc_tlds(CT, OT, NS) ? TF_F + AS_F + ET_F + CT * CT * 256 + 2 * 16 * CT : 0);
+// Sums carried over the workgroup's clips that ONE phase touches are parked in LDS outside it, so that the K pass (the register
+// peak: two accumulator sets, the ring, two operand sets) does not hold them: each wave has a private lane-major slot behind the
+// window (one float4 per lane and register quad: ds_write_b128 / ds_read_b128 of 64 consecutive float4, conflict-free; only the
+// owning wave touches it, so no barrier).  A phase restores its sums at entry and parks them at exit; they come back for good in
+// front of the end-of-launch row, which takes the first 32 KB + the extra row: the slots lie behind both.  What is parked is
+// set by the LDS a workgroup may take at the kernel's occupancy: 32 -> 64 with the chain has 36 KB to spare (dT's 5 quads and the
+// chain's 4: 36 KB for the four waves, 80 640 B of 81 920 in all); the parameter-operand instantiations have 2.4 KB and the
+// three-per-CU ones 9.5 KB: they park nothing.
+constexpr int PK_DT = 1, PK_NS = 2;
+constexpr int bpc_park(int CT, int OT, int NS) { return CT == 2 && OT == 4 && NS == 2 ? PK_DT | PK_NS : 0; }
+constexpr int bpc_park_quads(int CT, int OT, int NS, int CB) {
+  return ((bpc_park(CT, OT, NS) & PK_DT) ? (V + 3) / 4 : 0) + ((bpc_park(CT, OT, NS) & PK_NS) ? (NS == 2 ? 2 * CB : 1) * CT : 0);
 }
-#ifndef FBB_BDBL   // K passes: operands of k-step s+1 read in front of step s's MFMAs (two register sets) / behind them (one): same speed
-#define FBB_BDBL 0
-#endif
+constexpr int bpc_lds_floats(int CT, int OT, int NS, int CB) {
+  return WAVE_LDS_W + 4 * 256 + (bpc_tlds(CT, OT, NS) ? TF_F + AS_F + ET_F + CT * CT * 256 + 2 * 16 * CT : 0) +
+         4 * 256 * bpc_park_quads(CT, OT, NS, CB);
+}
 #ifndef FBB_SKIP   // timing-only builds (wrong results): 1 temporal mixes, 2 K passes, 4 dA, 8 spatial, 16 dT, 32 row pass + statistics
 #define FBB_SKIP 0
 #endif
@@ -144,6 +155,10 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
   float* et = as + AS_F;
   float* krl = et + ET_F;
   float* kql = krl + CT * CT * 256;
+  constexpr int PARK = bpc_park(CT, OT, NS);
+  static_assert(!(PARK && TLDS), "the parked sums' slots start where the parameter operands would");
+  static_assert(bpc_lds_floats(CT, OT, NS, CB) * 4 * bpc_occ(CT, NS) <= 160 * 1024, "LDS: the occupancy the registers allow");
+  f32x4* pk = reinterpret_cast<f32x4*>(lds + WAVE_LDS_W + 4 * 256) + (threadIdx.x >> 6) * bpc_park_quads(CT, OT, NS, CB) * 64 + (threadIdx.x & 63);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   auto geo = [&]() {
@@ -204,6 +219,38 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
     for (int c = 0; c < CT; ++c) nsb[g][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int c = 0; c < CT; ++c) nss[c] = 0.f;
+  // parked sums: quads [0, MAXJ) dTacc, then nsb
+  auto park_dt = [&]() {
+    if constexpr ((PARK & PK_DT) != 0) {
+#pragma unroll
+      for (int k = 0; k < MAXJ; ++k) pk[64 * k] = dTacc[k];
+    }
+  };
+  auto restore_dt = [&]() {
+    if constexpr ((PARK & PK_DT) != 0) {
+#pragma unroll
+      for (int k = 0; k < MAXJ; ++k) dTacc[k] = pk[64 * k];
+    }
+  };
+  constexpr int PK_NS0 = (PARK & PK_DT) ? MAXJ : 0;
+  auto park_ns = [&]() {
+    if constexpr ((PARK & PK_NS) != 0) {
+#pragma unroll
+      for (int g = 0; g < NGB; ++g)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) pk[64 * (PK_NS0 + g * CT + c)] = nsb[g][c];
+    }
+  };
+  auto restore_ns = [&]() {
+    if constexpr ((PARK & PK_NS) != 0) {
+#pragma unroll
+      for (int g = 0; g < NGB; ++g)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) nsb[g][c] = pk[64 * (PK_NS0 + g * CT + c)];
+    }
+  };
+  park_dt();
+  park_ns();
   const bool bpre = NS != 0 && below_slope != nullptr;
   const float a_b = bpre ? below_slope[0] : 0.f;
 
@@ -357,7 +404,7 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
         }
       };
       cload(0, 0);
-      float b[1 + FBB_BDBL][MAXF + 1];
+      float b[2][MAXF + 1];                              // two operand sets: k-step s + 1's batch flies during step s's products
 #pragma unroll
       for (int k = 0; k <= MAXF; ++k) b[0][k] = r2[L.q * LDW + pos_of(k)];
 #pragma unroll
@@ -368,7 +415,7 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
           // every wave has read rows 4s .. 4s+3 (a k-step ago); in the last group: its fourth quarter (stored a k-step ago) is visible
           if (g + 1 < NG || s == 0) __syncthreads();
           const int sn = (s + 1) & 3;
-          if (FBB_BDBL && (s + 1 < 4 || g + 1 < NG)) {   // the next k-step's operands take off in front of this step's MFMAs
+          if (s + 1 < 4 || g + 1 < NG) {                 // the next k-step's operands: ONE batch in front of this step's MFMAs
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k <= MAXF; ++k) b[(s + 1) & 1][k] = r2[(4 * sn + L.q) * LDW + pos_of(k)];
@@ -380,15 +427,11 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
           }
 #pragma unroll
           for (int k = 0; k <= MAXF; ++k)
-            if (k < MAXF || with16) acc[k] = mfma(wc[g & 1][s], b[FBB_BDBL ? (s & 1) : 0][k], acc[k]);
+            if (k < MAXF || with16) acc[k] = mfma(wc[g & 1][s], b[s & 1][k], acc[k]);
           if (DUAL && g < OT) {
 #pragma unroll
             for (int k = 0; k <= MAXF; ++k)
-              if (k < MAXF || with16b) acc2[k] = mfma(wc2[g & 1][s], b[FBB_BDBL ? (s & 1) : 0][k], acc2[k]);
-          }
-          if (!FBB_BDBL && (s + 1 < 4 || g + 1 < NG)) {  // single set: the next k-step's operands behind this step's MFMAs
-#pragma unroll
-            for (int k = 0; k <= MAXF; ++k) b[0][k] = r2[(4 * sn + L.q) * LDW + pos_of(k)];
+              if (k < MAXF || with16b) acc2[k] = mfma(wc2[g & 1][s], b[s & 1][k], acc2[k]);
           }
         }
       }
@@ -448,7 +491,29 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
     // ---- dT[v] += X_v^T dY_v for this wave's joints: X re-staged 16 rows at a time in the window --------------------------------
     L = geo();
     {
-      const int ic = L.j < T ? L.j : T - 1;
+      const bool tj = L.j < T;
+      const int ic = tj ? L.j : T - 1;
+      // The operands of one k-step are read as ONE batch, a step ahead of the products that consume them (two operand sets): a
+      // read -> wait -> MFMA link per product left one LDS round trip exposed in front of every 32-cycle MFMA.  A set is waited
+      // for once, where its `L.j < T` selects are applied; the next step's batch takes off behind that, in front of the products.
+      struct DtOps { float bx[MAXF + 1], a[MAXJ], bb[MAXJ]; };
+      auto dt_reads = [&](DtOps& o, int h, int s) {
+        const float* w = r2 + (4 * s + L.q) * LDW;
+        const float* y = r1 + (16 * h + 4 * s + L.q) * LD + ic * V;
+        if (!(FBB_SKIP & 2)) {
+#pragma unroll
+          for (int k = 0; k <= MAXF; ++k) o.bx[k] = w[pos_of(k)];
+        }
+#pragma unroll
+        for (int k = 0; k < MAXJ; ++k) {
+          const int v = k + 1 < MAXJ || wave == 0 ? wave + 4 * k : V - 1;   // (joint 16 is wave 0's: the others read, and drop, it)
+          o.a[k] = w[ic * V + v];
+          o.bb[k] = y[v];
+        }
+      };
+      constexpr int DTS = bpc_occ(CT, NS) == 2 ? 2 : 1;   // (three waves per SIMD: 168 registers have no room for a second set)
+      DtOps dto[DTS];
+      restore_dt();
 #pragma unroll
       for (int h = 0; h < ((FBB_SKIP & 16) ? 0 : CT); ++h) {
 #pragma unroll
@@ -461,28 +526,34 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
         for (int s = 0; s < 4; ++s)                      // Kr rows
           wk[s] = TLDS ? krl[((4 * h + s) * CT + ct) * 64 + 16 * L.q + L.j] : buf_load1(cres, lq, ((DX0 / CiP + Co + 16 * h + 4 * s) * CiP) * 4);
         __syncthreads();
+        dt_reads(dto[0], h, 0);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          if (!(FBB_SKIP & 2)) {                         // + Kr.X: the staged half IS the second pass's last group
-            float bx[MAXF + 1];
-#pragma unroll
-            for (int k = 0; k <= MAXF; ++k) bx[k] = r2[(4 * s + L.q) * LDW + pos_of(k)];
-#pragma unroll
-            for (int k = 0; k <= MAXF; ++k)
-              if (k < MAXF || owns16) xr[k] = mfma(wk[s], bx[k], xr[k]);
-          }
+          DtOps& o = dto[s % DTS];
 #pragma unroll
           for (int k = 0; k < MAXJ; ++k) {
-            const int v = wave + 4 * k;
-            if (v < V) {
-              const float a = r2[(4 * s + L.q) * LDW + ic * V + v];
-              const float bb = r1[(16 * h + 4 * s + L.q) * LD + ic * V + v];
-              dTacc[k] = mfma(L.j < T ? a : 0.f, L.j < T ? bb : 0.f, dTacc[k]);
-            }
+            o.a[k] = tj ? o.a[k] : 0.f;
+            o.bb[k] = tj ? o.bb[k] : 0.f;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (DTS == 2 && s + 1 < 4) dt_reads(dto[(s + 1) % DTS], h, s + 1);
+          __builtin_amdgcn_sched_barrier(0);
+          if (!(FBB_SKIP & 2)) {                         // + Kr.X: the staged half IS the second pass's last group
+#pragma unroll
+            for (int k = 0; k <= MAXF; ++k)
+              if (k < MAXF || owns16) xr[k] = mfma(wk[s], o.bx[k], xr[k]);
+          }
+#pragma unroll
+          for (int k = 0; k < MAXJ; ++k)
+            if (k + 1 < MAXJ || wave == 0) dTacc[k] = mfma(o.a[k], o.bb[k], dTacc[k]);
+          if (DTS == 1 && s + 1 < 4) {                   // one set: the next batch behind this step's products
+            __builtin_amdgcn_sched_barrier(0);
+            dt_reads(dto[0], h, s + 1);
           }
         }
         __syncthreads();                                 // the window is rewritten next
       }
+      park_dt();
     }
     float4 u[XL];
     {
@@ -541,6 +612,54 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
         }
       }
       xload(xs, xn);
+      // (NS) the products of one operand group of the layer below: acc[c] += dU_prev (image, `pa`) x group^T (window, `pb`) over this
+      // wave's k-steps m = wave, wave + 4, ..  The operands of step m + 4 are read in front of step m's products and masked once
+      // they have landed; at CT == 2 the products go c0.x, c1.x, c0.y, c1.y, so that the two dependent ones of an accumulator are
+      // an independent product apart; at CT == 1 the next reads sit between the pair.  The order within an accumulator stays.
+      auto chain_products = [&](const float* pa, const float* pb, f32x4 (&acc)[CT], bool rowsum, bool bok) {
+        constexpr int NM = (TV + 7) / 8;
+        auto land = [&](int m, float2& b, float2 (&a)[CT]) {
+          const bool aok = 8 * m + 2 * L.q < TV, ok = aok && bok;
+          b.x = ok ? b.x : 0.f; b.y = ok ? b.y : 0.f;
+#pragma unroll
+          for (int c = 0; c < CT; ++c) { a[c].x = aok ? a[c].x : 0.f; a[c].y = aok ? a[c].y : 0.f; }
+        };
+        auto reads = [&](int m, float2& b, float2 (&a)[CT]) {
+          b = *reinterpret_cast<const float2*>(pb + 8 * m);
+#pragma unroll
+          for (int c = 0; c < CT; ++c) a[c] = *reinterpret_cast<const float2*>(pa + 16 * c * LD + 8 * m);
+        };
+        float2 b, a[CT], bn, an[CT];
+        reads(wave, b, a);
+        land(wave, b, a);
+        for (int m = wave; m < NM; m += 4) {
+          const int mn = m + 4 < NM ? m + 4 : m;         // (the last step reads its own operands again: nobody uses them)
+          if constexpr (CT == 2) {
+            __builtin_amdgcn_sched_barrier(0);
+            reads(mn, bn, an);
+            __builtin_amdgcn_sched_barrier(0);
+            acc[0] = mfma(a[0].x, b.x, acc[0]);
+            acc[CT - 1] = mfma(a[CT - 1].x, b.x, acc[CT - 1]);
+            acc[0] = mfma(a[0].y, b.y, acc[0]);
+            acc[CT - 1] = mfma(a[CT - 1].y, b.y, acc[CT - 1]);
+          } else {
+            acc[0] = mfma(a[0].x, b.x, acc[0]);
+            __builtin_amdgcn_sched_barrier(0);
+            reads(mn, bn, an);
+            __builtin_amdgcn_sched_barrier(0);
+            acc[0] = mfma(a[0].y, b.y, acc[0]);
+          }
+          if (rowsum) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) nss[c] += a[c].x + a[c].y;
+          }
+          __builtin_amdgcn_sched_barrier(0);             // (the masks wait for the batch: behind the products, not among them)
+          land(mn, bn, an);
+          b = bn;
+#pragma unroll
+          for (int c = 0; c < CT; ++c) a[c] = an[c];
+        }
+      };
       if constexpr (NS == 1) {
         // ---- the layer below (two input channels): [P | Q] += dU_prev (image rows) x (Z0 Z1 X0 X1)^T (window rows 0..3) ----------
         {
@@ -557,20 +676,7 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
         L = geo();
         const float* pb = r2 + (L.j & 3) * LD + 2 * L.q;
         const float* pa = r1 + L.j * LD + 2 * L.q;
-        constexpr int NM = (TV + 7) / 8;
-        for (int m = wave; m < NM; m += 4) {
-          float2 b = *reinterpret_cast<const float2*>(pb + 8 * m);
-          const bool aok = 8 * m + 2 * L.q < TV, ok = aok && L.j < 4;
-          b.x = ok ? b.x : 0.f; b.y = ok ? b.y : 0.f;
-#pragma unroll
-          for (int c = 0; c < CT; ++c) {
-            float2 a = *reinterpret_cast<const float2*>(pa + 16 * c * LD + 8 * m);
-            a.x = aok ? a.x : 0.f; a.y = aok ? a.y : 0.f;
-            nsb[0][c] = mfma(a.x, b.x, nsb[0][c]);
-            nsb[0][c] = mfma(a.y, b.y, nsb[0][c]);
-            nss[c] += a.x + a.y;
-          }
-        }
+        chain_products(pa, pb, nsb[0], true, L.j < 4);
 #pragma unroll
         for (int q = 0; q < 4; ++q) gq[q] = qload(dun, 0, q);   // (the group registers were not used: the next clip's first dU group)
       }
@@ -578,7 +684,7 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
         // ---- the layer below: [P | Q] += dU_prev (image rows) x group^T (16 window rows at stride LD), k-steps dealt to the waves ----
         auto bres = [&](int g) { return g < CB ? clip_res(below_z, clip, 16 * CB) : clip_res(below_x, clip, 16 * CB); };
         auto brow = [&](int g) { return 16 * (g < CB ? g : g - CB); };
-        constexpr int NM = (TV + 7) / 8;
+        restore_ns();
 #pragma unroll
         for (int g = 0; g < NGB; ++g) {
           __syncthreads();                               // the row pass's image writes / the previous group's window reads are done
@@ -591,25 +697,16 @@ __global__ __launch_bounds__(256, bpc_occ(CT, NS)) void k_layer_bwd_bpc(const fl
           L = geo();
           const float* pb = r2 + L.j * LD + 2 * L.q;
           const float* pa = r1 + L.j * LD + 2 * L.q;
-          for (int m = wave; m < NM; m += 4) {
-            float2 b = *reinterpret_cast<const float2*>(pb + 8 * m);
-            const bool ok = 8 * m + 2 * L.q < TV;
-            b.x = ok ? b.x : 0.f; b.y = ok ? b.y : 0.f;
-#pragma unroll
-            for (int c = 0; c < CT; ++c) {
-              float2 a = *reinterpret_cast<const float2*>(pa + 16 * c * LD + 8 * m);
-              a.x = ok ? a.x : 0.f; a.y = ok ? a.y : 0.f;
-              nsb[g][c] = mfma(a.x, b.x, nsb[g][c]);
-              nsb[g][c] = mfma(a.y, b.y, nsb[g][c]);
-              if (g == 0) nss[c] += a.x + a.y;
-            }
-          }
+          chain_products(pa, pb, nsb[g], g == 0, true);
         }
+        park_ns();
       }
     }
   }
 
   // ---- the workgroup's sums: the waves add theirs into ONE lane-major row in LDS one after another (fixed order), then it leaves ----
+  restore_dt();
+  restore_ns();
   __syncthreads();
   float4* row4 = reinterpret_cast<float4*>(lds);         // PR_N records x 64 lanes (32 KB) over the image and the window
   for (int e = tid; e < PR_N * 64; e += 256) row4[e] = float4{0.f, 0.f, 0.f, 0.f};
@@ -691,7 +788,7 @@ int launch_layer_bwd_bpc(const float* in, const float* Zg, const float* dU, cons
 #define LAUNCH_FBB(CT, OT, NS, CB)                                                                                   \
   do {                                                                                                               \
     rc = launch_lds<fb::k_layer_bwd_bpc<CT, OT, NS, CB>>("bwd_bpc", dim3(grid), dim3(256),                          \
-                                                         fb::bpc_lds_floats(CT, OT, NS) * sizeof(float), st, in, Zg, dU, coef,  \
+                                                         fb::bpc_lds_floats(CT, OT, NS, CB) * sizeof(float), st, in, Zg, dU, coef,  \
                                                          (const float*)btab, in_slope, dIn, partials, dap, B, below_z,      \
                                                          below_x, below_slope, below_stats);                                \
   } while (0)
