@@ -74,10 +74,9 @@ constexpr int kDzStr = 20;       // row stride of the dz image: = 4 (mod 16), cl
 constexpr int kMaxKS = 8;        // split-K slices the HD form takes
 
 __device__ __forceinline__ void head_ride_block(const HeadRide& hr, int B, int L) {
-  float vals[kHeadSlots];
-#pragma unroll
-  for (int k = 0; k < kHeadSlots; ++k) vals[k] = 0.f;
-  const Vec c = load_vec(hr.c, L);
+  using Vec = Row<PerThread>;
+  HeadSums<PerThread> sums;
+  const Vec c = load<PerThread>(hr.c, L);
   const int bid = (int)blockIdx.x - hr.nbwd;
   const int n = bid * kFlatBlock + (int)threadIdx.x;
   if (n < B) {
@@ -92,12 +91,12 @@ __device__ __forceinline__ void head_ride_block(const HeadRide& hr, int B, int L
       }
       u.v[j] = z;
     }
-    store_vec(hr.z + (size_t)n * L, u, L);
-    const float sq = mse_head_row(u, c, L, hr.gscale, vals, g);
-    store_vec(hr.dz + (size_t)n * L, g, L);
+    store(hr.z + (size_t)n * L, u, L);
+    const float sq = mse_head_row(u, c, hr.gscale, sums, g);
+    store(hr.dz + (size_t)n * L, g, L);
     if (hr.score) hr.score[n] = sq / (float)L;
   }
-  block_partials(vals, hr.hpart, hr.scale0, hr.stats, hr.acc, bid, hr.nhead);
+  flush(sums, HeadOut{hr.hpart, hr.scale0, hr.stats, hr.acc}, L, bid, hr.nhead);
 }
 
 template <int CT, bool HD>

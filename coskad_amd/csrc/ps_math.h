@@ -1,4 +1,4 @@
-// Scalar special functions of the PowerSpherical head (csrc/vae_head.hip at latent <= 16, csrc/vae_head_wide.hip above):
+// Scalar special functions of the latent heads of the VAEs (csrc/vae_head.hip, csrc/vae_head_normal.hip):
 // digamma / trigamma by recurrence + asymptotic series in fp64, F.softplus, and the entropy constants.
 #pragma once
 #include "common.h"
@@ -22,17 +22,5 @@ __device__ __forceinline__ double trigamma_d(double x) {      // x > 0
 }
 __device__ __forceinline__ float softplus_f(float v) { return v > 20.f ? v : log1pf(expf(v)); }   // F.softplus(beta = 1, threshold = 20)
 
-constexpr int kWideLMax = 512;      // widest latent of the head (vae_head_wide.hip)
-
 }  // namespace vh
-
-// vae_head_wide.hip (16 < L <= vh::kWideLMax): the launches behind coskad_ps_head_{prep,sample,bwd}_f32, arguments as there
-int wide_ps_head_prep(const float* mean_raw, int ld_mean, const float* var_raw, int ld_var, float* mu, float* kappa, float* concentration,
-                      float* total, int B, int L, hipStream_t stream);
-int wide_ps_head_sample(const float* x, const float* eps, const float* mu, const float* kappa, float* z, float* kl, float* inv_kappa, int B,
-                        int L, hipStream_t stream);
-int wide_ps_head_bwd(const float* dz, const float* x, const float* dirichlet_grad, const float* eps, const float* mu, const float* kappa,
-                     const float* mean_raw, int ld_mean, const float* var_raw, int ld_var, float w_kl, float w_exp, float* d_mean_raw,
-                     int ld_dmean, float* d_var_raw, int ld_dvar, int B, int L, hipStream_t stream);
-
 }  // namespace coskad

@@ -15,13 +15,12 @@
 // -- the SAME element-to-lane map either way, so a row sum (the lane's eight terms in (c, k) order, then wave_sum) is formed in an
 // order that depends on L alone: not on B, the grid, the wave that takes the clip or the operands' alignment.  Pad lanes (l >= L)
 // and clips beyond B hold exact zeros in every sum and store nothing.  Grid-stride over waves' clip groups; no atomics, no LDS.
-#include "common.h"
+#include "latent_row.h"
 #include "ps_math.h"
 
 namespace coskad {
 namespace vhn {
 
-using vh::kWideLMax;
 using vh::softplus_f;
 constexpr int kWaves = 4;              // waves per block
 constexpr float kCosEps = 1e-8f;       // F.cosine_similarity's default eps: each norm is clamped from below on its own
@@ -220,13 +219,13 @@ using namespace coskad;
 
 extern "C" {
 
-int coskad_normal_head_ok(int L) { return (L >= 1 && L <= vhn::kWideLMax) ? 1 : 0; }
+int coskad_normal_head_ok(int L) { return (L >= 1 && L <= kWideLMax) ? 1 : 0; }
 
 int coskad_normal_head_fwd_f32(const float* mean_raw, int ld_mean, const float* var_raw, int ld_var, const float* eps, float* z,
                                float* sigma, float* kl, float* inv, const float* ref, float* score, int B, int L,
                                hipStream_t stream) {
   if (!mean_raw || !var_raw || !eps) return fail(COSKAD_ERR_ARG, "normal_head_fwd: null pointer (mean_raw / var_raw / eps)");
-  if (!coskad_normal_head_ok(L)) return fail(COSKAD_ERR_SHAPE, "normal_head_fwd: latent=%d outside 1..%d", L, vhn::kWideLMax);
+  if (!coskad_normal_head_ok(L)) return fail(COSKAD_ERR_SHAPE, "normal_head_fwd: latent=%d outside 1..%d", L, kWideLMax);
   if (B == 0) return fail(COSKAD_ERR_SHAPE, "normal_head_fwd: B=%d latent=%d", B, L);      // as the ps_head entries
   if (B < 0) return fail(COSKAD_ERR_ARG, "normal_head_fwd: B=%d", B);
   if (ld_mean < L) return fail(COSKAD_ERR_ARG, "normal_head_fwd: ld_mean=%d < latent=%d", ld_mean, L);
@@ -245,7 +244,7 @@ int coskad_normal_head_bwd_f32(const float* dz, const float* eps, const float* s
                                float* d_var_raw, int ld_dvar, int B, int L, hipStream_t stream) {
   if (!dz || !eps || !sigma || !mean_raw || !var_raw || !d_mean_raw || !d_var_raw)
     return fail(COSKAD_ERR_ARG, "normal_head_bwd: null pointer");
-  if (!coskad_normal_head_ok(L)) return fail(COSKAD_ERR_SHAPE, "normal_head_bwd: latent=%d outside 1..%d", L, vhn::kWideLMax);
+  if (!coskad_normal_head_ok(L)) return fail(COSKAD_ERR_SHAPE, "normal_head_bwd: latent=%d outside 1..%d", L, kWideLMax);
   if (B == 0) return fail(COSKAD_ERR_SHAPE, "normal_head_bwd: B=%d latent=%d", B, L);
   if (B < 0) return fail(COSKAD_ERR_ARG, "normal_head_bwd: B=%d", B);
   if (ld_mean < L) return fail(COSKAD_ERR_ARG, "normal_head_bwd: ld_mean=%d < latent=%d", ld_mean, L);

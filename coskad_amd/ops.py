@@ -653,7 +653,7 @@ def btlnk_fwd(U: Tensor, W: Tensor, bias: Optional[Tensor], slope: Optional[Tens
 
 
 BTLNK_SPLITK_MIN_B = 1      # always (K % 16 == 0): a clip's latent must not depend on the batch it arrives in (bit-exact chunking)
-BTLNK_LMAX = 512            # widest latent of the bottleneck and head kernels (csrc/btlnk_wide.hip, csrc/heads_wide.hip)
+BTLNK_LMAX = 512            # widest latent of the bottleneck and head kernels (csrc/btlnk_wide.hip, csrc/heads.hip)
 
 
 def btlnk_bwd_ws_bytes(B, K, L) -> int:
@@ -1335,11 +1335,11 @@ def _rows(t: Tensor, name: str, cols: int):
     return t.stride(0)
 
 
-PS_HEAD_LMAX = 512          # widest latent of the PowerSpherical head (csrc/vae_head.hip to 16, csrc/vae_head_wide.hip above)
+PS_HEAD_LMAX = 512          # widest latent of the PowerSpherical head (csrc/vae_head.hip: a thread per clip to 16, a wave above)
 
 
 def ps_head_forward(mean_raw: Tensor, var_raw: Tensor, generator=None):
-    """The spherical VAE's latent head on csrc/vae_head.hip / vae_head_wide.hip (2 <= L <= PS_HEAD_LMAX; reference models/sts/vae.py:79-91,104-118; PowerSpherical restated in
+    """The spherical VAE's latent head on csrc/vae_head.hip (2 <= L <= PS_HEAD_LMAX; reference models/sts/vae.py:79-91,104-118; PowerSpherical restated in
     coskad_amd/models/sts/vae.py): mean_raw [B, L], var_raw [B, 1] (views of one tensor are fine) -> (z [B, L] sampled latent,
     kl [B], inv_kappa [B], saved) with saved = what ps_head_backward needs.  The Beta draw and the Gaussian direction are torch's
     (torch._sample_dirichlet, torch.randn): the noise streams are the module path's."""

@@ -976,7 +976,7 @@ class _CentreLatent(_LatentHead):
 
 
 class _PowerSphericalLatent(_LatentHead):
-    """The PowerSpherical head on csrc/vae_head.hip / vae_head_wide.hip (normalise, softplus + 1, Householder sample, KL, 1 / kappa: three launches +
+    """The PowerSpherical head on csrc/vae_head.hip (normalise, softplus + 1, Householder sample, KL, 1 / kappa: three launches +
     torch's Beta draw instead of ~80 element-wise launches under autograd); the two small Linears of the `mlp` projector's heads ride
     on the strided GEMM with the weights stacked"""
 
@@ -1151,7 +1151,7 @@ class STSAETrainStep(_FlatStep):
 
     @staticmethod
     def supports(model) -> bool:
-        """the stages take the model: latents up to 512 -- above 16 on csrc/btlnk_wide.hip, vae_head_wide.hip and rev_btlnk_wide.hip
+        """the stages take the model: latents up to 512 -- above 16 on csrc/btlnk_wide.hip, vae_head.hip's wave-per-clip kernels and rev_btlnk_wide.hip
         (the decoder entry is then _PlainEntry), unless a measurement switched that latent off (ops.AE_WIDE_OFF)"""
         from .models.sts.vae import STSVAE
         from .models.common.components import MLP
@@ -1341,7 +1341,7 @@ def make_decoder_step(model, mode: str, fused_window: bool = True, wide_latent: 
     yamls): at window length 8 / 16 / 24 the flat step takes the model when the stored-Z layer kernels serve EVERY layer of both stacks
     (no `wide` segment: such a stack -- 8-channel layers, a joint layout without window kernels -- stays on the autograd route, as
     does every model with `fused_window` off).  `wide_latent` (the wrappers ask for it; their yaml key `flat_wide_latent`): a latent
-    beyond 16 that `supports` admits takes the flat step too (csrc/vae_head_wide.hip, rev_btlnk_wide.hip); off: the autograd route.
+    beyond 16 that `supports` admits takes the flat step too (csrc/vae_head.hip, rev_btlnk_wide.hip); off: the autograd route.
     `gaussian_head` (the wrappers ask for it; their yaml key `flat_gaussian_head`): the step of a `distribution: 'normal'` VAE runs its
     latent head on csrc/vae_head_normal.hip; off: that head stays under its local autograd graph."""
     from .models.common.components import Encoder

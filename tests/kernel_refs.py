@@ -167,12 +167,12 @@ def gather_transform_f32(xy, mats, index, N, ntrans):
     return out
 
 
-# ---- the one-class heads (csrc/heads.hip: L <= 16, one thread per clip; csrc/heads_wide.hip: 16 < L <= 512, one wave per clip) ---------
+# ---- the one-class heads (csrc/heads.hip over the maps of latent_row.h: L <= 16 one thread per clip, 16 < L <= 512 one wave per clip) --
 
-HEAD_LMAX = 16            # heads_common.h LMAX: latents up to here run one thread per clip
+HEAD_LMAX = 16            # latent_row.h LMAX: latents up to here run one thread per clip
 HEAD_ROWS = 512           # kFlatBlock: clips per block of the narrow heads; one block writes stats / acc itself
-WIDE_TILE = 16            # hw::kTileRows: clips per block of the wide heads (4 waves)
-WIDE_MAX_BLOCKS = 1024    # hw::kMaxBlocks
+WIDE_TILE = 16            # kWideTileRows (heads_common.h): clips per block of the wide heads (4 waves)
+WIDE_MAX_BLOCKS = 1024    # kWideMaxBlocks
 
 # Largest error of the device's tanhf / log1pf in ulps of the float32 result.  Neither can be derived from the kernels' text; both were
 # measured once on an MI355X (torch's float32 tanh / log1p on the device against float64 over the argument ranges of
@@ -373,8 +373,8 @@ class EVMath:
         return EV(torch.where(cond, a.v, b.v + torch.zeros_like(a.v)), torch.where(cond, a.e, b.e + torch.zeros_like(a.e)))
 
     def dot(self, a, b, wide):
-        """[.., L] x [.., L] -> [.., 1] in the kernel's order: dot() of heads_common.h (one fmaf chain) or wdot() of heads_wide.hip
-        (lane l: a chain over j = l + 64 v, then wave_sum).  Every partial sum is rounded once."""
+        """[.., L] x [.., L] -> [.., 1] in the kernel's order: dot() of latent_row.h, one fmaf chain (PerThread) or, wide, lane l's chain over
+        j = l + 64 i, then wave_sum (PerWave).  Every partial sum is rounded once."""
         t = a.v * b.v
         prop = (a.v.abs() * b.e + b.v.abs() * a.e + a.e * b.e).sum(-1, keepdim=True)
         L = t.shape[-1]
@@ -508,7 +508,7 @@ def _f32sub(a, b):
 
 
 def hyp_embed(A, u, wide):
-    """heads.hip hyp_embed / heads_wide.hip hw::hyp_embed: p = project(expmap0(u)) and what the backward keeps"""
+    """heads.hip hyp_embed<M>: p = project(expmap0(u)) and what the backward keeps"""
     kmin = A.const(1e-5)
     un_raw = A.dot(u, u, wide).sqrt()
     un = un_raw.maximum(kmin)
@@ -567,7 +567,7 @@ def hyp_embed_bwd(A, u, em, gp, wide):
 
 
 def poincare_head_chain(A, z, c, wide, gscale=None):
-    """one clip of k_poincare_head / hw::k_poincare_wide on float32 z [B, L], c [L] or None: zh, the slot terms gamma zh, gamma - 1,
+    """one clip of k_poincare_head<M> on float32 z [B, L], c [L] or None: zh, the slot terms gamma zh, gamma - 1,
     |zh|, and with a centre the distance and dz = hyp_embed_bwd(gscale dd/dp) (gscale: (exact, as the kernel's float32 holds it))"""
     u = A.inp(z)
     em = hyp_embed(A, u, wide)

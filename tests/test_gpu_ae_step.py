@@ -234,6 +234,36 @@ def test_power_spherical_head_kernels_vs_torch_autograd(L):
     np.testing.assert_allclose(got[ok], ref[ok], rtol=2e-3, atol=2e-6 + 2e-4 * np.abs(ref[ok]).max())
 
 
+@pytest.mark.parametrize("L", [2, 16])
+def test_power_spherical_head_repeats_bit_for_bit(L):
+    """The thread-per-clip head (L <= 16) gives what the wave-per-clip one is held to in test_gpu_ae_wide_latent.py: the same seed
+    again draws the same noise and repeats z, kl, 1 / kappa and the gradient bit for bit.  B = 131 leaves the one block ragged; the
+    gradient goes into column views between sentinel guard columns; rows 0 / 1 sit on the poles."""
+    from coskad_amd import ops
+    SENT = -777.0
+    g = torch.Generator().manual_seed(5 + L)
+    B = 131
+    H2 = torch.randn(B, L + 1, generator=g)
+    H2[:, L] = torch.linspace(-6, 25, B)
+    H2[0, :L] = 0.0; H2[0, 0] = 3.0                       # mu = e1
+    H2[1, :L] = 0.0; H2[1, 0] = -2.0                      # mu = -e1
+    H2d, wd = H2.cuda(), torch.randn(B, L, generator=g).cuda()
+    w_kl, w_exp = 0.3 / B, 0.2 / B
+    runs = []
+    for _ in range(2):
+        torch.manual_seed(40 + L)
+        z, kl, ik, saved = ops.ps_head_forward(H2d[:, :L], H2d[:, L:L + 1])
+        out = torch.full((B, L + 3), SENT, device="cuda")  # guard columns 0 and L + 2 around the [B, L + 1] gradient
+        ops.ps_head_backward(saved, wd, w_kl, w_exp, out[:, 1:L + 1], out[:, L + 1:L + 2])
+        assert bool((out[:, 0] == SENT).all()) and bool((out[:, L + 2] == SENT).all())
+        assert bool((out[:, 1:L + 2] != SENT).all())      # every gradient element was written
+        runs.append((saved[6], saved[7], z, kl, ik, out))
+    a, b = runs
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])            # the same draws
+    for p, q in zip(a[2:], b[2:]):                                        # (bit patterns: the pole row may hold a NaN)
+        assert torch.equal(p.contiguous().view(torch.int32), q.contiguous().view(torch.int32))
+
+
 @pytest.mark.parametrize("variant", ["kernel", "explicit", "autograd", "graph"])
 @pytest.mark.parametrize("name", ["stsae_small.npz", "stsae_v25.npz"])
 def test_folded_first_decoder_layer_equals_the_layer_by_layer_path(golden, name, variant, monkeypatch):

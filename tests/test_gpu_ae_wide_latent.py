@@ -1,5 +1,5 @@
 """The decoder models (autoencoder, spherical VAE) at latents 17 .. 512 on the flat HIP step: the wide PowerSpherical head
-(csrc/vae_head_wide.hip) against the float64 restatement, the three MFMA products of rev_btlnk (csrc/rev_btlnk_wide.hip) against
+(csrc/vae_head.hip, one wave per clip) against the float64 restatement, the three MFMA products of rev_btlnk (csrc/rev_btlnk_wide.hip) against
 float64, the steps against the module surface, scoring, and the wrappers."""
 from argparse import Namespace
 
@@ -288,7 +288,7 @@ def test_flat_vae_step_wide_latent_matches_module_autograd(V, projector, L, B):
 
 # ---- e. scoring --------------------------------------------------------------------------------------------------------------------------
 def test_vae_eval_forward_head_on_hip_at_latent_32_equals_the_torch_head(monkeypatch):
-    """STSVAE.forward in eval mode without autograd takes the head kernels at latent 32 too (csrc/vae_head_wide.hip); with autograd
+    """STSVAE.forward in eval mode without autograd takes the head kernels at latent 32 too (csrc/vae_head.hip); with autograd
     enabled the same call runs the torch restatement: same seed -> same sample, reconstruction and concentration."""
     from coskad_amd import ops
     from coskad_amd.models.sts.vae import STSVAE

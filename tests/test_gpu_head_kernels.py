@@ -1,5 +1,5 @@
-"""Kernel-level checks of the one-class heads and their centres: csrc/heads.hip (L <= 16, one thread per clip) and csrc/heads_wide.hip
-(16 < L <= 512, one wave per clip), called directly with guard bands around every output.  The value compared with is always
+"""Kernel-level checks of the one-class heads and their centres: csrc/heads.hip (L <= 16, one thread per clip; 16 < L <= 512, one wave
+per clip) and the MFMA Mahalanobis head and Gram of csrc/heads_wide.hip, called directly with guard bands around every output.  The value compared with is always
 oracle/ref_cpu.py evaluated in double on the float32 inputs, gradients from autograd on that forward.  Bounds: for the Euclidean and
 Mahalanobis heads, the Gram matrix, sqnorm and the finalizers k * U32 * M derived by hand in the docstrings (plus (count + 8) * U64 * M
 where the kernel sums in double); for the Poincare chain the running-error arithmetic of kernel_refs.py, which restates the kernels'
@@ -119,7 +119,7 @@ def _assert_margins(A, tag):
 
 @pytest.mark.parametrize("L,B", SHAPES)
 def test_poincare_head(L, B):
-    """k_poincare_head / hw::k_poincare_wide at the four centres |c| in {0, 0.4, 0.93, 0.995} and without a centre.
+    """k_poincare_head<PerThread> / <PerWave> at the four centres |c| in {0, 0.4, 0.93, 0.995} and without a centre.
 
     zh, score and dz per element against the oracle within the running-error bound of kernel_refs.poincare_head_chain (dz for
     upstream in {1, 0.37, B}; the other outputs do not depend on upstream: bit-equal).  Slot sums: a clip's term t_n carries its chain
@@ -228,7 +228,7 @@ def _euclid_sums(z, ks, P, L, S):
 
 @pytest.mark.parametrize("L,B", SHAPES)
 def test_mse_head(L, B):
-    """k_mse_head / hw::k_mse_wide.  d = u - c rounds once; sq = sum d^2 is an fmaf chain (kd = dot_roundings(L) roundings: L fmaf, or
+    """k_mse_head<PerThread> / <PerWave>.  d = u - c rounds once; sq = sum d^2 is an fmaf chain (kd = dot_roundings(L) roundings: L fmaf, or
     the lane's ceil(L / 64) and wave_sum's 6) of terms that carry d's rounding twice: err(sq) <= (kd + 2) U32 sq.
     score = sq / (float)L: (kd + 3) U32 score.
     dz = 2 d gscale, gscale = upstream / ((float)B (float)L): the product B L, the division, d and the product round (2 d is exact):

@@ -1,4 +1,4 @@
-"""Latents wider than 16 (16 < L <= 512) on the HIP path: the wide one-class heads (csrc/heads_wide.hip), the wide bottleneck
+"""Latents wider than 16 (16 < L <= 512) on the HIP path: the wide one-class heads (csrc/heads.hip, heads_wide.hip), the wide bottleneck
 (csrc/btlnk_wide.hip), the flat train step, the Lightning-style wrappers, the CLI and two gloo ranks -- against the oracle
 formulas (oracle/ref_cpu.py) with fp64 autograd for the gradients."""
 import os

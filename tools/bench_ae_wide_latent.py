@@ -11,7 +11,7 @@ more than 3 % faster than the parent's (twice the +-1.5 % box-to-box spread); ot
 Kernel rows (this tree, one process, the two sides alternating per block): rev_btlnk's forward and its backward (dz and dW / db share
 one entry point and are timed together) on csrc/rev_btlnk_wide.hip against the ops fallback they replace (the strided GEMM + cat +
 copies), with the roof max(2 B N L / 157.3 TF, bytes / 8 TB/s) per product; and the three launches of the PowerSpherical head at
-L = 16 (csrc/vae_head.hip) against L in {32, 512} (csrc/vae_head_wide.hip), for the record.
+L = 16 (csrc/vae_head.hip, a thread per clip) against L in {32, 512} (a wave per clip), for the record.
 
 Every child runs under a time limit; the first failure ends the run.  Warm-up first, then the median of >= 3 timed blocks x 5 steps
 (HIP events; every block printed).
@@ -151,7 +151,7 @@ def bench_ps_head(L, B, warmup, blocks, steps):
         ops.call("coskad_ps_head_sample_f32", x, eps, mu, kappa, zs, kl, ik, B, L, st)
         ops.call("coskad_ps_head_bwd_f32", dz, x, gr, eps, mu, kappa, mean_raw, L + 1, var_raw, L + 1, 0.3 / B, 0.2 / B, dH2[:, :L],
                  L + 1, dH2[:, L:L + 1], L + 1, B, L, st)
-    return dict({"what": "ps_head", "L": L, "B": B, "kernels": "vae_head.hip" if L <= 16 else "vae_head_wide.hip"},
+    return dict({"what": "ps_head", "L": L, "B": B, "kernels": "vae_head.hip PerThread" if L <= 16 else "vae_head.hip PerWave"},
                 **_row(_time_blocks(three, warmup, blocks, steps)))
 
 
