@@ -4,6 +4,9 @@
 // where the track has a full window, writes the window's K affine copies with the expression of k_gather_frames (data.hip).  After the
 // model has scored those windows, k_stream_frames keeps the scores in a ring per track and finalises the one row that no later window
 // can cover, by the rules of k_score_person_frames (score_frames.hip).  k_stream_close finalises a closed track's trailing rows.
+// For many cameras per tick (StreamBank) k_stream_push_cams is the push kernel with the video resolution per detection, and
+// k_stream_smooth hands out the shifted, Gaussian-smoothed clip scores of a flat clip buffer (one segment per camera) item by item, with
+// k_score_smooth's arithmetic.
 //
 // Device state, capacity M tracks, R = (T - 1) step + 1 rows between a window's first and last row:
 //   ring   [M, R, 2, V] f32 : row r of a track at slot r % R
@@ -21,6 +24,10 @@ constexpr int kStreamWave = 64;
 constexpr int kStreamKp = 17;                  // joints of a raw row (x1, y1, ..., x17, y17)
 constexpr int kStreamBlock = 256;
 enum { kStreamKp18 = 1, kStreamHeadless = 2, kStreamNormalised = 4 };
+constexpr int kStreamRadius = 120;             // the smoothing filter of score_frames.hip: gaussian_filter1d(sigma 30), truncate 4
+constexpr int kStreamTaps = kStreamRadius + 1;
+constexpr int kStreamShift = 11;               // score_process's shift
+constexpr int kStreamSmoothChunk = 8;          // transformations summed side by side per pass of k_stream_smooth
 
 __host__ __device__ inline bool stream_window_ok(int T) { return T == 8 || T == 12 || T == 16 || T == 24; }
 __host__ __device__ inline bool stream_joints_ok(int V) { return V == 14 || V == 17 || V == 18; }
@@ -50,13 +57,14 @@ __device__ __forceinline__ float robust_f32(float v, double center, double scale
   return (float)((double)y / scale);
 }
 
-// one wave = one detection; lane j < 17 owns joint j of the raw row
-__global__ __launch_bounds__(kStreamWave) void k_stream_push(const float* __restrict__ raw, const int* __restrict__ slot,
-                                                             const int* __restrict__ reset, const int* __restrict__ out_index,
-                                                             const double* __restrict__ center, const double* __restrict__ scale,
-                                                             float wmax, float hmax, int flags, const float* __restrict__ mats,
-                                                             float* __restrict__ ring, int* __restrict__ count,
-                                                             float* __restrict__ x_out, int m, int M, int K, int T, int V, int step) {
+// one wave = one detection; lane j < 17 owns joint j of the raw row.  wmax / hmax: the video's width - 1 and height - 1 of THIS detection
+// (uniform per wave), so one body serves a launch of one camera (k_stream_push) and of many (k_stream_push_cams).
+__device__ __forceinline__ void stream_push_body(const float* __restrict__ raw, const int* __restrict__ slot,
+                                                 const int* __restrict__ reset, const int* __restrict__ out_index,
+                                                 const double* __restrict__ center, const double* __restrict__ scale, float wmax,
+                                                 float hmax, int flags, const float* __restrict__ mats, float* __restrict__ ring,
+                                                 int* __restrict__ count, float* __restrict__ x_out, int m, int M, int K, int T, int V,
+                                                 int step) {
   const int d = blockIdx.x, lane = threadIdx.x;
   const int sl = slot[d];
   if ((unsigned)sl >= (unsigned)M) return;             // uniform per wave: never a store outside the state
@@ -134,6 +142,27 @@ __global__ __launch_bounds__(kStreamWave) void k_stream_push(const float* __rest
   }
 }
 
+__global__ __launch_bounds__(kStreamWave) void k_stream_push(const float* __restrict__ raw, const int* __restrict__ slot,
+                                                             const int* __restrict__ reset, const int* __restrict__ out_index,
+                                                             const double* __restrict__ center, const double* __restrict__ scale,
+                                                             float wmax, float hmax, int flags, const float* __restrict__ mats,
+                                                             float* __restrict__ ring, int* __restrict__ count,
+                                                             float* __restrict__ x_out, int m, int M, int K, int T, int V, int step) {
+  stream_push_body(raw, slot, reset, out_index, center, scale, wmax, hmax, flags, mats, ring, count, x_out, m, M, K, T, V, step);
+}
+
+// the detections of many cameras in one launch: res [n, 2] = (width, height) of each detection's video
+__global__ __launch_bounds__(kStreamWave) void k_stream_push_cams(const float* __restrict__ raw, const int* __restrict__ slot,
+                                                                  const int* __restrict__ reset, const int* __restrict__ out_index,
+                                                                  const double* __restrict__ center, const double* __restrict__ scale,
+                                                                  const float* __restrict__ res, int flags,
+                                                                  const float* __restrict__ mats, float* __restrict__ ring,
+                                                                  int* __restrict__ count, float* __restrict__ x_out, int m, int M, int K,
+                                                                  int T, int V, int step) {
+  const float wmax = res[2 * (size_t)blockIdx.x] - 1.f, hmax = res[2 * (size_t)blockIdx.x + 1] - 1.f;
+  stream_push_body(raw, slot, reset, out_index, center, scale, wmax, hmax, flags, mats, ring, count, x_out, m, M, K, T, V, step);
+}
+
 // Row i of a track whose last window ends at row `last`: the mean over the windows that end at i + (R - 1) - t step, t < T, inside
 // [R - 1, last], by ascending window start (t descending); exactly-zero scores are missing, 0 when none is left (k_score_person_frames)
 __device__ __forceinline__ double stream_row_mean(const double* __restrict__ ws, int i, int last, int R, int T, int step) {
@@ -201,6 +230,55 @@ __global__ __launch_bounds__(kStreamBlock) void k_stream_close(const int* __rest
   frame_mean[id] = mean;
 }
 
+// Fixed-lag smoothing of the clip vectors.  The flat buffer clip [K, F] holds one segment per camera; an item
+// (offset, n, i) asks for output i of the segment [offset, offset + n): shifted[j] = raw[j - 11] (0 below 11) under scipy's `reflect`
+// boundary of period 2n (d c b a | a b c d | d c b a; a segment shorter than the halo reflects several times).
+__device__ __forceinline__ double smooth_tap_in(const double* __restrict__ r, int n, int j) {
+  j %= 2 * n;
+  if (j < 0) j += 2 * n;
+  if (j >= n) j = 2 * n - 1 - j;
+  return j >= kStreamShift ? r[j - kStreamShift] : 0.0;
+}
+
+// One wave = one item.  The lanes form the 121 terms of a transformation -- x[i] taps[0] and (x[i - k] + x[i + k]) taps[k], each rounded
+// once, as k_score_smooth (score_frames.hip) rounds them -- into LDS; then ONE lane per transformation adds them in that kernel's order
+// (centre first, then k = 120 .. 1), and lane 0 adds the transformations in order of t and divides by K.  No atomics: the value of an
+// item depends on the item alone, and equals k_score_smooth's of the same segment bit for bit.
+__global__ __launch_bounds__(kStreamWave) void k_stream_smooth(const double* __restrict__ clip, const int* __restrict__ items,
+                                                               const double* __restrict__ taps, double* __restrict__ per_t,
+                                                               double* __restrict__ mean, int n_items, int K, int F) {
+  __shared__ double term[kStreamSmoothChunk][kStreamTaps];
+  __shared__ double sums[kStreamSmoothChunk];
+  const int q = blockIdx.x, lane = threadIdx.x;
+  const int off = items[3 * (size_t)q], n = items[3 * (size_t)q + 1], i = items[3 * (size_t)q + 2];
+  const bool ok = off >= 0 && n > 0 && off <= F - n && i >= 0 && i < n;        // uniform per wave; the launcher checked the host's copy
+  double acc_t = 0.0;
+  for (int t0 = 0; t0 < K; t0 += kStreamSmoothChunk) {
+    const int kc = K - t0 < kStreamSmoothChunk ? K - t0 : kStreamSmoothChunk;
+    if (ok) {
+      for (int e = lane; e < kc * kStreamTaps; e += kStreamWave) {
+        const int tt = e / kStreamTaps, k = e - tt * kStreamTaps;
+        const double* r = clip + (size_t)(t0 + tt) * F + off;
+        term[tt][k] = k == 0 ? smooth_tap_in(r, n, i) * taps[0] : (smooth_tap_in(r, n, i - k) + smooth_tap_in(r, n, i + k)) * taps[k];
+      }
+    }
+    __syncthreads();
+    if (lane < kc) {
+      double acc = 0.0;
+      if (ok) {
+        acc = term[lane][0];
+        for (int k = kStreamRadius; k >= 1; --k) acc += term[lane][k];
+      }
+      per_t[(size_t)(t0 + lane) * n_items + q] = acc;
+      sums[lane] = acc;
+    }
+    __syncthreads();
+    if (lane == 0)
+      for (int tt = 0; tt < kc; ++tt) acc_t += sums[tt];
+  }
+  if (lane == 0) mean[q] = ok ? acc_t / (double)K : 0.0;
+}
+
 // the host mirror of a launch's slots: every one inside [0, M); `distinct`: no slot twice (two waves would write one ring)
 static const char* bad_slots(const int* slot_host, int n, int M, bool distinct) {
   for (int i = 0; i < n; ++i)
@@ -222,22 +300,32 @@ using namespace coskad;
 extern "C" {
 
 int coskad_stream_ok(int T, int V) { return stream_window_ok(T) && stream_joints_ok(V) ? 1 : 0; }
+int coskad_stream_smooth_lag(void) { return kStreamRadius; }
+
+// the checks both push entries share; `who` names the entry in the message
+static int push_args_bad(const char* who, const float* raw, const int* slot, const int* slot_host, const int* reset,
+                         const int* out_index, const double* center, const double* scale, int flags, const float* mats,
+                         const float* ring, const int* count, const float* x_out, int n, int m, int M, int K, int T, int V, int step) {
+  if (!raw || !slot || !slot_host || !reset || !out_index || !mats || !ring || !count) return fail(COSKAD_ERR_ARG, "%s: null pointer", who);
+  if ((center == nullptr) != (scale == nullptr)) return fail(COSKAD_ERR_ARG, "%s: center and scale come together", who);
+  if (n <= 0 || m < 0 || m > n || M <= 0 || K <= 0 || step <= 0)
+    return fail(COSKAD_ERR_ARG, "%s: n=%d m=%d max_tracks=%d K=%d step=%d", who, n, m, M, K, step);
+  if (m > 0 && !x_out) return fail(COSKAD_ERR_ARG, "%s: null pointer", who);
+  if (flags < 0 || flags > 7) return fail(COSKAD_ERR_ARG, "%s: flags=%d", who, flags);
+  if (!coskad_stream_ok(T, V))
+    return fail(COSKAD_ERR_SHAPE, "%s: unsupported (n_frames=%d, n_joints=%d): windows of 8 / 12 / 16 / 24 frames, 14 / 17 / 18 joints", who,
+                T, V);
+  if (V != stream_layout_joints(flags)) return fail(COSKAD_ERR_ARG, "%s: n_joints=%d with layout flags %d", who, V, flags);
+  return 0;
+}
 
 int coskad_stream_push_f32(const float* raw, const int* slot, const int* slot_host, const int* reset, const int* out_index,
                            const double* center, const double* scale, float width, float height, int flags, const float* mats,
                            float* ring, int* count, float* x_out, int n, int m, int M, int K, int T, int V, int step,
                            hipStream_t stream) {
-  if (!raw || !slot || !slot_host || !reset || !out_index || !mats || !ring || !count)
-    return fail(COSKAD_ERR_ARG, "stream_push: null pointer");
-  if ((center == nullptr) != (scale == nullptr)) return fail(COSKAD_ERR_ARG, "stream_push: center and scale come together");
-  if (n <= 0 || m < 0 || m > n || M <= 0 || K <= 0 || step <= 0)
-    return fail(COSKAD_ERR_ARG, "stream_push: n=%d m=%d max_tracks=%d K=%d step=%d", n, m, M, K, step);
-  if (m > 0 && !x_out) return fail(COSKAD_ERR_ARG, "stream_push: null pointer");
-  if (flags < 0 || flags > 7) return fail(COSKAD_ERR_ARG, "stream_push: flags=%d", flags);
-  if (!coskad_stream_ok(T, V))
-    return fail(COSKAD_ERR_SHAPE, "stream_push: unsupported (n_frames=%d, n_joints=%d): windows of 8 / 12 / 16 / 24 frames, 14 / 17 / 18 joints",
-                T, V);
-  if (V != stream_layout_joints(flags)) return fail(COSKAD_ERR_ARG, "stream_push: n_joints=%d with layout flags %d", V, flags);
+  if (int rc = push_args_bad("stream_push", raw, slot, slot_host, reset, out_index, center, scale, flags, mats, ring, count, x_out, n, m, M,
+                             K, T, V, step))
+    return rc;
   if (!(flags & kStreamNormalised) && !(width >= 1.f && height >= 1.f))
     return fail(COSKAD_ERR_ARG, "stream_push: video resolution %g x %g", (double)width, (double)height);
   if ((long long)(T - 1) * step + 1 > 0x7fffffffLL / (2 * 18)) return fail(COSKAD_ERR_ARG, "stream_push: step=%d", step);
@@ -245,6 +333,31 @@ int coskad_stream_push_f32(const float* raw, const int* slot, const int* slot_ho
   hipLaunchKernelGGL(k_stream_push, dim3((unsigned)n), dim3(kStreamWave), 0, stream, raw, slot, reset, out_index, center, scale,
                      width - 1.f, height - 1.f, flags, mats, ring, count, x_out, m, M, K, T, V, step);
   return check_launch("stream_push");
+}
+
+int coskad_stream_push_cams_f32(const float* raw, const int* slot, const int* slot_host, const int* reset, const int* out_index,
+                                const double* center, const double* scale, const float* res, const float* res_host, int flags,
+                                const float* mats, float* ring, int* count, float* x_out, int n, int m, int M, int K, int T, int V,
+                                int step, hipStream_t stream) {
+  if (int rc = push_args_bad("stream_push_cams", raw, slot, slot_host, reset, out_index, center, scale, flags, mats, ring, count, x_out, n,
+                             m, M, K, T, V, step))
+    return rc;
+  if (!(flags & kStreamNormalised)) {
+    if (!res || !res_host) return fail(COSKAD_ERR_ARG, "stream_push_cams: null pointer (res)");
+    for (int i = 0; i < n; ++i)
+      if (!(res_host[2 * i] >= 1.f && res_host[2 * i + 1] >= 1.f))
+        return fail(COSKAD_ERR_ARG, "stream_push_cams: res[%d]: video resolution %g x %g", i, (double)res_host[2 * i],
+                    (double)res_host[2 * i + 1]);
+  }
+  if ((long long)(T - 1) * step + 1 > 0x7fffffffLL / (2 * 18)) return fail(COSKAD_ERR_ARG, "stream_push_cams: step=%d", step);
+  if (const char* why = bad_slots(slot_host, n, M, true)) return fail(COSKAD_ERR_ARG, "stream_push_cams: %s", why);
+  if (flags & kStreamNormalised)        // the resolution is not read: no box is formed
+    hipLaunchKernelGGL(k_stream_push, dim3((unsigned)n), dim3(kStreamWave), 0, stream, raw, slot, reset, out_index, center, scale, 0.f, 0.f,
+                       flags, mats, ring, count, x_out, m, M, K, T, V, step);
+  else
+    hipLaunchKernelGGL(k_stream_push_cams, dim3((unsigned)n), dim3(kStreamWave), 0, stream, raw, slot, reset, out_index, center, scale, res,
+                       flags, mats, ring, count, x_out, m, M, K, T, V, step);
+  return check_launch("stream_push_cams");
 }
 
 int coskad_stream_frames_f64(const void* scores, int scores_f64, const int* slot, const int* slot_host, const int* clip_index,
@@ -278,6 +391,26 @@ int coskad_stream_close_f64(const int* row_slot, const int* row_slot_host, const
   hipLaunchKernelGGL(k_stream_close, dim3((unsigned)ceil_div(rows * K, kStreamBlock)), dim3(kStreamBlock), 0, stream, row_slot, row_index,
                      clip_index, count, wscore, frame_mean, clip, rows, M, K, T, step, clip_frames);
   return check_launch("stream_close");
+}
+
+int coskad_stream_smooth_f64(const double* clip, const int* items, const int* items_host, const double* taps, int n_taps, double* per_t,
+                             double* mean, int n_items, int K, int F, hipStream_t stream) {
+  if (!clip) return fail(COSKAD_ERR_ARG, "stream_smooth: null pointer (clip)");
+  if (!items || !items_host) return fail(COSKAD_ERR_ARG, "stream_smooth: null pointer (items)");
+  if (!taps) return fail(COSKAD_ERR_ARG, "stream_smooth: null pointer (taps)");
+  if (!per_t || !mean) return fail(COSKAD_ERR_ARG, "stream_smooth: null pointer (per_t, mean)");
+  if (n_items <= 0 || K <= 0 || F <= 0 || (long long)n_items * K > 0x7fffffffLL)
+    return fail(COSKAD_ERR_ARG, "stream_smooth: n_items=%d K=%d F=%d", n_items, K, F);
+  if (n_taps != kStreamTaps)
+    return fail(COSKAD_ERR_SHAPE, "stream_smooth: unsupported tap table of %d entries: the filter has %d taps (centre + radius %d)", n_taps,
+                kStreamTaps, kStreamRadius);
+  for (int q = 0; q < n_items; ++q) {
+    const int off = items_host[3 * q], n = items_host[3 * q + 1], i = items_host[3 * q + 2];
+    if (off < 0 || n <= 0 || n > 0x3fffffff || off > F - n || i < 0 || i >= n)
+      return fail(COSKAD_ERR_ARG, "stream_smooth: items[%d] = (offset %d, n %d, index %d) outside the buffer of %d frames", q, off, n, i, F);
+  }
+  hipLaunchKernelGGL(k_stream_smooth, dim3((unsigned)n_items), dim3(kStreamWave), 0, stream, clip, items, taps, per_t, mean, n_items, K, F);
+  return check_launch("stream_smooth");
 }
 
 }  // extern "C"

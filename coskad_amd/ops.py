@@ -1893,3 +1893,41 @@ def stream_close(row_slot, row_slot_host, row_index, clip_index, count, wscore, 
     call("coskad_stream_close_f64", row_slot, row_slot_host, row_index, clip_index if clip is not None else None, count, wscore, out, clip,
          clip.shape[1] if clip is not None else 0, rows, M, K, T, step, _stream())
     return out
+
+
+def stream_push_cams(raw, slot, slot_host, reset, out_index, center, scale, res, res_host, flags, mats, ring, count, m, T, V, step):
+    """`stream_push` for the detections of several cameras in one launch (`coskad_stream_push_cams_f32`): res [n, 2] f32 on the device =
+    (width, height) of each detection's video, res_host the host's copy; both None with STREAM_NORMALISED.  -> x_out [K m, 2, T, V]
+    (None at m = 0)."""
+    n, M, K = raw.shape[0], count.numel(), mats.shape[0]
+    R = stream_rows(T, step)
+    _chk(raw, "raw", (n, 34)); _chk(mats, "mats", (K, 3, 3)); _chk(ring, "ring", (M, R, 2, V)); _chk(count, "count", (M,), dtype=torch.int32)
+    for name, t in (("slot", slot), ("reset", reset), ("out_index", out_index)):
+        _chk(t, name, (n,), dtype=torch.int32)
+    _chk_host_i32(slot_host, "slot_host", n)
+    _chk(center, "center", (34,), dtype=torch.float64, optional=True); _chk(scale, "scale", (34,), dtype=torch.float64, optional=True)
+    if res is not None or not flags & STREAM_NORMALISED:
+        _chk(res, "res", (n, 2))
+        if res_host is None or res_host.is_cuda or res_host.dtype != torch.float32 or not res_host.is_contiguous() or res_host.numel() != 2 * n:
+            raise ValueError(f"res_host: expected {2 * n} contiguous float32 values on the host")
+    x_out = torch.empty(K * m, 2, T, V, device=raw.device, dtype=torch.float32) if m > 0 else None
+    call("coskad_stream_push_cams_f32", raw, slot, slot_host, reset, out_index, center, scale, res, res_host, flags, mats, ring, count,
+         x_out, n, m, M, K, T, V, step, _stream())
+    return x_out
+
+
+def stream_smooth(clip, items, items_host, taps):
+    """Fixed-lag smoothing over the flat clip buffer (`coskad_stream_smooth_f64`): clip [K, F] f64, items [n_items, 3] int32 on the
+    device = (segment offset, segment length, output index), items_host the host's copy, taps = gaussian_taps().
+    -> (per_t [K, n_items], mean over the transformations [n_items]), float64."""
+    _chk(clip, "clip", dtype=torch.float64); _chk(taps, "taps", dtype=torch.float64)
+    if clip.dim() != 2:
+        raise ValueError(f"clip: expected [K, F], got {tuple(clip.shape)}")
+    K, F = clip.shape
+    n = items.shape[0]
+    _chk(items, "items", (n, 3), dtype=torch.int32)
+    _chk_host_i32(items_host, "items_host", 3 * n)
+    per_t = torch.empty(K, n, device=clip.device, dtype=torch.float64)
+    mean = torch.empty(n, device=clip.device, dtype=torch.float64)
+    call("coskad_stream_smooth_f64", clip, items, items_host, taps, taps.numel(), per_t, mean, n, K, F, _stream())
+    return per_t, mean

@@ -611,20 +611,37 @@ int coskad_attribution_frames_f64(const float* attr, const int* frames, const in
  *           is order-free, so the result is reproducible); clip_index[j] outside [0, clip_frames) is skipped.
  *   close : row_slot / row_index [rows]: trailing rows of closed tracks (at most min(count, R - 1) per track) -> frame_mean [K, rows]
  *           from the windows that exist (0 for a track that never filled one), folded into clip likewise.
+ *   push_cams: `push` for the detections of several cameras in one launch (coskad_amd.stream.StreamBank): res [n, 2] f32 on
+ *           the device = (width, height) of each detection's video instead of the two scalars, res_host the host's copy, which the
+ *           launcher checks (every side >= 1); both are ignored (may be NULL) with flags & 4.  Same arithmetic, same results.
+ *   smooth: fixed-lag smoothing over a flat clip buffer clip [K, F] that holds one segment per camera.  items [n_items, 3] int32 =
+ *           (segment offset, segment length n, output index i), items_host the host's copy: per transformation shifted[j] = raw[j - 11]
+ *           (0 below 11) under the `reflect` boundary of period 2n, the centre tap first, then (x[i - k] + x[i + k]) taps[k] for
+ *           k = 120 .. 1 -- bit for bit coskad_score_smooth_f64's value of that segment; per_t [K, n_items], mean [n_items] = (sum over
+ *           t in order) / K.  No atomics.  An item reads raw[max(0, i - 131) .. min(n - 1, i + 109)] (reflected where i + 120 >= n or
+ *           i < 120): while a segment's right end is open the caller asks only for i whose reads are final.  n_taps != 121:
+ *           COSKAD_ERR_SHAPE; an item with offset < 0, n <= 0, offset + n > F or i outside [0, n): COSKAD_ERR_ARG, naming the row.
  * slot_host / row_slot_host: the host's copy of the slots, which the launcher checks before the launch.  NULL pointers, non-positive
  * sizes, m > n, a slot outside [0, M) or twice in one push / frames launch, V that does not match the flags: COSKAD_ERR_ARG;
  * T outside {8, 12, 16, 24} or V outside {14, 17, 18}: COSKAD_ERR_SHAPE; all before the device is touched. */
 int coskad_stream_ok(int T, int V);
+int coskad_stream_smooth_lag(void);      /* 120: frames between a final raw clip score and its final smoothed score */
 int coskad_stream_push_f32(const float* raw, const int* slot, const int* slot_host, const int* reset, const int* out_index,
                            const double* center, const double* scale, float width, float height, int flags, const float* mats,
                            float* ring, int* count, float* x_out, int n, int m, int M, int K, int T, int V, int step,
                            hipStream_t stream);
+int coskad_stream_push_cams_f32(const float* raw, const int* slot, const int* slot_host, const int* reset, const int* out_index,
+                                const double* center, const double* scale, const float* res, const float* res_host, int flags,
+                                const float* mats, float* ring, int* count, float* x_out, int n, int m, int M, int K, int T, int V,
+                                int step, hipStream_t stream);
 int coskad_stream_frames_f64(const void* scores, int scores_f64, const int* slot, const int* slot_host, const int* clip_index,
                              const int* count, double* wscore, double* frame_mean, double* clip, int clip_frames, int m, int M, int K,
                              int T, int step, hipStream_t stream);
 int coskad_stream_close_f64(const int* row_slot, const int* row_slot_host, const int* row_index, const int* clip_index, const int* count,
                             const double* wscore, double* frame_mean, double* clip, int clip_frames, int rows, int M, int K, int T,
                             int step, hipStream_t stream);
+int coskad_stream_smooth_f64(const double* clip, const int* items, const int* items_host, const double* taps, int n_taps, double* per_t,
+                             double* mean, int n_items, int K, int F, hipStream_t stream);
 
 /* ---- one-class heads, centre statistics, regulariser, optimiser ------------------------ */
 

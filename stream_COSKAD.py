@@ -3,7 +3,12 @@
 scaler beside it), replay the test split's trajectories clip by clip, frame by frame, through coskad_amd.stream.StreamScorer -- all
 persons of a clip interleaved by frame id, every track closed at the end of its clip -- then smooth the streamed clip vectors and take
 the AUC with the host functions eval_COSKAD.py's scoring uses.  Prints the same `final AUC score:` line; --out DIR keeps the
-pre-smoothing scores per clip as <scene>_<clip>.npy [num_transform, frames]."""
+pre-smoothing scores per clip as <scene>_<clip>.npy [num_transform, frames].
+
+--cameras N replays N clips at a time through one coskad_amd.stream.StreamBank: clip i of a group is camera i, the cameras' frames are
+interleaved tick by tick (one bank push serves them all), and each clip ends with `finish`.  The printed line is the same.
+--smoothed-out DIR additionally writes the scores the bank smoothed on the device at a lag of 120 frames, as
+<scene>_<clip>_smoothed.npy [num_transform, frames] (implies --cameras 1 where --cameras is not given)."""
 import argparse
 import os
 import pickle
@@ -15,7 +20,7 @@ import yaml
 from sklearn.metrics import roc_auc_score
 
 from coskad_amd.lit import LitEncoder, load_checkpoint
-from coskad_amd.stream import StreamScorer
+from coskad_amd.stream import StreamBank, StreamScorer
 from coskad_amd.utils.argparser import init_sub_args
 from coskad_amd.utils.eval_utils import eval_loss_type, score_process
 
@@ -45,11 +50,49 @@ def replay_clip(scorer, trajs, tids):
     scorer.close()
 
 
+def replay_group(bank, trajs, group, lengths):
+    """The clips `group` = [(scene, clip)] through the bank, clip i on camera i: every tick pushes the next frame of every camera that
+    has one (frames 1 .. n of a clip, nobody in view included), a camera whose clip is over is finished.
+    -> ({key: clip vector [K, n]}, {key: smoothed [K, n]} with `bank.smooth`), on the host"""
+    frames, pos, tids = {}, {}, {}
+    for cam, key in enumerate(group):
+        bank.reset(cam, clip_frames=lengths[key])
+        tids[cam] = [t for t in trajs if t[:2] == key]
+        pos[cam] = {t: {int(f): i for i, f in enumerate(trajs[t][0])} for t in tids[cam]}
+        frames[cam] = sorted(set(range(1, lengths[key] + 1)) | {f for t in tids[cam] for f in pos[cam][t]})
+    pieces = {cam: [] for cam in frames}
+
+    def keep(out):
+        at = 0
+        for cam, _, count in out.smoothed:
+            pieces[cam].append(out.smoothed_scores[:, at:at + count])
+            at += count
+
+    for tick in range(max(len(f) for f in frames.values())):
+        batch = {}
+        for cam, fr in frames.items():
+            if tick < len(fr):
+                here = [t for t in tids[cam] if fr[tick] in pos[cam][t]]
+                batch[cam] = (fr[tick], here, np.stack([trajs[t][1][pos[cam][t][fr[tick]]] for t in here]) if here else np.zeros((0, 34)))
+        keep(bank.push(batch))
+        for cam, fr in frames.items():
+            if tick == len(fr) - 1:
+                keep(bank.finish(cam))
+    raw = {key: bank.clip_scores(cam).cpu().numpy() for cam, key in enumerate(group)}
+    smoothed = {key: torch.cat(pieces[cam], 1).cpu().numpy() for cam, key in enumerate(group)} if bank.smooth else {}
+    return raw, smoothed
+
+
 def main():
     parser = argparse.ArgumentParser(description='Pose_AD_Experiment')
     parser.add_argument('-c', '--config', type=str, required=True)
     parser.add_argument('--out', type=str, default=None)        # <scene>_<clip>.npy: the streamed scores before smoothing
+    parser.add_argument('--cameras', type=int, default=None)    # N clips at a time through one StreamBank, clip i on camera i
+    parser.add_argument('--smoothed-out', type=str, default=None)       # <scene>_<clip>_smoothed.npy: the bank's device-smoothed scores
     cli = parser.parse_args()
+    n_cams = cli.cameras if cli.cameras is not None else (1 if cli.smoothed_out else None)
+    if n_cams is not None and n_cams < 1:
+        parser.error("--cameras: at least 1")
     args = argparse.Namespace(**yaml.load(open(cli.config), Loader=yaml.FullLoader))
     args, dataset_args, ae_args, res_args, opt_args = init_sub_args(args)
     torch.cuda.set_device(0)
@@ -79,7 +122,11 @@ def main():
         mats = np.stack([np.eye(3, dtype=np.float32), np.array([[0, 1, 0], [1, 0, 0], [0, 0, 1]], dtype=np.float32)])
         if K > 2:
             raise ValueError("stream_COSKAD.py: the synthetic generator has two transformations")
-        scorer = StreamScorer(model, None, None, max_tracks=16, num_transform=K, clip_frames=1, mats=mats[:K])
+        if n_cams is None:
+            scorer = StreamScorer(model, None, None, max_tracks=16, num_transform=K, clip_frames=1, mats=mats[:K])
+        else:
+            scorer = StreamBank(model, None, {c: dict(vid_res=None, clip_frames=1) for c in range(n_cams)}, max_tracks=16 * n_cams,
+                                num_transform=K, mats=mats[:K], smooth=bool(cli.smoothed_out))
         hr_masks = None
     else:
         # eval_COSKAD.py:107-116: test split of the Morais-format tree, scaler pickled by the training run
@@ -97,12 +144,22 @@ def main():
         gts = model._load_gts()
         hr_masks = model._load_hr_masks()
         live = max(len([t for t in trajs if t[:2] == c]) for c in {t[:2] for t in trajs})
-        scorer = StreamScorer(model, scaler, getattr(dataset_args, 'vid_res', [1080, 720]), max_tracks=max(live, 1), num_transform=K,
-                              clip_frames=1)
-    raw = {}
-    for key in sorted(gts):
-        n = int(np.asarray(gts[key]).shape[0])
-        scorer.reset(clip_frames=n)
+        res = getattr(dataset_args, 'vid_res', [1080, 720])
+        if n_cams is None:
+            scorer = StreamScorer(model, scaler, res, max_tracks=max(live, 1), num_transform=K, clip_frames=1)
+        else:
+            scorer = StreamBank(model, scaler, {c: dict(vid_res=res, clip_frames=1) for c in range(n_cams)},
+                                max_tracks=max(live, 1) * n_cams, num_transform=K, smooth=bool(cli.smoothed_out))
+    raw, smoothed = {}, {}
+    keys = sorted(gts)
+    lengths = {key: int(np.asarray(gts[key]).shape[0]) for key in keys}
+    if n_cams is not None:
+        for g in range(0, len(keys), n_cams):
+            a, b = replay_group(scorer, trajs, keys[g:g + n_cams], lengths)
+            raw.update(a)
+            smoothed.update(b)
+    for key in keys if n_cams is None else []:
+        scorer.reset(clip_frames=lengths[key])
         tids = [t for t in trajs if t[:2] == key]
         if tids:
             replay_clip(scorer, trajs, tids)
@@ -111,8 +168,11 @@ def main():
         os.makedirs(cli.out, exist_ok=True)
         for (sc, cl), v in raw.items():
             np.save(os.path.join(cli.out, f"{sc}_{cl}.npy"), v)
+    if cli.smoothed_out:
+        os.makedirs(cli.smoothed_out, exist_ok=True)
+        for (sc, cl), v in smoothed.items():
+            np.save(os.path.join(cli.smoothed_out, f"{sc}_{cl}_smoothed.npy"), v)
     hr_masks = hr_masks or {}
-    keys = sorted(gts)
     per_t = [np.concatenate([score_process(raw[k][t][hr_masks[k]] if k in hr_masks else raw[k][t], win_size=int(getattr(args, 'smoothing', 50)),
                                            dataname=args.dataset_choice, use_scaler=False) for k in keys]) for t in range(K)]
     gt = np.concatenate([np.asarray(gts[k])[hr_masks[k]] if k in hr_masks else np.asarray(gts[k]) for k in keys])
