@@ -6,7 +6,8 @@
 // can cover, by the rules of k_score_person_frames (score_frames.hip).  k_stream_close finalises a closed track's trailing rows.
 // For many cameras per tick (StreamBank) k_stream_push_cams is the push kernel with the video resolution per detection, and
 // k_stream_smooth hands out the shifted, Gaussian-smoothed clip scores of a flat clip buffer (one segment per camera) item by item, with
-// k_score_smooth's arithmetic.
+// k_score_smooth's arithmetic.  k_stream_maps / k_stream_maps_close do for per-joint window maps (attribution, reconstruction error)
+// what k_stream_frames / k_stream_close do for the scores, with k_attribution_frames' arithmetic.
 //
 // Device state, capacity M tracks, R = (T - 1) step + 1 rows between a window's first and last row:
 //   ring   [M, R, 2, V] f32 : row r of a track at slot r % R
@@ -279,6 +280,78 @@ __global__ __launch_bounds__(kStreamWave) void k_stream_smooth(const double* __r
   if (lane == 0) mean[q] = ok ? acc_t / (double)K : 0.0;
 }
 
+// Per-joint maps beside the scores: the streaming counterpart of k_attribution_frames (attribution_frames.hip).  A window's
+// map [T, V] holds one row per frame of the window; a track row's map is the mean, over the windows that cover the row, of the row each
+// holds for it.  Windows arrive in ascending start, so adding a window's rows on arrival forms that kernel's fp64 sums in its order.
+// State per (track, transformation): sums [R, V] f64 and counts [R] i32, row i of the track at slot i % R; one buffer, the sums of all
+// tracks [M, K, R, V] first, then the counts [M, K, R].  The state is keyed on `count`: a track's FIRST window (e == R - 1) overwrites
+// every slot -- its T target rows with their value, the rows between them (step > 1) with an empty sum -- and a later window overwrites
+// the slot of its newest row e, whose former tenant e - R was final a push ago.  So a reused slot never sees its previous track's sums
+// and nothing has to be cleared.  Unlike the score ring an exact 0 counts, and a row no window covers is NaN.
+__host__ __device__ inline size_t stream_maps_rows(int M, int K, int T, int step) { return (size_t)M * K * ((size_t)(T - 1) * step + 1); }
+
+// one wave = one (transformation, ready track): its T target rows are distinct, so no two lanes add to one sum
+__global__ __launch_bounds__(kStreamWave) void k_stream_maps(const float* __restrict__ maps, const int* __restrict__ slot,
+                                                             const int* __restrict__ count, double* __restrict__ sums,
+                                                             int* __restrict__ cnts, double* __restrict__ frame_map, int m, int M, int K,
+                                                             int T, int V, int step) {
+  const int j = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+  const int sl = slot[j];
+  const int R = (T - 1) * step + 1;
+  double* out = frame_map + ((size_t)k * m + j) * V;
+  const int e = (unsigned)sl < (unsigned)M ? uniform(count[sl]) - 1 : -1;
+  if (e < R - 1) {                                      // uniform per wave: the host's mirror and `count` disagree
+    if (lane < V) out[lane] = __builtin_nan("");
+    return;
+  }
+  double* S = sums + ((size_t)sl * K + k) * R * V;
+  int* C = cnts + ((size_t)sl * K + k) * R;
+  const bool first = e == R - 1;
+  // the count of the row that becomes final, read by every lane before any lane stores one (readfirstlane waits for the load)
+  const int c0 = first ? 0 : uniform(C[(e - (R - 1)) % R]);
+  if (first && step > 1) {                              // rows between the first window's rows: covered later, or never
+    for (int q = lane; q < R * V; q += kStreamWave) {
+      const int r = q / V;
+      if (r % step == 0) continue;
+      S[q] = 0.0;
+      if (q == r * V) C[r] = 0;
+    }
+  }
+  const float* w = maps + ((size_t)k * m + j) * T * V;
+  for (int p = lane; p < T * V; p += kStreamWave) {
+    const int t = p / V, v = p - t * V;
+    const int pos = (e - (T - 1 - t) * step) % R;
+    const bool fresh = first || t == T - 1;
+    const double s = (fresh ? 0.0 : S[(size_t)pos * V + v]) + (double)w[p];        // 0.0 + x: the offline sum's first step
+    S[(size_t)pos * V + v] = s;
+    if (v == 0) C[pos] = fresh ? 1 : C[pos] + 1;
+    if (t == 0) out[v] = s / (double)(c0 + 1);
+  }
+}
+
+// one thread = one (transformation, trailing row of a closed track, joint); the row is final with the windows that exist
+__global__ __launch_bounds__(kStreamBlock) void k_stream_maps_close(const int* __restrict__ row_slot, const int* __restrict__ row_index,
+                                                                    const int* __restrict__ count, const double* __restrict__ sums,
+                                                                    const int* __restrict__ cnts, double* __restrict__ frame_map,
+                                                                    int rows, int M, int K, int T, int V, int step) {
+  const size_t id = (size_t)blockIdx.x * kStreamBlock + threadIdx.x;
+  if (id >= (size_t)rows * K * V) return;
+  const int v = (int)(id % V);
+  const int q = (int)((id / V) % rows), k = (int)(id / V / rows);
+  const int sl = row_slot[q], i = row_index[q];
+  const int R = (T - 1) * step + 1;
+  double mean = __builtin_nan("");
+  if ((unsigned)sl < (unsigned)M) {
+    const int last = count[sl] - 1;
+    if (last >= R - 1 && i >= 0 && i <= last && i > last - R) {      // the track filled a window and the state still holds the row
+      const size_t at = ((size_t)sl * K + k) * R + (size_t)(i % R);
+      const int c = cnts[at];
+      if (c > 0) mean = sums[at * V + v] / (double)c;
+    }
+  }
+  frame_map[id] = mean;
+}
+
 // the host mirror of a launch's slots: every one inside [0, M); `distinct`: no slot twice (two waves would write one ring)
 static const char* bad_slots(const int* slot_host, int n, int M, bool distinct) {
   for (int i = 0; i < n; ++i)
@@ -391,6 +464,53 @@ int coskad_stream_close_f64(const int* row_slot, const int* row_slot_host, const
   hipLaunchKernelGGL(k_stream_close, dim3((unsigned)ceil_div(rows * K, kStreamBlock)), dim3(kStreamBlock), 0, stream, row_slot, row_index,
                      clip_index, count, wscore, frame_mean, clip, rows, M, K, T, step, clip_frames);
   return check_launch("stream_close");
+}
+
+size_t coskad_stream_maps_state_bytes(int M, int K, int T, int V, int step) {
+  if (M <= 0 || K <= 0 || step <= 0 || !coskad_stream_ok(T, V) || (long long)(T - 1) * step + 1 > 0x7fffffffLL / (2 * 18)) return 0;
+  const size_t rows = stream_maps_rows(M, K, T, step);
+  return rows * V * sizeof(double) + (rows * sizeof(int) + 7) / 8 * 8;
+}
+
+// the checks both maps entries share; `who` names the entry in the message
+static int maps_args_bad(const char* who, const char* items, const void* state, size_t state_bytes, int n, int M, int K, int T, int V,
+                         int step) {
+  if (n <= 0 || M <= 0 || K <= 0 || step <= 0 || (long long)n * K * 18 > 0x7fffffffLL)
+    return fail(COSKAD_ERR_ARG, "%s: %s=%d max_tracks=%d K=%d step=%d", who, items, n, M, K, step);
+  if (!coskad_stream_ok(T, V))
+    return fail(COSKAD_ERR_SHAPE, "%s: unsupported (n_frames=%d, n_joints=%d): windows of 8 / 12 / 16 / 24 frames, 14 / 17 / 18 joints", who,
+                T, V);
+  const size_t need = coskad_stream_maps_state_bytes(M, K, T, V, step);
+  if (need == 0) return fail(COSKAD_ERR_ARG, "%s: step=%d", who, step);
+  if (state_bytes < need) return fail(COSKAD_ERR_ARG, "%s: state of %zu bytes, coskad_stream_maps_state_bytes asks for %zu", who, state_bytes, need);
+  if ((size_t)state % sizeof(double)) return fail(COSKAD_ERR_ARG, "%s: state is not aligned to 8 bytes", who);
+  return 0;
+}
+
+int coskad_stream_maps_f64(const float* maps, const int* slot, const int* slot_host, const int* count, double* state, size_t state_bytes,
+                           double* frame_map, int m, int M, int K, int T, int V, int step, hipStream_t stream) {
+  if (!maps || !slot || !slot_host || !count || !state || !frame_map) return fail(COSKAD_ERR_ARG, "stream_maps: null pointer");
+  if (m > M) return fail(COSKAD_ERR_ARG, "stream_maps: m=%d ready tracks, more than max_tracks=%d", m, M);
+  if (int rc = maps_args_bad("stream_maps", "m", state, state_bytes, m, M, K, T, V, step)) return rc;
+  if (K > 65535) return fail(COSKAD_ERR_ARG, "stream_maps: K=%d", K);
+  if (const char* why = bad_slots(slot_host, m, M, true)) return fail(COSKAD_ERR_ARG, "stream_maps: %s", why);
+  const size_t rows = stream_maps_rows(M, K, T, step);
+  hipLaunchKernelGGL(k_stream_maps, dim3((unsigned)m, (unsigned)K), dim3(kStreamWave), 0, stream, maps, slot, count, state,
+                     reinterpret_cast<int*>(state + rows * V), frame_map, m, M, K, T, V, step);
+  return check_launch("stream_maps");
+}
+
+int coskad_stream_maps_close_f64(const int* row_slot, const int* row_slot_host, const int* row_index, const int* count,
+                                 const double* state, size_t state_bytes, double* frame_map, int rows, int M, int K, int T, int V,
+                                 int step, hipStream_t stream) {
+  if (!row_slot || !row_slot_host || !row_index || !count || !state || !frame_map)
+    return fail(COSKAD_ERR_ARG, "stream_maps_close: null pointer");
+  if (int rc = maps_args_bad("stream_maps_close", "rows", state, state_bytes, rows, M, K, T, V, step)) return rc;
+  if (const char* why = bad_slots(row_slot_host, rows, M, false)) return fail(COSKAD_ERR_ARG, "stream_maps_close: %s", why);
+  const size_t all = stream_maps_rows(M, K, T, step);
+  hipLaunchKernelGGL(k_stream_maps_close, dim3((unsigned)ceil_div(rows * K * V, kStreamBlock)), dim3(kStreamBlock), 0, stream, row_slot,
+                     row_index, count, state, reinterpret_cast<const int*>(state + all * V), frame_map, rows, M, K, T, V, step);
+  return check_launch("stream_maps_close");
 }
 
 int coskad_stream_smooth_f64(const double* clip, const int* items, const int* items_host, const double* taps, int n_taps, double* per_t,

@@ -1931,3 +1931,46 @@ def stream_smooth(clip, items, items_host, taps):
     mean = torch.empty(n, device=clip.device, dtype=torch.float64)
     call("coskad_stream_smooth_f64", clip, items, items_host, taps, taps.numel(), per_t, mean, n, K, F, _stream())
     return per_t, mean
+
+
+def stream_maps_state_bytes(M: int, K: int, T: int, V: int, step: int) -> int:
+    """Host arithmetic of `coskad_stream_maps_state_bytes`: fp64 sums [M, K, R, V], then int32 counts [M, K, R] rounded up to 8 bytes;
+    0 for sizes the maps entries refuse.  tests/test_stream_maps_host.py holds the two in agreement."""
+    if M <= 0 or K <= 0 or step <= 0 or not stream_ok(T, V) or stream_rows(T, step) > (2 ** 31 - 1) // 36:
+        return 0
+    rows = M * K * stream_rows(T, step)
+    return rows * V * 8 + (rows * 4 + 7) // 8 * 8
+
+
+def stream_maps_state(M: int, K: int, T: int, V: int, step: int, device) -> Tensor:
+    """The per-track map state of `stream_maps`, as float64 words (the counts live in its tail); needs no clearing between tracks."""
+    nbytes = stream_maps_state_bytes(M, K, T, V, step)
+    if nbytes == 0:
+        raise ValueError(f"stream_maps_state: unsupported (max_tracks={M}, K={K}, n_frames={T}, n_joints={V}, step={step})")
+    return torch.zeros(nbytes // 8, device=device, dtype=torch.float64)
+
+
+def stream_maps(maps, slot, slot_host, count, state, K, T, V, step):
+    """The window maps [K m, T, V] f32 of a push's windows into the tracks' running sums; -> frame_map [K, m, V] f64, the map of the row
+    of every ready track that became final (`coskad_stream_maps_f64`): the mean over its covering windows in ascending start, NaN where
+    the track has no window.  After `stream_frames` of the same push, on every push that hands the track a window."""
+    M, m = count.numel(), slot.numel()
+    _chk(maps, "maps", (K * m, T, V)); _chk(slot, "slot", (m,), dtype=torch.int32); _chk(count, "count", (M,), dtype=torch.int32)
+    _chk(state, "state", dtype=torch.float64)
+    _chk_host_i32(slot_host, "slot_host", m)
+    out = torch.empty(K, m, V, device=maps.device, dtype=torch.float64)
+    call("coskad_stream_maps_f64", maps, slot, slot_host, count, state, _bytes(state), out, m, M, K, T, V, step, _stream())
+    return out
+
+
+def stream_maps_close(row_slot, row_slot_host, row_index, count, state, K, T, V, step):
+    """The maps of the trailing rows of closed tracks, final with the windows that exist (`coskad_stream_maps_close_f64`): row_slot /
+    row_index [rows] int32 -> frame_map [K, rows, V] f64; NaN for a track that never filled a window."""
+    M, rows = count.numel(), row_slot.numel()
+    _chk(row_slot, "row_slot", (rows,), dtype=torch.int32); _chk(row_index, "row_index", (rows,), dtype=torch.int32)
+    _chk(count, "count", (M,), dtype=torch.int32); _chk(state, "state", dtype=torch.float64)
+    _chk_host_i32(row_slot_host, "row_slot_host", rows)
+    out = torch.empty(K, rows, V, device=state.device, dtype=torch.float64)
+    call("coskad_stream_maps_close_f64", row_slot, row_slot_host, row_index, count, state, _bytes(state), out, rows, M, K, T, V, step,
+         _stream())
+    return out

@@ -139,6 +139,8 @@ class StreamOut(NamedTuple):
     final: List[Tuple[Hashable, int]]
     frame_scores: Optional[torch.Tensor]
     windows: Optional[torch.Tensor] = None          # [K m, 2, T, V]: the batch the stream formed (item k m + j)
+    frame_maps: Optional[torch.Tensor] = None       # maps = True: [K, len(final), V] float64, the per-joint map of every final row
+    window_maps: Optional[torch.Tensor] = None      # maps = True: [K m, T, V], the per-joint map of every window (item k m + j)
 
 
 def _refusal(lit, what: str = "StreamScorer") -> Optional[str]:
@@ -153,12 +155,23 @@ def _refusal(lit, what: str = "StreamScorer") -> Optional[str]:
     return None
 
 
+def _maps_refusal(lit, what: str) -> Optional[str]:
+    """why `maps = True` does not take this wrapper: the reason its own map call would give, before any push"""
+    from .lit import LitAutoEncoder
+    if isinstance(lit, LitAutoEncoder):
+        why = lit._error_map_refusal()
+        return None if why is None else f"{what}: maps = True: window_error_map: {why}"
+    from . import attribution
+    why = attribution.unsupported_reason(lit)
+    return None if why is None else f"{what}: maps = True: window_attribution: {why}"
+
+
 class _StreamState:
     """What `StreamScorer` and `StreamBank` share: the wrapper and its layout, the transformations, the scaler's columns, the device
     state of the tracks (rings, row counts, score rings) and the pinned staging buffers of the one upload per push."""
 
-    def _setup(self, what, lit, scaler, normalised, max_tracks, seg_stride, num_transform, mats) -> None:
-        why = _refusal(lit, what)
+    def _setup(self, what, lit, scaler, normalised, max_tracks, seg_stride, num_transform, mats, maps=False) -> None:
+        why = _refusal(lit, what) or (_maps_refusal(lit, what) if maps else None)
         if why:
             raise ValueError(why)
         from .lit import LitAutoEncoder, _joints
@@ -188,6 +201,9 @@ class _StreamState:
         self.ring = torch.zeros(self.M, self.R, 2, self.V, device=dev, dtype=torch.float32)
         self.count = torch.zeros(self.M, device=dev, dtype=torch.int32)
         self.wscore = torch.zeros(self.M, self.K, self.R, device=dev, dtype=torch.float64)
+        # per-joint maps: running fp64 sums and counts per (track, transformation, ring row, joint)
+        self.maps = bool(maps)
+        self.map_state = ops.stream_maps_state(self.M, self.K, self.T, self.V, self.step, dev) if self.maps else None
         self._turn = 0
 
     def _staging(self, words: int) -> None:
@@ -211,6 +227,13 @@ class _StreamState:
                 return self.lit.window_scores_from_batch(x)
             return self.lit.window_scores(self.lit.model(x))
 
+    def _window_maps(self, x: torch.Tensor) -> torch.Tensor:
+        """[K m, T, V]: the wrapper's per-joint map of every window -- the reconstruction error of an autoencoder, the attribution of a
+        one-class encoder.  The window scores stay those of `_score`: the map chain's own score is not substituted."""
+        if self._ae:
+            return self.lit.window_error_map(x)[1].contiguous()
+        return self.lit.window_attribution(x)[2].contiguous()
+
 
 class StreamScorer(_StreamState):
     """StreamScorer(lit, scaler, vid_res, max_tracks=256, seg_stride=1, num_transform=1, clip_frames=None)
@@ -219,14 +242,18 @@ class StreamScorer(_StreamState):
     layout (`dataset_kp18_format`, `dataset_headless`) come from its args.  scaler: the training run's RobustScaler, or None with
     `normalize_pose` off.  vid_res: (width, height) of the video; None says the rows are normalised already (only the layout applies).
     num_transform: the first K of the dataset's affine transformations (`mats` [K, 3, 3] replaces them).  clip_frames: length of the
-    clip vector `clip_scores()` accumulates (max over persons at index frame id - 1), None for none.
+    clip vector `clip_scores()` accumulates (max over persons at index frame id - 1), None for none.  maps: also hand out WHERE a frame
+    was anomalous -- `window_maps`, the per-joint map of every window (`window_attribution` of an encoder wrapper,
+    `window_error_map` of the autoencoder), and `frame_maps`, the map of every (track, frame) as it becomes final: the mean over its
+    covering windows, bit for bit `eval_utils.attribution_frames_device`'s (NaN for a row no window covers).  One map call and one
+    launch more per push; ValueError with the map call's own reason for a wrapper it does not take.
 
     `push` enqueues one pinned non-blocking upload, the push launch, the wrapper's eval scoring of the windows and the frames launch on
     the current stream and never synchronises.  ValueError, naming the reason, for train mode, `LitVAE` and `num_coords != 2`."""
 
     def __init__(self, lit, scaler, vid_res, max_tracks: int = 256, seg_stride: int = 1, num_transform: int = 1,
-                 clip_frames: Optional[int] = None, mats=None) -> None:
-        self._setup("StreamScorer", lit, scaler, vid_res is None, max_tracks, seg_stride, num_transform, mats)
+                 clip_frames: Optional[int] = None, mats=None, maps: bool = False) -> None:
+        self._setup("StreamScorer", lit, scaler, vid_res is None, max_tracks, seg_stride, num_transform, mats, maps)
         self.vid_res = None if vid_res is None else (float(vid_res[0]), float(vid_res[1]))
         self.clip = None if clip_frames is None else torch.zeros(self.K, int(clip_frames), device=self.device, dtype=torch.float64)
         # one upload per push: raw rows, slots, reset flags, window positions, ready slots and clip indices in one buffer of 4-byte words
@@ -283,11 +310,17 @@ class StreamScorer(_StreamState):
         scores = self._score(x).reshape(-1)
         fm = ops.stream_frames(scores.contiguous(), d[b:b + m], self._pin[i][b:b + m], d[b + m:tot], self.count, self.wscore, self.clip,
                                self.T, self.step)
-        return StreamOut(p.ready_tracks, p.first_frames, scores.reshape(self.K, m), list(zip(p.ready_tracks, p.first_frames)), fm, x)
+        wmap = fmap = None
+        if self.maps:
+            wmap = self._window_maps(x)
+            fmap = ops.stream_maps(wmap, d[b:b + m], self._pin[i][b:b + m], self.count, self.map_state, self.K, self.T, self.V, self.step)
+        return StreamOut(p.ready_tracks, p.first_frames, scores.reshape(self.K, m), list(zip(p.ready_tracks, p.first_frames)), fm, x,
+                         fmap, wmap)
 
     def close(self, track_ids: Optional[Iterable[Hashable]] = None) -> StreamOut:
         """Ends the tracks (all live ones by default): -> the trailing (track, frame id) rows, final with the windows that exist, and
-        their frame scores [K, rows]; all 0 for a track that never filled a window.  The slots are free for new tracks."""
+        their frame scores [K, rows]; all 0 for a track that never filled a window (their maps, with `maps`, are NaN then).  The slots
+        are free for new tracks."""
         closed = self.plan.close(track_ids)
         final = [(c.track, f) for c in closed for _, f in c.rows]
         if not final:
@@ -296,7 +329,10 @@ class StreamScorer(_StreamState):
                               [f - 1 for c in closed for _, f in c.rows]], dtype=torch.int32).pin_memory()
         dev = table.to(self.device, non_blocking=True)
         fm = ops.stream_close(dev[0], table[0], dev[1], dev[2], self.count, self.wscore, self.clip, self.T, self.step)
-        return StreamOut([], [], None, final, fm)
+        fmap = None
+        if self.maps:
+            fmap = ops.stream_maps_close(dev[0], table[0], dev[1], self.count, self.map_state, self.K, self.T, self.V, self.step)
+        return StreamOut([], [], None, final, fm, None, fmap)
 
     def clip_scores(self) -> torch.Tensor:
         """[K, clip_frames] float64 on the device: per transformation the max over the persons of the frame scores that are final,
@@ -312,6 +348,8 @@ class StreamScorer(_StreamState):
             self.clip = torch.zeros(self.K, int(clip_frames), device=self.device, dtype=torch.float64)
         elif self.clip is not None:
             self.clip.zero_()
+        if self.map_state is not None:
+            self.map_state.zero_()
 
 
 # ---- many cameras per tick, fixed-lag smoothed scores --------------------------------------------------------------
@@ -547,6 +585,8 @@ class BankOut(NamedTuple):
     smoothed: Sequence[Tuple[Hashable, int, int]] = ()
     smoothed_scores: Optional[torch.Tensor] = None
     smoothed_mean: Optional[torch.Tensor] = None
+    frame_maps: Optional[torch.Tensor] = None       # maps = True: [K, len(final), V] float64
+    window_maps: Optional[torch.Tensor] = None      # maps = True: [K m, T, V]
 
 
 class StreamBank(_StreamState):
@@ -561,16 +601,18 @@ class StreamBank(_StreamState):
     smoothed score became emit-able.  Nothing synchronises, and the number of library calls does not depend on the number of cameras.
     smooth: hand out the shifted, Gaussian-smoothed clip score (what the offline evaluation thresholds) 120 frames behind the raw one;
     `finish(cam)` emits the clip's tail.  idle_close = N closes, at the start of a push, the tracks of a pushed camera not seen for more
-    than N of its frame ids (a lost track would hold the camera's watermark back for ever)."""
+    than N of its frame ids (a lost track would hold the camera's watermark back for ever).  maps: as `StreamScorer`'s -- one map call
+    on the ready windows of all cameras and ONE maps launch per tick (plus one beside the close launch on ticks that close tracks); the
+    map state is indexed by slot, as the score ring is, and keyed on the row count, so `reset(cam)` has nothing to clear."""
 
     def __init__(self, lit, scaler, cameras, max_tracks: int = 1024, seg_stride: int = 1, num_transform: int = 1, mats=None,
-                 smooth: bool = False, idle_close: Optional[int] = None) -> None:
+                 smooth: bool = False, idle_close: Optional[int] = None, maps: bool = False) -> None:
         why = _refusal(lit, "StreamBank")
         if why:
             raise ValueError(why)
         self.bank = BankPlan(cameras, max_tracks, int(lit.args.dataset_seg_len), seg_stride, smooth, idle_close)
         normalised = next(iter(self.bank.cams.values())).res is None
-        self._setup("StreamBank", lit, scaler, normalised, max_tracks, seg_stride, num_transform, mats)
+        self._setup("StreamBank", lit, scaler, normalised, max_tracks, seg_stride, num_transform, mats, maps)
         self.plan = self.bank.plan
         self.smooth = self.bank.smooth
         self.clip = self._new_clip()
@@ -619,10 +661,13 @@ class StreamBank(_StreamState):
         ev = self._busy[i] or torch.cuda.Event()
         ev.record()
         self._busy[i] = ev
-        final, parts = [], []
+        final, parts, mparts, wmap = [], [], [], None
         if r:       # before the push launch: a freed slot may start a new track in this very tick
             parts.append(ops.stream_close(d[c:c + r], pin[c:c + r], d[c + r:c + 2 * r], d[c + 2 * r:e], self.count, self.wscore, self.clip,
                                           self.T, self.step))
+            if self.maps:
+                mparts.append(ops.stream_maps_close(d[c:c + r], pin[c:c + r], d[c + r:c + 2 * r], self.count, self.map_state, self.K,
+                                                    self.T, self.V, self.step))
             final += [(t.track, f) for t in tick.closed for _, f in t.rows]
         scores = x = None
         if n:
@@ -637,12 +682,17 @@ class StreamBank(_StreamState):
             parts.append(ops.stream_frames(scores.contiguous(), d[b:b + m], pin[b:b + m], d[b + m:c], self.count, self.wscore, self.clip,
                                            self.T, self.step))
             final += list(zip(p.ready_tracks, p.first_frames))
+            if self.maps:
+                wmap = self._window_maps(x)
+                mparts.append(ops.stream_maps(wmap, d[b:b + m], pin[b:b + m], self.count, self.map_state, self.K, self.T, self.V,
+                                              self.step))
         per_t = mean = None
         if s:
             per_t, mean = ops.stream_smooth(self.clip, d[e:tot].view(s, 3), pin[e:tot], self.taps)
         fm = None if not parts else parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        fmap = None if not mparts else mparts[0] if len(mparts) == 1 else torch.cat(mparts, 1)
         return BankOut(list(p.ready_tracks) if m else [], list(p.first_frames) if m else [], scores.reshape(self.K, m) if m else None,
-                       final, fm, x, tick.smoothed, per_t, mean)
+                       final, fm, x, tick.smoothed, per_t, mean, fmap, wmap)
 
     def push(self, batch) -> BankOut:
         """batch: {cam: (frame_id, track_ids, keypoints)}, keypoints [n, 17, 2] or [n, 34] per camera (pixel coordinates, zeros =

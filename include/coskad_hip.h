@@ -643,6 +643,30 @@ int coskad_stream_close_f64(const int* row_slot, const int* row_slot_host, const
 int coskad_stream_smooth_f64(const double* clip, const int* items, const int* items_host, const double* taps, int n_taps, double* per_t,
                              double* mean, int n_items, int K, int F, hipStream_t stream);
 
+/* Per-joint maps beside the scores: the streaming counterpart of coskad_attribution_frames_f64.  state: one buffer of
+ * coskad_stream_maps_state_bytes(M, K, T, V, step) bytes, aligned to 8 -- running fp64 sums [M, K, R, V], then int32 counts [M, K, R],
+ * row i of a track at slot i % R (0 bytes for sizes the entries refuse).  The caller never has to clear it: a track's first window
+ * (count == R) overwrites every slot of the track, so a reused slot does not see its previous track's sums.
+ *   maps      : after `frames` of the same push.  maps [K m, T, V] f32, item k m + j as in x_out: the map of the window that ends at
+ *               the ready track's newest row e = count - 1; its row t is added to track row e - (T - 1 - t) step.  frame_map [K, m, V]
+ *               = the map of row e - (R - 1), final now: the mean over the windows that cover the row of the row each holds for it --
+ *               fp64 sums in ascending window start (the order of arrival), one division by the count, bit for bit
+ *               coskad_attribution_frames_f64's value.  Unlike `frames` an exact 0 counts.  NaN where count < R (the host's mirror and
+ *               `count` disagree).  One wave per (transformation, track), no atomics.  It must follow EVERY push that hands the track
+ *               a window: the sums are formed on arrival.
+ *   maps_close: row_slot / row_index [rows] as for `close`, before the slot's next push -> frame_map [K, rows, V] from the windows
+ *               that exist; NaN for a track that never filled a window, for a row no window covers (step > 1) and for a row the state
+ *               no longer holds.
+ * NULL pointers, non-positive sizes, m > M, a slot outside [0, M) or twice in one maps launch, state_bytes below the query or a
+ * misaligned state: COSKAD_ERR_ARG; T outside {8, 12, 16, 24} or V outside {14, 17, 18}: COSKAD_ERR_SHAPE; all before the device is
+ * touched. */
+size_t coskad_stream_maps_state_bytes(int M, int K, int T, int V, int step);
+int coskad_stream_maps_f64(const float* maps, const int* slot, const int* slot_host, const int* count, double* state, size_t state_bytes,
+                           double* frame_map, int m, int M, int K, int T, int V, int step, hipStream_t stream);
+int coskad_stream_maps_close_f64(const int* row_slot, const int* row_slot_host, const int* row_index, const int* count,
+                                 const double* state, size_t state_bytes, double* frame_map, int rows, int M, int K, int T, int V,
+                                 int step, hipStream_t stream);
+
 /* ---- one-class heads, centre statistics, regulariser, optimiser ------------------------ */
 
 int coskad_head_slots(void);            /* floats in a stats / acc block (19) at latent <= 16 */
