@@ -13,6 +13,7 @@
 #include "tile_ops.h"
 #include "layer_launch.h"
 #include "heads_common.h"
+#include "fused_ops.h"
 
 namespace coskad {
 
@@ -76,67 +77,117 @@ __global__ __launch_bounds__(64 * kBtlFwdWaves) void k_btlnk_fwd(const float* __
 // the L2 traffic of W drops to a quarter of the HBM traffic of U) x one of KS slices of K; the four waves split the
 // slice again.  Partials [KS][B][16] are summed in a fixed order by k_btlnk_fwd_sum (deterministic, no atomics).
 #ifndef BTL_KS
-#define BTL_KS 4      // sweep at B = 4096 (tools/ab_fused.sh, -DBTL_KS / -DBTL_UB): 4 x 2 -> 40.6 us, 8 x 2 -> 44.5, 16 x 2 -> 51.5, 8 x 4 -> 50
-#endif
-#ifndef BTL_UB
-#define BTL_UB 2
+#define BTL_KS 4      // sweep of the unstaged kernel at B = 4096, alone (tools/ab_fused.sh, -DBTL_KS, x steps per batch): 4 x 2 -> 40.6 us, 8 x 2 -> 44.5, 16 x 2 -> 51.5, 8 x 4 -> 50
 #endif
 constexpr int kBtlKS = BTL_KS;
+// The 16 K slices (4 per block x KS blocks) and the sums over them are fixed: slice g owns the k-steps [nsteps g / 16, nsteps (g + 1) / 16),
+// one MFMA chain per (slice, clip tile) in k order with the operands the MFMA layout asks for (lane (i, kk) of step s: the float4 at
+// row i, k = 16 s + 4 kk), the block's four slices meet as (r0 + r1) + (r2 + r3).  What is free is how the operands reach the lanes.
+// Loaded straight into that layout, a wave instruction touches 16 rows and half a 128-B line in each, and the kernel runs at the CU's
+// rate of line accesses, not at the memory rate: in the step 64 us, 50 without the W loads (a fifth of the instructions, all L2 hits), 47
+// with U read in whole runs (sweep below).  So every operand is STAGED: per group of kBtlGS = 4 k-steps a wave reads, for each of its
+// four clip tiles and for the W tile, 16 rows x 256 B with four instructions (4 rows x 16 lanes x 16 B: whole lines), writes them to
+// its own LDS image (row stride 72 floats: the ds_write_b128 of 8 lanes on a row and the ds_read_b128 of lane (i, kk) at row i,
+// 16 u + 4 kk are both conflict-free) and reads the MFMA operands back.  The image is private to the wave and the LDS pipe keeps a
+// wave's accesses in order, so there is no barrier in the loop.  A tile's next group is requested as soon as its registers have been
+// written to the image: 16 to 20 KB per wave stay in flight and the queue never drains (the loads return in issue order; each
+// tile waits with a counted vmcnt for its own four).  Buffer loads, whole offset in the lane register: rows past B and latents past L
+// fail the hardware's range check and read 0, the zero operand they always were; steps past the slice re-read its last step and are
+// left out by the tail.
+// Sweep, one traced train step each (B = 4096, K = 13 056, L = 16; the parent's 4 waves x 2 steps without prefetch: 63.1 - 64.4 us):
+//   direct loads, two register sets of 4 steps (40 loads in flight per wave)  60.5 - 61.1      sets of 2 steps  62.6      of 6  62.2
+//   the same on 8 waves x 2 tiles  68.6      on 16 waves x 1 tile  80.0   (W is loaded once per wave: instructions, not bytes in flight)
+//   staged as above  45.4 - 48.6 (median of three 46.7)
+constexpr int kBtlGS = 4;                       // k-steps per group: 256 B per row
+constexpr int kBtlLd = 72;                      // image row stride in floats (64 + 8)
+constexpr int kBtlTiles = 5;                    // four clip tiles + W
+constexpr int kBtlImg = kBtlTiles * 16 * kBtlLd;            // floats per wave
+constexpr size_t kBtlFwdLds = (size_t)4 * kBtlImg * sizeof(float);   // 92 160 B; the block's reduction reuses it
+static_assert(4 * 4 * 256 <= 4 * kBtlImg, "red[4][4][256] fits the images");
+template <bool PRE>
 __global__ __launch_bounds__(256) void k_btlnk_fwd_t(const float* __restrict__ U, const float* __restrict__ W,
                                                      const float* __restrict__ slope, float* __restrict__ part,
                                                      int B, int K, int L) {
-  __shared__ float red[4][4][256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = lane & 15, kk = lane >> 4;
+  constexpr int GS = kBtlGS, LD = kBtlLd, NT = kBtlTiles;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int lane = threadIdx.x & 63, wave = uniform(threadIdx.x >> 6);
+  const int i = lane & 15, kk = lane >> 4;                     // MFMA operand lane: row i, k quarter kk;  staging lane: row kk of four, float4 i
   const int clip0 = blockIdx.x * 64;
-  const bool pre = slope != nullptr;
-  const float a = pre ? slope[0] : 0.f;
-  const bool colok = i < L;
-  const float* wp = W + (size_t)(colok ? i : 0) * K + 4 * kk;
-  const float* up[4];
-  bool rowok[4];
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-    const int n = clip0 + 16 * ct + i;
-    rowok[ct] = n < B;
-    up[ct] = U + (size_t)(rowok[ct] ? n : 0) * K + 4 * kk;
-  }
+  const float a = PRE ? slope[0] : 0.f;
+  const int rows = min(64, B - clip0);
+  const ff::BufRes ures = ff::make_res(U + (size_t)clip0 * K, (unsigned)rows * (unsigned)K * 4u);   // <= 256 K bytes (K <= 2^23: the launcher)
+  const ff::BufRes wres = ff::make_res(W, (unsigned)L * (unsigned)K * 4u);
+  float* img = lds + wave * kBtlImg;
+  float* wr = img + kk * LD + 4 * i;                           // + (16 t + 4 q) LD: instruction q of tile t
+  const float* rd = img + i * LD + 4 * kk;                     // + 16 t LD + 16 u: step u of tile t
   const int nsteps = K / 16;                                   // K % 16 == 0 (checked by the launcher)
   const int g = blockIdx.y * 4 + wave, G = gridDim.y * 4;      // this wave's slice of the k-steps
   const int s0 = (int)((long long)nsteps * g / G), s1 = (int)((long long)nsteps * (g + 1) / G);
   f32x4 acc[4];
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int UB = BTL_UB;
-  for (int sb = s0; sb < s1; sb += UB) {
-    float4 x[4][UB], w[UB];
+  for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float4 gr[NT][4];                                            // a tile's four instructions of the group in flight
+  // tile t (0..3: clips 16 t ..; 4: W) of the group at step sb: lane (kk, i) of instruction q reads row 4 q + kk, floats 16 sb + 4 i ..
+  auto gload = [&](int t, int sb) {
+    const int st = min(sb + (i >> 2), s1 - 1);
+    const int ko = (16 * st + 4 * (i & 3)) * 4;
 #pragma unroll
-    for (int u = 0; u < UB; ++u) {
-      const bool ok = sb + u < s1;
-      const int k = (sb + u) * 16;
-      w[u] = (ok && colok) ? *reinterpret_cast<const float4*>(wp + k) : float4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        x[ct][u] = (ok && rowok[ct]) ? *reinterpret_cast<const float4*>(up[ct] + k) : float4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < 4; ++q) {
+      const int row = (t < 4 ? 16 * t : 0) + 4 * q + kk;
+      gr[t][q] = ff::buf_load4(t < 4 ? ures : wres, row * K * 4 + ko, 0);
     }
+  };
+  auto swrite = [&](int t) {
 #pragma unroll
-    for (int u = 0; u < UB; ++u)
+    for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(wr + (16 * t + 4 * q) * LD) = gr[t][q];
+  };
+  auto mac = [&](int nu) {                                     // the group's first nu steps (wave-uniform) from the image
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        float4 xv = x[ct][u];
-        if (pre) { xv.x = prelu_f(xv.x, a); xv.y = prelu_f(xv.y, a); xv.z = prelu_f(xv.z, a); xv.w = prelu_f(xv.w, a); }
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.x, w[u].x, acc[ct], 0, 0, 0);
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.y, w[u].y, acc[ct], 0, 0, 0);
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.z, w[u].z, acc[ct], 0, 0, 0);
-        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.w, w[u].w, acc[ct], 0, 0, 0);
+    for (int u = 0; u < GS; ++u) {
+      if (u >= nu) break;
+      const float4 wv = *reinterpret_cast<const float4*>(rd + 16 * 4 * LD + 16 * u);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float4 xv = *reinterpret_cast<const float4*>(rd + 16 * c * LD + 16 * u);
+        if (PRE) { xv.x = prelu_f(xv.x, a); xv.y = prelu_f(xv.y, a); xv.z = prelu_f(xv.z, a); xv.w = prelu_f(xv.w, a); }
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.x, wv.x, acc[c], 0, 0, 0);
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.y, wv.y, acc[c], 0, 0, 0);
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.z, wv.z, acc[c], 0, 0, 0);
+        acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv.w, wv.w, acc[c], 0, 0, 0);
       }
+    }
+  };
+  if (s0 < s1) {
+    int sb = s0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) gload(t, sb);
+    // whole groups, no branch inside: a skipped step would leave loads pending on a path back to the loop's head, and the compiler
+    // then drains the queue there on every trip.  The fences keep the scheduler from gathering the tiles' loads behind the last write
+    // (a drained queue once per group) or sinking them below the MFMAs.
+    for (; sb + GS <= s1; sb += GS) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        swrite(t);
+        gload(t, sb + GS);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      mac(GS);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (sb < s1) {                                             // the last 1 .. 3 steps
+#pragma unroll
+      for (int t = 0; t < NT; ++t) swrite(t);
+      mac(s1 - sb);
+    }
   }
+  __syncthreads();                                             // every wave is done with its image: the reduction takes the space
+  float (*red)[4][256] = reinterpret_cast<float (*)[4][256]>(lds);
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
+  for (int c = 0; c < 4; ++c)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave][ct][(4 * kk + r) * 16 + i] = acc[ct][r];
+    for (int r = 0; r < 4; ++r) red[wave][c][(4 * kk + r) * 16 + i] = acc[c][r];
   __syncthreads();
-  // 64 clips x 16 latents = 1024 sums of four wave partials; thread e handles 4 of them
+  // 64 clips x 16 latents = 1024 sums of four slice partials; thread e handles 4 of them
   for (int e = threadIdx.x; e < 1024; e += 256) {
     const int ct = e >> 8, rc = e & 255, row = rc >> 4, col = rc & 15;
     const int n = clip0 + 16 * ct + row;
@@ -358,6 +409,14 @@ int launch_btlnk_reduce(const float* partials, int P, size_t E, float* out, cons
   return check_launch("btlnk_bwd_reduce");
 }
 
+// the split-K partials [kBtlKS][B][16] (K % 16 == 0, L <= 16: checked by the callers)
+static int launch_btlnk_fwd_t(const float* U, const float* W, const float* slope, float* part, int B, int K, int L, hipStream_t stream) {
+  if (K > (1 << 23)) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_t: K=%d > 2^23 (32-bit lane offsets)", K);
+  const dim3 grid(ceil_div(B, 64), kBtlKS), block(256);
+  if (slope) return launch_lds<k_btlnk_fwd_t<true>>("btlnk_fwd_t", grid, block, kBtlFwdLds, stream, U, W, slope, part, B, K, L);
+  return launch_lds<k_btlnk_fwd_t<false>>("btlnk_fwd_t", grid, block, kBtlFwdLds, stream, U, W, slope, part, B, K, L);
+}
+
 // btlnk_wide.hip: 16 < L <= kBtlWideMax
 constexpr int kBtlWideMax = 512;
 
@@ -399,9 +458,8 @@ int coskad_btlnk_fwd_ws_f32(const float* U, const float* W, const float* bias, c
   if (K % 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_ws: K=%d must be a multiple of 16", K);
   if (ws_bytes < coskad_btlnk_fwd_ws_bytes(B)) return fail(COSKAD_ERR_WORKSPACE, "btlnk_fwd_ws: workspace too small");
   float* part = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(k_btlnk_fwd_t, dim3(ceil_div(B, 64), kBtlKS), dim3(256), 0, stream, U, W, slope, part, B, K, L);
   int rc;
-  if ((rc = check_launch("btlnk_fwd_t"))) return rc;
+  if ((rc = launch_btlnk_fwd_t(U, W, slope, part, B, K, L, stream))) return rc;
   hipLaunchKernelGGL(k_btlnk_fwd_sum, dim3(ceil_div(B * 16, 256)), dim3(256), 0, stream, part, bias, z, B, L, kBtlKS);
   return check_launch("btlnk_fwd_sum");
 }
@@ -417,8 +475,7 @@ int coskad_btlnk_fwd_parts_f32(const float* U, const float* W, const float* slop
   if (L > 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_parts: latent_dim=%d > 16 not supported", L);
   if (K % 16) return fail(COSKAD_ERR_SHAPE, "btlnk_fwd_parts: K=%d must be a multiple of 16", K);
   if (part_bytes < coskad_btlnk_fwd_ws_bytes(B)) return fail(COSKAD_ERR_WORKSPACE, "btlnk_fwd_parts: partials buffer too small");
-  hipLaunchKernelGGL(k_btlnk_fwd_t, dim3(ceil_div(B, 64), kBtlKS), dim3(256), 0, stream, U, W, slope, part, B, K, L);
-  return check_launch("btlnk_fwd_t");
+  return launch_btlnk_fwd_t(U, W, slope, part, B, K, L, stream);
 }
 
 size_t coskad_btlnk_bwd_ws_bytes(int B, int K, int L) {
