@@ -1,6 +1,7 @@
 """Float64 restatements of the stand-alone kernels the kernel-level tests compare with (test_gpu_wide_kernels.py,
-test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py, test_gpu_btlnk_kernels.py), in plain torch / numpy on the
-CPU.  Every function takes
+test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py, test_gpu_btlnk_kernels.py, test_gpu_decoder_kernels.py),
+in plain torch / numpy on the CPU (the PowerSpherical restatement at the end, shared by test_gpu_ae_step.py and
+test_gpu_ae_wide_latent.py, builds on the package's torch distribution class, not on a kernel).  Every function takes
 the float32 inputs converted to double, composes the forward only -- gradients come from torch autograd on that forward, never from a
 hand-written backward -- and never calls the library.  test_kernel_refs_host.py holds them against torch.nn / torch.optim before a
 device sees them.  The one-class heads' section also restates the kernels' Poincare sequences, backward included, over a running-error
@@ -728,3 +729,203 @@ def wide_dw_chunks(B, K, L):
 
 def wide_dx_blocks(B, K):
     return ceil_div(K, 128) * ceil_div(B, 128)
+
+
+# ---- the decoder models' stand-alone kernels (test_gpu_decoder_kernels.py) ----------------------------------------------------------------
+# rev_btlnk at latent 8 / 16 (csrc/rev_btlnk.hip)
+
+def rev_btlnk(z, W, b):
+    """H = z W^T + b on z [B, L], W [N, L], b [N] or None (nn.Linear(latent -> hidden T V), ae.py:223-227)"""
+    H = z @ W.T
+    return H if b is None else H + b
+
+
+def rev_slices(B, N):
+    """csrc/rev_btlnk.hip rb::slices: clip slices of the backward's (column blocks) x (slices) grids"""
+    if B < 16:
+        return 1
+    s = ceil_div(1024, ceil_div(N // 4, 256))
+    s = min(max(s, 16), 64, B // 16)
+    return max(s, 1)
+
+
+def rev_fwd_slices(B, N):
+    """coskad_rev_btlnk_fwd_f32's three branches"""
+    return 1 if B < 64 else (4 if B < 1024 else rev_slices(B, N))
+
+
+def rev_inputs(B, N, L, seed):
+    """float32 inputs of the rev_btlnk tests: z ~ N(0, 1) with a per-clip magnitude from BTLNK_MAGS, W ~ N(0, 1 / L) with a per-column
+    offset (a zero-mean W would hide a dropped clip in db less than in dW), bias, dH ~ N(0, 1), a prior for dz"""
+    g = torch.Generator().manual_seed(seed)
+    mags = torch.tensor(BTLNK_MAGS)[torch.randint(0, len(BTLNK_MAGS), (B, 1), generator=g)]
+    d = dict(z=(torch.randn(B, L, generator=g) * mags).contiguous(), W=torch.randn(N, L, generator=g) * L ** -0.5 + 0.1,
+             b=torch.randn(N, generator=g), dH=torch.randn(B, N, generator=g) + 0.25, dz0=torch.randn(B, L, generator=g))
+    for k, v in d.items():
+        assert not bool(((v != 0) & (v.abs() < F32_TINY)).any()), f"subnormal in {k}"
+    return d
+
+
+# the folded first decoder layer's statistics algebra (csrc/lowrank_fold.hip, coskad_amd/lowrank.py)
+
+FOLD_K = 9                # latent 8 + the constant image
+FOLD_ROUND = 256          # positions per round (kThreads); MAXPOS = 2 rounds
+
+
+def fold(X, G, gammas, betas, eps, n_pos):
+    """The fold algebra in double.  X [2, 9, Co, TV] (branch r's rank-9 tensor), G [9, 9] or [Co, 9, 9] (a copy per channel: its
+    gradient is then the per-channel share), gammas / betas: two [Co] tensors, eps: two floats.
+        xbar[r, l, c] = sum_p X,   xx[r, c, l, m] = sum_p X_l X_m,
+        mean = sum_l G[l, 8] xbar_l / n_pos,   E2 = sum_lm G[l, m] xx[l, m] / n_pos,   var = max(E2 - mean^2, 0),
+        a = gamma / sqrt(var + eps),   Mw[c, p, l] = sum_r a_r X_rl (l < 8),   Mb[c, p] = sum_r a_r X_r8 + sum_r (beta_r - a_r mean_r).
+    The clamp is there for rounding only (the true variance is never negative) and the operation folded, nn.BatchNorm2d, differentiates
+    through its variance at 0 too: the clamp passes the gradient straight through.  -> dict"""
+    Co = X.shape[2]
+    Gc = G if G.dim() == 3 else G[None].expand(Co, FOLD_K, FOLD_K)
+    xbar = X.sum(-1)                                                # [2, 9, Co]
+    xx = torch.einsum("rlcp,rmcp->rclm", X, X)                      # [2, Co, 9, 9]
+    mean = torch.einsum("cl,rlc->rc", Gc[:, :, FOLD_K - 1], xbar) / n_pos
+    E2 = torch.einsum("clm,rclm->rc", Gc, xx) / n_pos
+    raw = E2 - mean * mean
+    var = raw + (raw.clamp(min=0.0) - raw).detach()
+    epsv = torch.tensor([f32(eps[0]), f32(eps[1])], dtype=torch.float64)[:, None]
+    istd = 1.0 / torch.sqrt(var + epsv)
+    gam, bet = torch.stack(list(gammas)), torch.stack(list(betas))
+    a = gam * istd
+    M = torch.einsum("rc,rlcp->cpl", a, X)
+    Mb = M[:, :, FOLD_K - 1] + (bet - a * mean).sum(0)[:, None]
+    return dict(xbar=xbar, xx=xx, mean=mean, E2=E2, var=var, istd=istd, a=a, Mw=M[:, :, :FOLD_K - 1], Mb=Mb)
+
+
+def fold_running(mean, var, n_pos, cbias, rmean, rvar, momentum):
+    """nn.BatchNorm2d's update of one branch behind a conv with bias `cbias` (None: none): the bias shifts the mean only"""
+    mom = f32(momentum)
+    unb = n_pos / (n_pos - 1.0) if n_pos > 1 else 1.0
+    mb = mean if cbias is None else mean + cbias
+    return (1.0 - mom) * rmean + mom * mb, (1.0 - mom) * rvar + mom * var * unb
+
+
+def fold_inputs(Co, TV, n, seed):
+    """float32 / float64 inputs of the fold tests: latents zt = [z, 1] of n clips and G = zt^T zt (symmetric bit for bit), n_pos = n TV;
+    X with a per-image scale; channel 1 (where there is one) has branch 0 all zero -- variance exactly 0 -- and the last channel of
+    Co >= 3 a constant image 10^3 times the others' spread."""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(n, FOLD_K - 1, generator=g, dtype=torch.float64) * 0.7 + 0.2
+    zt = torch.cat([z, torch.ones(n, 1, dtype=torch.float64)], 1)
+    G = zt.T @ zt
+    G = 0.5 * (G + G.T)
+    X = torch.randn(2, FOLD_K, Co, TV, generator=g) * torch.linspace(0.3, 1.5, FOLD_K)[None, :, None, None]
+    if Co >= 2:
+        X[0, :, 1] = 0.0
+    if Co >= 3:
+        X[:, FOLD_K - 1, Co - 1] = X[:, FOLD_K - 1, Co - 1] * 0.5 + 2000.0       # (the expanded layer's spread there is about 2)
+    d = dict(X=X.contiguous(), G=G, zt=zt, n_pos=float(n * TV))
+    for r in range(2):
+        d[f"gamma{r}"] = torch.rand(Co, generator=g) + 0.5
+        d[f"beta{r}"] = torch.randn(Co, generator=g)
+        d[f"cbias{r}"] = torch.randn(Co, generator=g)
+        d[f"rmean{r}"] = torch.randn(Co, generator=g)
+        d[f"rvar{r}"] = torch.rand(Co, generator=g) + 0.5
+    d["dMw"] = torch.randn(Co * TV, FOLD_K - 1, generator=g)
+    d["dMb"] = torch.randn(Co * TV, generator=g) + 0.3
+    return d
+
+
+# the `mlp` projector's tail (csrc/mlp_head.hip)
+
+MLP_HP = 16               # hidden, out <= 16: the 64-rows-per-block kernels
+MLP_RB = 64
+
+
+def mlp_fast(H, L):
+    return H <= MLP_HP and L <= MLP_HP
+
+
+def mlp_head(y, gamma, beta, W2, b2, eps, training, running_mean=None, running_var=None):
+    """z = W2 relu(BatchNorm1d(y)) + b2 in double on y [B, H]: batch statistics (biased variance, differentiated through) in training
+    mode, the running ones otherwise.  -> dict z, y2, xh, mean, var, inv"""
+    if training:
+        mean = y.mean(0)
+        var = ((y - mean) ** 2).mean(0)
+    else:
+        mean, var = running_mean, running_var
+    inv = 1.0 / torch.sqrt(var + f32(eps))
+    xh = (y - mean) * inv
+    y2 = xh * gamma + beta
+    z = torch.relu(y2) @ W2.T
+    if b2 is not None:
+        z = z + b2
+    return dict(z=z, y2=y2, xh=xh, mean=mean, var=var, inv=inv)
+
+
+MLP_PLANTS = 5            # from this many features on, features 1 .. 4 are planted
+
+
+def mlp_inputs(B, H, L, seed):
+    """float32 inputs of the mlp_head tests.  y ~ N(offset_k, scale_k^2) per feature; with H >= 5: feature 1 has gamma = beta = 0 (gate
+    closed, exactly), feature 2 gamma = 0, beta = 0.75 (gate open everywhere), feature 3 is the constant 1.5 (sums of 1.5 and 2.25 are
+    exact in double at these B: variance exactly 0), feature 4 has a mean 10^3 times its deviation."""
+    g = torch.Generator().manual_seed(seed)
+    off = torch.linspace(-1.0, 2.0, H) if H > 1 else torch.tensor([0.4])
+    sc = torch.linspace(0.5, 2.0, H) if H > 1 else torch.tensor([1.3])
+    y = torch.randn(B, H, generator=g) * sc + off
+    gamma, beta = torch.rand(H, generator=g) + 0.5, torch.randn(H, generator=g) * 0.5
+    if H >= MLP_PLANTS:
+        gamma[1], beta[1] = 0.0, 0.0
+        gamma[2], beta[2] = 0.0, 0.75
+        y[:, 3] = 1.5
+        y[:, 4] = torch.randn(B, generator=g) * 0.25 + 250.0
+    d = dict(y=y.contiguous(), gamma=gamma, beta=beta, W2=torch.randn(L, H, generator=g) * H ** -0.5, b2=torch.randn(L, generator=g),
+             dz=torch.randn(B, L, generator=g) + 0.2, rmean=torch.randn(H, generator=g), rvar=torch.rand(H, generator=g) + 0.5)
+    for k, v in d.items():
+        assert not bool(((v != 0) & (v.abs() < F32_TINY)).any()), f"subnormal in {k}"
+    return d
+
+
+# ---- the PowerSpherical head in float64 (csrc/vae_head.hip, narrow and wide) --------------------------------------------------------------
+
+class _GivenDirichlet(torch.autograd.Function):
+    """torch.distributions.dirichlet._Dirichlet with the draw handed in: forward returns x, backward is _Dirichlet_backward."""
+
+    @staticmethod
+    def forward(ctx, conc, x):
+        ctx.save_for_backward(x, conc)
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, go):
+        x, conc = ctx.saved_tensors
+        total = conc.sum(-1, True).expand_as(conc)
+        grad = torch._dirichlet_grad(x, conc, total)
+        return grad * (go - (x * go).sum(-1, True)), None
+
+
+def _uniform_entropy_f64(L):
+    """HypersphericalUniform(L - 1).entropy() as a Python float: the class rounds it to float32 (torch.tensor of a float), 3e-5 at
+    L = 512 -- more than the KL's tolerance"""
+    return math.log(2) + (L / 2) * math.log(math.pi) - math.lgamma(L / 2)
+
+
+def _ps_restatement_f64(H2, x, eps, w, w_kl, w_exp):
+    """coskad_amd/models/sts/vae.py's head (_finish_heads, PowerSpherical.rsample / entropy, kl_ps_uniform) in float64 on the CPU, on
+    the given draws -> (z, kl, 1 / kappa, gradient w.r.t. H2)"""
+    import torch.nn.functional as F
+    from coskad_amd.models.sts.vae import PowerSpherical
+    L = H2.shape[1] - 1
+    Hr = H2.double().cpu().clone().requires_grad_(True)
+    x, eps, w = x.double().cpu(), eps.double().cpu(), w.double().cpu()
+    Z_mean = Hr[:, :L] / torch.norm(Hr[:, :L], dim=-1, keepdim=True)
+    Z_var = F.softplus(Hr[:, L:]) + 1
+    q = PowerSpherical(loc=Z_mean, scale=Z_var.squeeze(-1))
+    zb = _GivenDirichlet.apply(torch.stack([q.alpha, q.beta], -1), x)[..., 0]
+    t = (2 * zb - 1).unsqueeze(-1)
+    v = F.normalize(eps, dim=-1)
+    y = torch.cat([t, torch.sqrt(torch.clamp(1 - t * t, min=0)) * v], -1)
+    e1 = torch.zeros_like(Z_mean)
+    e1[..., 0] = 1
+    u = F.normalize(e1 - Z_mean, dim=-1)
+    z = y - 2 * (y * u).sum(-1, keepdim=True) * u
+    kl = -q.entropy() + _uniform_entropy_f64(L)
+    ik = (1 / Z_var).squeeze(-1)
+    ((z * w).sum() + w_kl * kl.sum() + w_exp * ik.sum()).backward()
+    return z.detach().numpy(), kl.detach().numpy(), ik.detach().numpy(), Hr.grad.numpy()

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import state_from
+from kernel_refs import _GivenDirichlet, _ps_restatement_f64          # the PowerSpherical head in float64, shared with test_gpu_ae_wide_latent.py
 
 pytestmark = pytest.mark.gpu
 
@@ -169,20 +170,51 @@ def test_flat_autoencoder_step_default_widths_vs_oracle():
             np.testing.assert_allclose(sd[k].cpu().numpy(), v.numpy(), rtol=1e-4, atol=1e-5, err_msg=k)
 
 
-class _GivenDirichlet(torch.autograd.Function):
-    """torch.distributions.dirichlet._Dirichlet with the draw handed in: forward returns x, backward is _Dirichlet_backward."""
-
-    @staticmethod
-    def forward(ctx, conc, x):
-        ctx.save_for_backward(x, conc)
-        return x.clone()
-
-    @staticmethod
-    def backward(ctx, go):
-        x, conc = ctx.saved_tensors
-        total = conc.sum(-1, True).expand_as(conc)
-        grad = torch._dirichlet_grad(x, conc, total)
-        return grad * (go - (x * go).sum(-1, True)), None
+@pytest.mark.parametrize("L", [2, 3, 8, 16])
+def test_narrow_power_spherical_head_vs_float64(L):
+    """The thread-per-clip head (csrc/vae_head.hip, L <= 16) against kernel_refs._ps_restatement_f64, as the wave-per-clip one is in
+    test_gpu_ae_wide_latent.py and with its tolerances: the float32 torch restatement below runs the same device math library and loses
+    digits in lgamma itself.  B = 131 leaves the block ragged; the concentration column sweeps the softplus and the identity region;
+    rows 0 / 1 sit on the poles; inputs and outputs are column views of wider tensors, guard columns keep a sentinel; the same seed
+    again repeats every output bit for bit."""
+    import torch.nn.functional as F
+    from coskad_amd import ops
+    SENT = -777.0
+    g = torch.Generator().manual_seed(5 + L)
+    B = 131
+    H2 = torch.randn(B, L + 1, generator=g)
+    H2[:, L] = torch.linspace(-6, 25, B)
+    H2[0, :L] = 0.0; H2[0, 0] = 3.0                       # mu = e1
+    H2[1, :L] = 0.0; H2[1, 0] = -2.0                      # mu = -e1
+    w = torch.randn(B, L, generator=g)
+    w_kl, w_exp = 0.3 / B, 0.2 / B
+    H2d, wd = H2.cuda(), w.cuda()
+    torch.manual_seed(40 + L)
+    z, kl, ik, saved = ops.ps_head_forward(H2d[:, :L], H2d[:, L:L + 1])
+    out = torch.full((B, L + 3), SENT, device="cuda")      # guard columns 0 and L + 2 around the [B, L + 1] gradient
+    ops.ps_head_backward(saved, wd, w_kl, w_exp, out[:, 1:L + 1], out[:, L + 1:L + 2])
+    assert bool((out[:, 0] == SENT).all()) and bool((out[:, L + 2] == SENT).all())
+    x, eps = saved[6], saved[7]
+    assert eps.shape == (B, L - 1)
+    z_ref, kl_ref, ik_ref, g_ref = _ps_restatement_f64(H2, x, eps, w, w_kl, w_exp)
+    np.testing.assert_allclose(saved[2].cpu().numpy(), F.normalize(H2[:, :L].double(), dim=-1).numpy(), rtol=1e-5, atol=2e-7)
+    np.testing.assert_allclose(z.cpu().numpy(), z_ref, rtol=1e-5, atol=2e-6)
+    print("L", L, "max |kl - ref|", float(np.abs(kl.cpu().numpy() - kl_ref).max()), "kl range", float(kl_ref.min()), float(kl_ref.max()))
+    np.testing.assert_allclose(kl.cpu().numpy(), kl_ref, rtol=2e-4, atol=2e-5)
+    np.testing.assert_allclose(ik.cpu().numpy(), ik_ref, rtol=1e-6)
+    got = out[:, 1:L + 2].cpu().numpy()
+    ok = np.isfinite(g_ref).all(axis=1)                    # (mu = e1 exactly: the restatement's own gradient is 0 / 0 there)
+    assert ok.sum() >= B - 2
+    print("L", L, "rows kept", int(ok.sum()), "max |grad - ref|", float(np.abs(got[ok] - g_ref[ok]).max()),
+          "max |ref|", float(np.abs(g_ref[ok]).max()))
+    np.testing.assert_allclose(got[ok], g_ref[ok], rtol=2e-3, atol=2e-6 + 2e-4 * np.abs(g_ref[ok]).max())
+    torch.manual_seed(40 + L)
+    z2, kl2, ik2, saved2 = ops.ps_head_forward(H2d[:, :L], H2d[:, L:L + 1])
+    assert torch.equal(saved2[6], x) and torch.equal(saved2[7], eps)
+    out2 = torch.full((B, L + 3), SENT, device="cuda")
+    ops.ps_head_backward(saved2, wd, w_kl, w_exp, out2[:, 1:L + 1], out2[:, L + 1:L + 2])
+    assert torch.equal(z2, z) and torch.equal(kl2, kl) and torch.equal(ik2, ik)
+    assert torch.equal(out2.view(torch.int32), out.view(torch.int32))     # (bit patterns: the pole row may hold a NaN)
 
 
 @pytest.mark.parametrize("L", [2, 8, 16])

@@ -8,59 +8,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_refs import _GivenDirichlet, _ps_restatement_f64, _uniform_entropy_f64          # noqa: F401  (the PowerSpherical head in float64)
+
 pytestmark = pytest.mark.gpu
 
 SENT = -777.0
 
 
 # ---- a. the PowerSpherical head ---------------------------------------------------------------------------------------------------------
-class _GivenDirichlet(torch.autograd.Function):
-    """torch.distributions.dirichlet._Dirichlet with the draw handed in: forward returns x, backward is _Dirichlet_backward."""
-
-    @staticmethod
-    def forward(ctx, conc, x):
-        ctx.save_for_backward(x, conc)
-        return x.clone()
-
-    @staticmethod
-    def backward(ctx, go):
-        x, conc = ctx.saved_tensors
-        total = conc.sum(-1, True).expand_as(conc)
-        grad = torch._dirichlet_grad(x, conc, total)
-        return grad * (go - (x * go).sum(-1, True)), None
-
-
-def _uniform_entropy_f64(L):
-    """HypersphericalUniform(L - 1).entropy() as a Python float: the class rounds it to float32 (torch.tensor of a float), 3e-5 at
-    L = 512 -- more than the KL's tolerance"""
-    import math
-    return math.log(2) + (L / 2) * math.log(math.pi) - math.lgamma(L / 2)
-
-
-def _ps_restatement_f64(H2, x, eps, w, w_kl, w_exp):
-    """coskad_amd/models/sts/vae.py's head (_finish_heads, PowerSpherical.rsample / entropy, kl_ps_uniform) in float64 on the CPU, on
-    the given draws -> (z, kl, 1 / kappa, gradient w.r.t. H2)"""
-    from coskad_amd.models.sts.vae import PowerSpherical
-    L = H2.shape[1] - 1
-    Hr = H2.double().cpu().clone().requires_grad_(True)
-    x, eps, w = x.double().cpu(), eps.double().cpu(), w.double().cpu()
-    Z_mean = Hr[:, :L] / torch.norm(Hr[:, :L], dim=-1, keepdim=True)
-    Z_var = F.softplus(Hr[:, L:]) + 1
-    q = PowerSpherical(loc=Z_mean, scale=Z_var.squeeze(-1))
-    zb = _GivenDirichlet.apply(torch.stack([q.alpha, q.beta], -1), x)[..., 0]
-    t = (2 * zb - 1).unsqueeze(-1)
-    v = F.normalize(eps, dim=-1)
-    y = torch.cat([t, torch.sqrt(torch.clamp(1 - t * t, min=0)) * v], -1)
-    e1 = torch.zeros_like(Z_mean)
-    e1[..., 0] = 1
-    u = F.normalize(e1 - Z_mean, dim=-1)
-    z = y - 2 * (y * u).sum(-1, keepdim=True) * u
-    kl = -q.entropy() + _uniform_entropy_f64(L)
-    ik = (1 / Z_var).squeeze(-1)
-    ((z * w).sum() + w_kl * kl.sum() + w_exp * ik.sum()).backward()
-    return z.detach().numpy(), kl.detach().numpy(), ik.detach().numpy(), Hr.grad.numpy()
-
-
 @pytest.mark.parametrize("L", [17, 65, 200, 512])
 def test_wide_power_spherical_head_vs_float64(L):
     """B = 131 leaves the last block three clips; the concentration column sweeps the softplus and the identity region; rows 0 / 1 sit

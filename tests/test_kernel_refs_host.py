@@ -1,6 +1,7 @@
 """The float64 references of kernel_refs.py against torch.nn / torch.optim on the CPU, before a device sees them: what the GPU
-kernel tests (test_gpu_wide_kernels.py, test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py) compare with is
-shown right here; the running-error arithmetic behind the Poincare head's bounds against the oracle and numpy float32.  Also
+kernel tests (test_gpu_wide_kernels.py, test_gpu_narrow_conv.py, test_gpu_flat_kernels.py, test_gpu_head_kernels.py,
+test_gpu_btlnk_kernels.py, test_gpu_decoder_kernels.py) compare with is shown right here, and the launch-plan restatements are held
+against the library's host-only size queries; the running-error arithmetic behind the Poincare head's bounds against the oracle and numpy float32.  Also
 the Python twin of the dropout hash (its keep rate; the numpy form against the integer form) and the share of elements the
 apply / backward test leaves out at the PReLU kink, from the reference alone.  No kernel runs."""
 import numpy as np
@@ -426,3 +427,238 @@ def test_btlnk_shapes_meet_the_edges_they_are_listed_for():
     assert {s[0] for s in BK.WIDE_SHAPES} >= {127, 129} and {s[1] for s in BK.WIDE_SHAPES} >= {100, 129, 272}       # both sides of 128
     assert R.wide_dw_chunk(1040, 36, 40) == 32 and all(R.wide_dw_chunk(*s) == 16 for s in BK.WIDE_SHAPES[:-1])
     assert R.wide_dw_chunks(300, 272, 64) == 19 > 8 and R.wide_dx_blocks(300, 272) == 9
+
+
+# ---- the decoder models' stand-alone kernels: rev_btlnk at latent 8 / 16, the fold, the mlp head ----------------------------------------
+
+@pytest.mark.parametrize("bias", [True, False])
+def test_rev_btlnk_is_linear(bias):
+    """kernel_refs.rev_btlnk == F.linear in double; dz = dH W, dW = dH^T z, db = sum_b dH are autograd's"""
+    d = R.rev_inputs(19, 36, 8, seed=2)
+    z, Wm, b, dH = (d[k].double().clone().requires_grad_(True) for k in ("z", "W", "b", "dH"))
+    H = R.rev_btlnk(z, Wm, b if bias else None)
+    _close(H, F.linear(z, Wm, b if bias else None), "H")
+    gz, gW = torch.autograd.grad(H, [z, Wm], dH.detach(), retain_graph=True)
+    _close(gz, dH.detach() @ Wm.detach(), "dz"); _close(gW, dH.detach().T @ z.detach(), "dW")
+    if bias:
+        (gb,) = torch.autograd.grad(H, [b], dH.detach())
+        _close(gb, dH.detach().sum(0), "db")
+
+
+def test_rev_plan_restatement_matches_the_library():
+    """kernel_refs.rev_slices against coskad_rev_btlnk_ws_floats(B, N, L) / (N (L + 1)) (a pure-host query) at every shape of
+    test_gpu_decoder_kernels.py and over a grid of others"""
+    import test_gpu_decoder_kernels as DK
+    lib = _library()
+    shapes = [(B, N, L) for B in DK.REV_BS for N in DK.REV_NS for L in DK.REV_LS] + [DK.REV_PROD]
+    shapes += [(B, N, L) for B in (1, 15, 16, 31, 32, 255, 256, 257, 450, 1023, 1024, 4096, 5000) for N in (4, 1024, 1028, 13056, 19200, 38400,
+                                                                                                        65536, 131072) for L in (8, 16)]
+    for B, N, L in shapes:
+        S = R.rev_slices(B, N)
+        assert lib.coskad_rev_btlnk_ws_floats(B, N, L) == S * N * (L + 1), (B, N, L)
+        assert 1 <= S <= 64 and (B < 16 or S <= B // 16)
+        assert R.rev_fwd_slices(B, N) in (1, 4, S)
+
+
+def test_rev_shapes_meet_the_edges_they_are_listed_for():
+    """every N and B of test_gpu_decoder_kernels.py's rev_btlnk section, from the plan restatement alone"""
+    import test_gpu_decoder_kernels as DK
+    cd = R.ceil_div
+    # N: one thread; under one column block; a second block of one thread (the others return at n >= N) and a second k_rev_dz stride
+    # of one float4; the folded first layer's 32 x 204 columns
+    assert DK.REV_NS == (4, 816, 1028, 6528) and all(N % 4 == 0 for N in DK.REV_NS)
+    assert 4 // 4 == 1 and 816 // 4 < 256 and cd(1028 // 4, 256) == 2 and 1028 // 4 - 256 == 1 and 1028 - 1024 == 4 and 6528 == 32 * 204
+    assert [cd(N, 1024) for N in DK.REV_NS] == [1, 1, 2, 7]
+    # B: k_rev_dz's CB = 4 (L = 8) and CB = 2 (L = 16) with every remainder
+    assert {B % 4 for B in DK.REV_BS} == {0, 1, 2, 3} and {B % 2 for B in DK.REV_BS} == {0, 1}
+    for N in DK.REV_NS:
+        sl = [R.rev_slices(B, N) for B in DK.REV_BS]
+        assert sl == [1, 1, 1, 1, 1, 1, 1, 2, 3, 4, 4, 63, 64, 64], (N, sl)
+        S, chunk = 64, cd(1030, 64)
+        assert sum(1 for y in range(S) if y * chunk >= 1030) == 3                        # wholly empty trailing slices
+        assert [R.rev_fwd_slices(B, N) for B in (63, 64, 65, 1023, 1024, 1030)] == [1, 4, 4, 4, 64, 64]
+    assert {1, 2, 3, 5, 15, 16, 17, 33, 63, 64, 65, 1023, 1024, 1030} == set(DK.REV_BS)
+    B, N, L = DK.REV_PROD
+    assert (B, N, L) == (450, 38400, 16) and R.rev_slices(B, N) == 27 and 16 < 27 < min(64, B // 16) and R.rev_fwd_slices(B, N) == 4
+
+
+def _fold_real_op(d, Co, TV, eps, moms, X, with_bias):
+    """the operation the fold stands for: the latents expanded through X into the layer's two branches, a conv bias on each, nn.BatchNorm2d
+    in training mode in double on each, added -> (out [n, Co, TV], the modules)"""
+    zt = d["zt"]
+    out, bns = 0.0, []
+    for r in range(2):
+        bn = torch.nn.BatchNorm2d(Co, eps=R.f32(eps[r]), momentum=R.f32(moms[r])).double().train()
+        with torch.no_grad():
+            bn.weight.copy_(d[f"gamma{r}"]); bn.bias.copy_(d[f"beta{r}"])
+            bn.running_mean.copy_(d[f"rmean{r}"]); bn.running_var.copy_(d[f"rvar{r}"])
+        Hr = torch.einsum("nl,lcp->ncp", zt, X[r])
+        if with_bias[r]:
+            Hr = Hr + d[f"cbias{r}"].double()[None, :, None]
+        out = out + bn(Hr[..., None])[..., 0]
+        bns.append(bn)
+    return out, bns
+
+
+@pytest.mark.parametrize("n,Co,TV,with_bias", [(37, 2, 20, (True, True)), (1, 2, 7, (False, True)), (5, 1, 1, (True, False)),
+                                               (37, 3, 20, (True, True))])
+def test_fold_is_batchnorm_of_the_expanded_layer(n, Co, TV, with_bias):
+    """kernel_refs.fold against the real operation in double: with G = zt^T zt and n_pos = n T V, zt [Mw | Mb] equals the sum of the two
+    train-mode BatchNorm2d outputs of the expanded branches to 1e-12 of its scale, the running statistics equal the modules' (conv bias
+    included, unbiased variance, per-branch momentum and eps), and the gradients with respect to X, gamma and beta through the
+    expansion equal autograd's on the restatement.  Co = 2 has the all-zero branch (variance exactly 0 on both sides).  Co = 3 adds the
+    channel whose constant image is 10^3 times its spread: there E2 - mean^2 cancels six digits in double itself, so that one case is
+    held to 1e-12 times (E2 + mean^2) / (var + eps), the cancellation's own amplification."""
+    eps, moms = (1e-5, 1e-3), (0.1, 0.3)
+    d = R.fold_inputs(Co, TV, n, seed=7 * n + Co + TV)
+    g = torch.Generator().manual_seed(n)
+    dOut = torch.randn(n, Co, TV, generator=g, dtype=torch.float64)
+    leaf = lambda t: t.double().clone().requires_grad_(True)
+    res = []
+    for real in (True, False):
+        X = leaf(d["X"])
+        gam, bet = [leaf(d["gamma0"]), leaf(d["gamma1"])], [leaf(d["beta0"]), leaf(d["beta1"])]
+        if real:
+            out, bns = _fold_real_op(d, Co, TV, eps, moms, X, with_bias)
+            gam, bet = [bn.weight for bn in bns], [bn.bias for bn in bns]
+        else:
+            f = R.fold(X, d["G"], gam, bet, eps, d["n_pos"])
+            out = torch.einsum("nl,cpl->ncp", d["zt"], torch.cat([f["Mw"], f["Mb"][..., None]], -1))
+        res.append((out,) + torch.autograd.grad(out, [X] + gam + bet, dOut))
+    f = {k: v.detach() for k, v in f.items()}
+    amp = 1.0
+    if Co >= 3:
+        amp = float(((f["E2"] + f["mean"] ** 2) / (f["var"] + torch.tensor(eps, dtype=torch.float64)[:, None])).max())
+        assert amp > 1e5
+    for k, (a, b) in enumerate(zip(*res)):
+        a, b = a.detach(), b.detach()
+        tol = 1e-12 * amp * max(1.0, float(b.abs().max()))
+        assert float((a - b).abs().max()) <= tol, (k, float((a - b).abs().max()), tol)
+    if Co >= 2:
+        assert float(f["var"][0, 1]) == 0.0 and float(f["istd"][0, 1]) == pytest.approx(1 / np.sqrt(R.f32(eps[0])), rel=1e-15)
+    for r in range(2):
+        cb = d[f"cbias{r}"].double() if with_bias[r] else None
+        rm, rv = R.fold_running(f["mean"][r].detach(), f["var"][r].detach(), d["n_pos"], cb, d[f"rmean{r}"].double(), d[f"rvar{r}"].double(),
+                                moms[r])
+        for got, want in ((rm, bns[r].running_mean), (rv, bns[r].running_var)):
+            assert float((got - want).abs().max()) <= 1e-12 * amp * max(1.0, float(want.abs().max())), r
+    # the per-channel copy of G: its gradient is the channel's share, and the shares add up to the gradient of the one G
+    X = d["X"].double()
+    gam, bet = [d["gamma0"].double(), d["gamma1"].double()], [d["beta0"].double(), d["beta1"].double()]
+    dMw, dMb = d["dMw"].double(), d["dMb"].double()
+    grads = []
+    for per_channel in (True, False):
+        Gl = (d["G"][None].expand(Co, 9, 9) if per_channel else d["G"]).clone().requires_grad_(True)
+        f2 = R.fold(X, Gl, gam, bet, eps, d["n_pos"])
+        loss = (f2["Mw"].reshape(Co * TV, 8) * dMw).sum() + (f2["Mb"].reshape(Co * TV) * dMb).sum()
+        grads.append(torch.autograd.grad(loss, Gl)[0])
+    assert float((grads[0].sum(0) - grads[1]).abs().max()) <= 1e-12 * amp * max(1.0, float(grads[1].abs().max()))
+
+
+def test_fold_shapes_meet_the_edges_they_are_listed_for():
+    """T V of test_gpu_decoder_kernels.py against the position rounds of k_fold_fwd / k_fold_bwd (256 threads, MAXPOS = 2), the
+    library's own shape query on both sides of its limit, and n_pos = 1"""
+    import test_gpu_decoder_kernels as DK
+    lib = _library()
+    rnd = R.FOLD_ROUND
+    assert DK.FOLD_TVS == (1, 63, 136, 204, 256, 257, 300, 408, 512) and DK.FOLD_COS == (1, 3, 32) and DK.FOLD_NS == (1, 37)
+    first = [min(TV, rnd) for TV in DK.FOLD_TVS]
+    second = [max(TV - rnd, 0) for TV in DK.FOLD_TVS]
+    assert first == [1, 63, 136, 204, 256, 256, 256, 256, 256] and second == [0, 0, 0, 0, 0, 1, 44, 152, 256]
+    for TV in range(1, 2 * rnd + 40):
+        assert lib.coskad_lowrank_fold_ok(R.FOLD_K - 1, TV) == int(TV <= 2 * rnd)
+    assert min(DK.FOLD_NS) * min(DK.FOLD_TVS) == 1
+    assert DK.FOLD_MOM[0] != DK.FOLD_MOM[1] and DK.FOLD_EPS[0] != DK.FOLD_EPS[1]
+    assert {c["cbias"] for c in DK.FOLD_CFGS} == {(True, True), (False, True), (True, False), (False, False)}
+    assert {c["run"] for c in DK.FOLD_CFGS} == {(True, True), (False, True), (True, False), (False, False)}
+
+
+@pytest.mark.parametrize("bias", [True, False])
+@pytest.mark.parametrize("training", [True, False])
+def test_mlp_head_is_batchnorm1d_relu_linear(training, bias):
+    """kernel_refs.mlp_head == nn.BatchNorm1d -> nn.ReLU -> nn.Linear in double: z, every gradient, the batch statistics and the
+    running update (unbiased variance) in train mode; the running statistics in eval mode.  The inputs carry the planted features."""
+    B, H, L, eps, mom = 37, 7, 5, 1e-5, 0.1
+    d = R.mlp_inputs(B, H, L, seed=3)
+    bn = torch.nn.BatchNorm1d(H, eps=R.f32(eps), momentum=R.f32(mom)).double()
+    lin = torch.nn.Linear(H, L, bias=bias).double()
+    with torch.no_grad():
+        bn.weight.copy_(d["gamma"]); bn.bias.copy_(d["beta"]); bn.running_mean.copy_(d["rmean"]); bn.running_var.copy_(d["rvar"])
+        lin.weight.copy_(d["W2"])
+        if bias:
+            lin.bias.copy_(d["b2"])
+    bn.train(training)
+    dz = d["dz"].double()
+    y = d["y"].double().clone().requires_grad_(True)
+    want = lin(torch.relu(bn(y)))
+    wp = [y, bn.weight, bn.bias, lin.weight] + ([lin.bias] if bias else [])
+    wg = torch.autograd.grad(want, wp, dz)
+    leaf = lambda t: t.double().clone().requires_grad_(True)
+    y2, gam, bet, W2 = leaf(d["y"]), leaf(d["gamma"]), leaf(d["beta"]), leaf(d["W2"])
+    b2 = leaf(d["b2"]) if bias else None
+    f = R.mlp_head(y2, gam, bet, W2, b2, eps, training, d["rmean"].double(), d["rvar"].double())
+    gg = torch.autograd.grad(f["z"], [y2, gam, bet, W2] + ([b2] if bias else []), dz)
+    _close(f["z"], want, "z")
+    for k, (a, b) in enumerate(zip(gg, wg)):
+        _close(a.reshape(-1), b.reshape(-1), f"grad {k}")
+    if training:
+        m = R.f32(mom)
+        _close((1 - m) * d["rmean"].double() + m * f["mean"].detach(), bn.running_mean, "running_mean")
+        _close((1 - m) * d["rvar"].double() + m * f["var"].detach() * B / (B - 1.0), bn.running_var, "running_var")
+        assert float(f["var"].detach()[3]) == 0.0                                          # the constant column
+    else:
+        assert torch.equal(bn.running_mean, d["rmean"].double()) and torch.equal(f["mean"], d["rmean"].double())
+    assert float(gam.detach()[1]) == 0.0 == float(bet.detach()[1]) and float(gg[0][:, 1].abs().max()) == 0.0 == float(gg[1][1])
+    assert float(gam.detach()[2]) == 0.0 < float(bet.detach()[2]) and float(gg[0][:, 2].abs().max()) == 0.0 != float(gg[1][2])
+
+
+def test_mlp_shapes_meet_the_edges_they_are_listed_for():
+    """the shapes of test_gpu_decoder_kernels.py's mlp_head section: which kernel set each takes, the blocks of 64 rows and sum_parts'
+    unroll of eight, and the workspace the library reports (stat / red: 2 H + 2 floats and the fast set's per-block partials)"""
+    import test_gpu_decoder_kernels as DK
+    lib = _library()
+    cd = R.ceil_div
+    assert DK.MLP_FAST == [(2, 1, 1), (63, 16, 16), (64, 16, 16), (65, 7, 12), (130, 12, 7), (513, 16, 1), (1024, 8, 8), (4099, 16, 16)]
+    assert DK.MLP_GENERAL == [(5, 17, 3), (77, 24, 16), (256, 33, 17), (257, 8, 40), (300, 64, 64)] and DK.MLP_EVAL_ONLY == [(1, 16, 16)]
+    assert all(R.mlp_fast(H, L) for _, H, L in DK.MLP_FAST + DK.MLP_EVAL_ONLY) and not any(R.mlp_fast(H, L) for _, H, L in DK.MLP_GENERAL)
+    nblk = [cd(B, R.MLP_RB) for B, _, _ in DK.MLP_FAST]
+    assert nblk == [1, 1, 1, 2, 3, 9, 16, 65] and [n % 8 for n in nblk] == [1, 1, 1, 2, 3, 1, 0, 1]
+    assert any(L > H for _, H, L in DK.MLP_FAST) and any(H > L for _, H, L in DK.MLP_FAST)
+    assert (257, 8, 40) in DK.MLP_GENERAL and 8 <= R.MLP_HP < 40                        # H <= 16 alone does not select the fast set
+    assert {B for B, _, _ in DK.MLP_GENERAL} >= {5, 256, 257}                            # under, at and over one pass of a block's 256 threads
+    for B, H, L in DK.MLP_FAST + DK.MLP_GENERAL + DK.MLP_EVAL_ONLY:
+        part = cd(B, R.MLP_RB) * max(2 * 2 * R.MLP_HP, 3 * R.MLP_HP + R.MLP_HP * R.MLP_HP) if R.mlp_fast(H, L) else 0
+        assert lib.coskad_mlp_head_ws_floats(B, H, L) == 2 * H + 2 + part, (B, H, L)
+
+
+def _mlp_shapes():
+    import test_gpu_decoder_kernels as DK
+    return [(s, t) for s in DK.MLP_FAST + DK.MLP_GENERAL for t in (True, False)] + [(s, False) for s in DK.MLP_EVAL_ONLY]
+
+
+@pytest.mark.parametrize("shape,training", _mlp_shapes())
+def test_mlp_kink_share_of_the_reference_alone(shape, training):
+    """the mlp_head test leaves out of dy the elements whose double y2 is non-zero and within the forward's and the backward's rounding
+    bound of 0; from the reference alone their share is within the test's cap at every shape and mode it runs, every reference value
+    and bound is finite, and the planted features are what the test says: an exact 0 is never a kink"""
+    import test_gpu_decoder_kernels as DK
+    B, H, L = shape
+    c = DK.mlp_case(B, H, L, training)
+    assert c["share"] <= DK.KINK_CAP, c["share"]
+    assert all(np.isfinite(v).all() for v in c["ref"].values()) and all(np.isfinite(v).all() and (v >= 0).all() for v in c["bound"].values())
+    if H >= R.MLP_PLANTS:
+        assert not c["kink"][:, 1].any() and not c["kink"][:, 2].any()
+        assert not c["ref"]["dy"][:, 1].any() and not c["ref"]["dy"][:, 2].any() and c["ref"]["dgamma"][2] != 0 and c["ref"]["dgamma"][1] == 0
+
+
+@pytest.mark.parametrize("Co,TV,n", [(1, 1, 1), (3, 63, 37), (3, 257, 1), (32, 204, 37)])
+def test_fold_case_bounds_are_finite_and_ordered(Co, TV, n):
+    """fold_case on the host: every reference value finite, every bound finite and non-negative, the float64 outputs' bounds far below
+    the float32 ones', and the all-zero branch's variance exactly 0"""
+    import test_gpu_decoder_kernels as DK
+    c = DK.fold_case(Co, TV, n)
+    assert all(np.isfinite(v).all() for v in c["ref"].values()) and all(np.isfinite(v).all() and (v >= 0).all() for v in c["bound"].values())
+    for q in ("xbar", "xx"):
+        assert (c["bound"][q] <= 1e-9 * np.maximum(np.abs(c["ref"][q]).max(), 1.0)).all()
+    if Co >= 2:
+        assert float(c["var"][0, 1]) == 0.0
